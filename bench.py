@@ -8,12 +8,16 @@ fusion -> masked-MSE loss -> backward -> (N>1: RCCL gradient all-reduce) -> clip
 synthetic, generated once and resident in HBM before the timed region.  `--config cfg3|cfg4|cfg5` runs the other
 BASELINE.json configurations (SURVEY 8d shapes) through the same measurement.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--full] [--dump-outputs DIR]
 
 For N>1 the driver launches one rank per GPU with torch.distributed.run; entities shard across ranks (weak scaling: 64
-windows per GPU).  Rank 0 prints ONE JSON line: metric/value, `roofline` (dominant MFMA GEMM, timed live), `roofline_hbm`
-(the gather / mask path as GB/s against 8 TB/s), `sweep` (windows per GPU 64..4096), `ms_per_step_fp32` (the 1e-4
-parity mode), `dropin` (the zero-edit main.py seam: compute_all_losses + torch Adam, eager), `cpu_baseline`.
+windows per GPU).  Rank 0 prints ONE JSON line: metric/value and `ms_per_step` of the K timed steps.  A plain run does only
+that: set up, W warm-up steps, K timed steps, the line.  `--full` adds the companion measurements: `step_stats` (the step
+replayed in blocks), `roofline` (dominant MFMA GEMM, timed live), `roofline_hbm` (the gather / mask path as GB/s against
+8 TB/s), `sweep` (windows per GPU 64..4096), `ms_per_step_fp32` (the 1e-4 parity mode), `dropin` (the zero-edit main.py
+seam: compute_all_losses + torch Adam, eager), `cpu_baseline`; `--no-roofline`, `--no-extras`, `--no-cpu-baseline` drop
+single legs of it.  `--dump-outputs DIR` writes what one step of the timed path computes from the fixed inputs and initial
+state (replayed after the timed region: dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -533,6 +537,54 @@ def time_steps(step, steps, warmup, barrier):
     return time.perf_counter() - t0, host, loss
 
 
+DUMP_MAX_ELEMS = 1 << 21     # --dump-outputs: elements per array (three float32 arrays + the float64 sample index: 42 MB, under 64 MB)
+
+
+def dump_outputs(w, step, snap, out_dir):
+    """--dump-outputs: what one step of the timed path computes from the benchmark's fixed inputs, as out_dir/<name>.npy.  The timed
+    steps train, and a run of them is chaotic in rounding: the weight gradients are summed with atomics, in no fixed order, and Adam's
+    normalised update turns those last-bit differences into visible ones within a few steps (two runs of 5 + 20 cfg2 steps: losses
+    0.4 % apart; of one step: the same loss, parameters within 1e-9).  So after the timed region the engine's own step is replayed once
+    more, untimed, from `snap` -- the trainer's state before the warm-up: seeded weights, zero moments, the first step's dropout and
+    Adam counters -- on the same batch, and what that step hands its caller is written: `loss` (float64) and the updated state,
+    `params`, `exp_avg`, `exp_avg_sq` (float32; after one step exp_avg is 0.1 x the clipped gradient), each the concatenation of the
+    backbone's then the fusion's named trainable parameters (a layout independent of the flat buffers').  Arrays longer than
+    DUMP_MAX_ELEMS hold the same fixed sample of positions, sorted, from a seeded generator (`sample_index`, float64).  Call on every
+    rank (the step may hold collectives; a sharded optimizer gathers its moments); out_dir None: take part without writing."""
+    t = w.trainer
+    if hasattr(step, "reset"):
+        step.reset()               # FlagStep: drop the optimizer step the last timed replay left pending (it is undone below)
+    t.restore(snap)
+    loss = step()
+    sd = t.state_dict()            # (applies the step's held-back optimizer update; full flat moments on every rank)
+    if out_dir is None:
+        return
+    flat = t.flat_param.detach().cpu().numpy()
+    n_flat = flat.shape[0]
+    owned = {id(p) for b in t.buckets for p in b}
+    seen, runs = set(), []
+    base = t.flat_param.data_ptr()
+    for mod in (w.model, w.fusion):
+        for name, p in mod.named_parameters():
+            if id(p) not in owned or id(p) in seen:
+                continue
+            seen.add(id(p))
+            off = (p.data_ptr() - base) // t.flat_param.element_size()
+            if off < 0 or off + p.numel() > n_flat:
+                raise RuntimeError(f"--dump-outputs: parameter {name} does not live in the trainer's flat buffer")
+            runs.append(np.arange(off, off + p.numel(), dtype=np.int64))
+    pos = np.concatenate(runs)
+    os.makedirs(out_dir, exist_ok=True)
+    if pos.shape[0] > DUMP_MAX_ELEMS:
+        sel = np.sort(np.random.default_rng(0).choice(pos.shape[0], DUMP_MAX_ELEMS, replace=False))
+        pos = pos[sel]
+        np.save(os.path.join(out_dir, "sample_index.npy"), sel.astype(np.float64))
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(float(loss.detach().float().item()), dtype=np.float64))
+    np.save(os.path.join(out_dir, "params.npy"), flat[pos].astype(np.float32))
+    for k in ("exp_avg", "exp_avg_sq"):
+        np.save(os.path.join(out_dir, f"{k}.npy"), sd[k].detach().cpu().numpy()[pos].astype(np.float32))
+
+
 def graph_kernel_us(fn, reps=50, replays=10):
     """mean device time of one `fn()` (which enqueues kernels on the current stream): `reps` calls captured in one hipGraph,
     HIP events around replays -- launch latency excluded, the figure rocprofv3 reports as the kernels' duration"""
@@ -893,9 +945,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS), help="BASELINE.json configuration (cfg2 = the headline metric)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sweep / fp32 / drop-in legs (cfg2, 1 GPU only anyway)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, the companion measurements too: step_stats, roofline, roofline_hbm, the sweep / "
+                         "padded / fp32 / drop-in legs, cpu_baseline (a plain run times the steps and prints the line, nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left its caller (loss, updated parameters, Adam moments) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline legs")
+    ap.add_argument("--no-extras", action="store_true", help="--full without step_stats and the sweep / fp32 / drop-in legs (cfg2, 1 GPU only anyway)")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying hipGraphs")
     ap.add_argument("--gemm-config", type=lambda x: int(x, 0), default=0,
                     help="A/B measurements only: immtsf_debug_gemm_config bits (0x100 no XCD order, 0x2000 no specialised wgrad kernel)")
@@ -941,6 +998,8 @@ def main():
     ap.add_argument("--windows-per-gpu", type=int, default=B_PER_GPU,
                     help="exploration only (the `sweep` field covers 64..4096): the metric is quoted on 64 windows per GPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     W = args.windows_per_gpu
     # stdout carries exactly one line, the JSON result: everything else a module prints (the fusion registry announces
     # its choices like the reference does) goes to stderr
@@ -1056,6 +1115,7 @@ def main():
         _side = torch.cuda.Stream(device=dev)
         _side.wait_stream(torch.cuda.current_stream())
         torch.cuda.set_stream(_side)
+    snap0 = trainer.snapshot() if args.dump_outputs else None      # (the state the dump's step starts from: dump_outputs)
     elapsed, host_enqueue_s, loss = time_steps(step, args.steps, args.warmup, barrier)
     if dist_on:
         import torch.distributed as dist
@@ -1085,10 +1145,12 @@ def main():
     assert torch.isfinite(loss).all(), "loss is not finite"
     ms_per_step = elapsed / args.steps * 1e3
     windows_per_s = W * world * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(w, step, snap0, args.dump_outputs if rank == 0 else None)
     # the contract's K steps are a ~15 ms sample at cfg2: the same step is replayed in blocks of 20 (>= 200 replays, N = 1 only: no
     # extra collectives are spent on it) and the block means are reported next to `ms_per_step` -- median and spread, not `value`
     step_stats = None
-    if world == 1 and use_graph and not args.no_extras:
+    if args.full and world == 1 and use_graph and not args.no_extras:
         blocks = []
         for _ in range(12):
             el, _, _ = time_steps(step, 20, 0, torch.cuda.synchronize)
@@ -1098,13 +1160,13 @@ def main():
                       "max_ms": round(blocks[-1], 4)}
 
     roofline = hbm = None
-    if not args.no_roofline and rank == 0:
+    if args.full and not args.no_roofline and rank == 0:
         roofline = gemm_roofline(w, lib, args)
         hbm = hbm_roofline(w, lib, roofline)
 
     extras = {}
     grad_bytes = trainer.grad_bytes()
-    if rank == 0 and world == 1 and args.config == "cfg2" and not args.no_extras and W == B_PER_GPU and not args.no_graph:
+    if args.full and rank == 0 and world == 1 and args.config == "cfg2" and not args.no_extras and W == B_PER_GPU and not args.no_graph:
         w.close()
         del step
         # windows per GPU: where the step leaves the launch-bound regime (the >= 40 % MFMA target presumes a batch size)
@@ -1159,10 +1221,10 @@ def main():
         config.precision = args.precision
 
     cpu = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1 and args.config == "cfg2":
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1 and args.config == "cfg2":
         cpu_b, _ = synth_batch(100, B_PER_GPU)
         cpu = cpu_baseline(cpu_b)
-    elif not args.no_cpu_baseline and rank == 0 and world == 1:
+    elif args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         cpu = cpu_baseline_fusion(args.config)
 
     if rank == 0:

@@ -1,12 +1,11 @@
 """The mirrored packages must coexist with a reference tree placed AFTER them on sys.path: modules this build does not
 mirror keep resolving to the reference, and mirrored modules re-export the reference names they do not define
 (immtsf/dropin.py).  Run in subprocesses so sys.path / sys.modules of the test session stay untouched."""
+import json
 import os
 import subprocess
 import sys
 import textwrap
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "imm-tsf_amd")
@@ -47,17 +46,28 @@ def test_standalone_import_without_any_reference_tree():
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference checkout (build container only)")
+def _reference_standin(root):
+    """a stand-in of the reference tree under `root`: every module its packages hold, each defining the public names the reference's
+    module defines as placeholder classes (tests/golden/reference_layout.json, written by tests/golden/make_golden_layout.py)"""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_layout.json")) as fh:
+        layout = json.load(fh)
+    for pkg, modules in layout.items():
+        (root / pkg).mkdir(parents=True)
+        for mod, names in modules.items():
+            (root / pkg / f"{mod}.py").write_text("".join(f"{n} = type({n!r}, (), {{'__module__': __name__}})\n" for n in names))
+    return layout
+
+
 def test_reference_main_imports_resolve_with_this_tree_in_front(tmp_path):
-    """the import block of the reference's main.py (lines 16-40), with stubs for its optional third-party packages"""
-    stubs = tmp_path / "stubs"
-    stubs.mkdir()
-    for name in ("reformer_pytorch", "stribor", "geotorch", "torchdiffeq", "seaborn", "prettytable", "tsfm_public"):
-        (stubs / f"{name}.py").write_text("class _Any:\n    def __init__(self, *a, **k): pass\n"
-                                          "def __getattr__(name):\n    return _Any\n")
-    r = _run("""
-        import os
-        os.environ.setdefault('HF_HUB_OFFLINE', '1')
+    """the import block of the reference's main.py (lines 16-40) with this tree in front of a stand-in of the reference's; and every
+    public name of a reference module this build mirrors resolves on the mirrored module (defined here or re-exported)"""
+    behind = tmp_path / "reference"
+    layout = _reference_standin(behind)
+    mirrored = sorted(f"{pkg}.{mod}" for pkg, modules in layout.items() for mod in modules
+                      if mod != "__init__" and os.path.isfile(os.path.join(PKG, pkg, f"{mod}.py")))
+    assert "models.tPatchGNN" in mirrored and "lib.evaluation" in mirrored and "layers.Embed" in mirrored
+    r = _run(f"""
+        import importlib, json
         import lib.utils as utils
         from lib.evaluation import compute_all_losses, evaluation
         from lib.parse_datasets import parse_datasets
@@ -68,8 +78,15 @@ def test_reference_main_imports_resolve_with_this_tree_in_front(tmp_path):
         from fusions.FusionModel import FusionModel
         from fusions.load_llm import get_context_window_size
         import models.tPatchGNN as m, lib.parse_datasets as p, fusions.FusionModel as f
-        assert 'imm-tsf_amd' in m.__file__ and 'imm-tsf_amd' in f.__file__ and '/root/reference' in p.__file__
+        assert 'imm-tsf_amd' in m.__file__ and 'imm-tsf_amd' in f.__file__ and {str(behind)!r} in p.__file__
         assert 'imm-tsf_amd' in evaluation.__code__.co_filename
+        layout = json.load(open({os.path.join(ROOT, "tests", "golden", "reference_layout.json")!r}))
+        for name in {mirrored!r}:
+            mod = importlib.import_module(name)
+            assert 'imm-tsf_amd' in mod.__file__, name
+            pkg, leaf = name.split('.')
+            missing = [n for n in layout[pkg][leaf] if not hasattr(mod, n)]
+            assert not missing, (name, missing)
         print('ok')
-        """, os.pathsep.join(["/root/reference", str(stubs)]))
+        """, str(behind))
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-3000:]

@@ -10,7 +10,7 @@ done
 IMMTSF_PMC_COMMIT=$C PMC_TAG=r04 bash tools/pmc_pass_r04.sh 2>&1 | tail -4
 mkdir -p profiles; cp $O/r04_pmc_traffic.json $O/r04_pmc_traffic_w4096.json profiles/
 timeout 300 python3 tools/flag_timeline.py 64 40 > $O/r04_flag_timeline.txt 2>&1; tail -5 $O/r04_flag_timeline.txt
-timeout 1500 python3 bench.py > $O/r04_bench_line.json 2> $O/r04_bench.err; tail -2 $O/r04_bench.err
+timeout 1500 python3 bench.py --full > $O/r04_bench_line.json 2> $O/r04_bench.err; tail -2 $O/r04_bench.err
 python3 -c "
 import json; d=json.load(open('$O/r04_bench_line.json')); r=d['roofline']
 print('ms', d['ms_per_step'], 'value', d['value'], d['engine']); print('roofline', r['kernel'][:100], r['avg_launch_us'], r['frac'], r['traffic'], r['algorithmic_bytes'])

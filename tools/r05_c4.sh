@@ -5,7 +5,7 @@ mkdir -p $out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout 900 python -m pytest tests/test_gpu_backbone.py tests/test_gpu_train.py -x -q -m gpu -k "timesnet or TimesNet or cfg4 or period or inception or cfg3_flag" > $out/test.log 2>&1; echo "tests rc=$?" | tee -a $out/summary.txt
 tail -3 $out/test.log | cut -c1-220 | tee -a $out/summary.txt
-timeout 600 python bench.py --config cfg4 --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_cfg4.json 2> $out/bench_cfg4.err
+timeout 600 python bench.py --full --config cfg4 --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_cfg4.json 2> $out/bench_cfg4.err
 python - <<PY | tee -a $out/summary.txt
 import json
 try:

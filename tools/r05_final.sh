@@ -32,7 +32,7 @@ if [[ $PART == *a* ]]; then
 fi
 if [[ $PART == *b* ]]; then
   mkdir -p profiles; cp $O/r05final/r05_pmc_traffic*.json $O/r05final/r05_sq_w*.json profiles/ 2>/dev/null
-  timeout 1800 python3 bench.py > $O/r05final/r05_bench_line.json 2> $O/r05final/r05_bench.err; tail -2 $O/r05final/r05_bench.err
+  timeout 1800 python3 bench.py --full > $O/r05final/r05_bench_line.json 2> $O/r05final/r05_bench.err; tail -2 $O/r05final/r05_bench.err
   python3 -c "
 import json; d=json.load(open('$O/r05final/r05_bench_line.json')); r=d['roofline']
 print('ms', d['ms_per_step'], 'value', d['value'], d['engine']); print('roofline', r['kernel'][:100], r['avg_launch_us'], r['frac'], r['traffic'], r['algorithmic_bytes'], 'mfma_busy', r.get('mfma_busy'))
@@ -46,11 +46,11 @@ import json
 for f in ('force_dist','single'):
     d=json.loads(open('$O/r05final/r05_bench_line_%s.json'%f).read().strip().splitlines()[-1]); print(f, d['ms_per_step'], d['config']['grad_allreduce'][:400])" | tee -a $S
   for c in cfg3 cfg4 cfg5; do
-    timeout 900 python3 bench.py --config $c --steps 20 --warmup 5 > $O/r05final/r05_bench_line_$c.json 2> $O/r05final/r05_bench_$c.err
+    timeout 900 python3 bench.py --full --config $c --steps 20 --warmup 5 > $O/r05final/r05_bench_line_$c.json 2> $O/r05final/r05_bench_$c.err
     python3 -c "
 import json; d=json.load(open('$O/r05final/r05_bench_line_$c.json')); r=d['roofline']; print('$c', d['ms_per_step'], d['engine'], 'host', d['host_enqueue_ms_per_step'], 'roofline', r['frac'], r['avg_launch_us'], r['kernel'][:90], 'cpu', (d.get('cpu_baseline') or {}).get('value'))" | tee -a $S
   done
-  timeout 900 python3 bench.py --config cfg5 --fusion-only --steps 10 --warmup 3 --no-cpu-baseline > $O/r05final/r05_bench_line_cfg5_fusion_only.json 2> $O/r05final/r05_bench_cfg5_fo.err
+  timeout 900 python3 bench.py --full --config cfg5 --fusion-only --steps 10 --warmup 3 --no-cpu-baseline > $O/r05final/r05_bench_line_cfg5_fusion_only.json 2> $O/r05final/r05_bench_cfg5_fo.err
   python3 -c "
 import json; d=json.load(open('$O/r05final/r05_bench_line_cfg5_fusion_only.json')); print('cfg5 fusion-only', d['ms_per_step'], d['roofline']['frac'], d['roofline']['kernel'][:90])" | tee -a $S
 fi

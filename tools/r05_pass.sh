@@ -11,7 +11,7 @@ if [ "$2" != "quick" ]; then
   timeout 1500 python -m pytest tests -x -q -m gpu --deselect tests/test_gpu_train.py > $out/test_all.log 2>&1; echo "other tests rc=$?" | tee -a $out/summary.txt
   tail -3 $out/test_all.log | tee -a $out/summary.txt
 fi
-timeout 600 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" | tee -a $out/summary.txt
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" | tee -a $out/summary.txt
 python - <<PY | tee -a $out/summary.txt
 import json
 try:
