@@ -17,12 +17,6 @@ precision = os.environ.get("IMMTSF_PRECISION", "fp32")
 nan_check = os.environ.get("IMMTSF_NAN_CHECK", "deferred")
 
 
-# While set, backward passes whose parameter gradients go to FlatTrainer sinks only compute the DATA gradients and queue
-# the parameter-gradient work in immtsf.ops (run_deferred() enqueues it): immtsf.train.PhasedStep uses it to take that
-# work off the path between the loss and the backbone's backward.  Off everywhere else.
-defer_param_grads = False
-
-
 def precision_code(p=None) -> int:
     p = precision if p is None else p
     if p not in _PRECISIONS:
@@ -107,9 +101,6 @@ seam_graph = True
 # notes in bf16 mode), "fold" = the folded form wherever its limits hold, "mix" = the mix-first variant wherever ITS limits hold (bf16
 # mode, one head, T <= 32), "chain" = the reference's GEMM chain as written
 t2v_form = "auto"
-# immtsf.train.FlagStep <-> MMFXRankQLossFn: address of the device flag that says "dY_ts is ready" (None: nobody is waiting)
-head_done_flag = None
-head_dy_ptr = None        # ... and, when a head took the flag: the address of the dY_ts buffer its kernel publishes
 # TTF_T2V_XAttn on PackedNotes: use the batch's prebuilt ragged index (PackedNotes.index(), built once per batch) instead of deriving
 # it inside every forward; False: the call derives it (two launches at its head) -- the cross-check
 note_index = True
@@ -124,13 +115,3 @@ z_handover = os.environ.get("IMMTSF_Z_HANDOVER", "1") != "0"
 # FullAttention over <= 32 positions with heads up to 256 wide as one kernel per direction (csrc/attn_mid.hip); False: batched GEMMs +
 # row softmax
 attn_mid = True
-# a torch.cuda.Stream on which MMF_XAttn_Add's fold (parameters only) may run ahead of the text side (None: in line); the stream
-# must be ordered behind the previous optimizer step (immtsf.train.FlagStep forks it at the start of the captured step)
-fold_stream = None
-param_tail = None        # FlagStep: {"flag": (address, time-out report address), "jobs": []} -- ops whose parameter-gradient tail nothing but the
-                         # optimizer waits for (MMF_XAttn_Add's chain rule through the fold) set the flag behind the data half and
-                         # leave the tail as a job (a callable taking a raw stream) for the branch that has time to spare
-sched_gate = None        # GraphedStep: (flag address, time-out report address) -- TTF_T2V_XAttn's backward sets the flag behind its row-bound
-                         # kernels, the patch encoder's backward (parameter gradients only, on the backbone's stream) spins on it first
-sched_armed = None       # stream of the TTF_T2V_XAttn forward that will set it (None: nobody will -- nobody may wait)
-fold_flag = None          # (flag address, time-out report address): hand the fold over through a device flag instead of a stream event

@@ -10,7 +10,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, config
+from . import _lib, config, step_plan
 from ._lib import DecoderParams, FusionCfg, GCNParams, GRParams, NoteIndex, RecAvgParams, T2VParams, TTCNParams, XAddParams, check, ptr, stream_ptr
 
 
@@ -270,11 +270,8 @@ class TTFT2VXAttnFn(torch.autograd.Function):
             _reg_put(_handover, E, (cfg, bool(cfg.form & _lib.FORM_HALF_OUT)))
         ctx.cfg, ctx.ws, ctx.src_rows = cfg, ws, src_rows
         # scheduling hint of a two-stream captured step (immtsf.train.GraphedStep): this call's backward will set the gate behind its
-        # row-bound kernels; remember who promised, so that nobody waits for a flag nobody sets
-        ctx.gate = None
-        if config.sched_gate is not None and training:
-            ctx.gate = config.sched_gate[0]
-            config.sched_armed = torch.cuda.current_stream().cuda_stream
+        # row-bound kernels; the plan remembers who promised, so that nobody waits for a flag nobody sets
+        ctx.gate = step_plan.current().arm_gate() if training else None
         ctx.save_for_backward(notes, tau, *[p if p is not None else notes.new_empty(0) for p in params])
         ctx.none_mask = [p is None for p in params]
         ctx.sinks = _sinks_of(params)
@@ -320,27 +317,21 @@ class TTFT2VXAttnFn(torch.autograd.Function):
                       "ttf_t2v_xattn_backward")
             cfg.bwd_phase = 0
 
-        tail = config.param_tail
-        split = (tail is not None and tail.get("ttf_flag") is not None and tail.get("defer", 0) > 0 and not ctx.folded and
-                 all(r is None for r in rets))
-        if split:
+        plan = step_plan.current()
+        if plan.ttf_flag is not None and not ctx.folded and all(r is None for r in rets):
             # a step with a parameter-only branch (immtsf.train.FlagStep): this stream runs the data path and the LAST phase's weight
             # gradients; the weight gradients of phases A and B -- whose inputs exist long before the end -- leave as one grouped launch
             # on that branch, behind a flag that says phase B's data path has run.  Their buckets' hooks fire there.
             call(_lib.BWD_PHASE_A | _lib.BWD_PHASE_B)
-            flag, err = tail["ttf_flag"]
-            check(lib.immtsf_flag_set(flag, stream_ptr()), "flag_set")
-            call(_lib.BWD_PHASE_C | _lib.BWD_WGRAD_C)
             early = [h for ph, h in hooks if ph < 2]
-            keep = (notes, tau, dE, sc, ps, gs, params, grads, dE_h, lowrank)   # the job runs later, on another stream: everything it touches stays alive
 
-            def job(stream, keep=keep):
-                check(lib.immtsf_flag_wait(flag, err, 50, stream), "flag_wait")
+            def wgrad(stream):
                 call(_lib.BWD_WGRAD_A | _lib.BWD_WGRAD_B, stream)
                 token = object()
                 for i_, h in enumerate(early):
                     _fire(h, (token, i_, len(early)))
-            tail["jobs"].append(job)
+            plan.defer_wgrad(wgrad, keep=(notes, tau, dE, sc, ps, gs, params, grads, dE_h, lowrank), ttf=True)
+            call(_lib.BWD_PHASE_C | _lib.BWD_WGRAD_C)
             for ph, h in hooks:
                 if ph == 2:
                     _fire(h)
@@ -535,18 +526,6 @@ class MMFXAttnKVFn(torch.autograd.Function):
         return (dE, None, None, None) + tuple(rets[1:5])
 
 
-_deferred = []          # parameter-gradient work postponed by a backward (config.defer_param_grads): closures
-
-
-def run_deferred():
-    """enqueue (on the current stream) the parameter-gradient work that backward passes postponed while
-    `immtsf.config.defer_param_grads` was set (immtsf.train.PhasedStep moves it off the path to the backbone's backward)"""
-    work = list(_deferred)
-    del _deferred[:]
-    for fn in work:
-        fn()
-
-
 def mmf_xattn_q_fold(Y_C, d, H, precision, params):
     """the query half's per-step product weights (see immtsf_mmf_xattn_q_fold): a flat fp32 tensor; no autograd -- the
     parameters' gradients come out of MMFXAttnQFn.backward by the chain rule"""
@@ -593,7 +572,7 @@ class MMFXAttnQFn(torch.autograd.Function):
         sc = _bytes(lib.immtsf_mmf_xattn_q_scratch_bytes(C.byref(ctx.cfg)), Y.device)
         ps, gs = _struct(XAddParams, params), _struct(XAddParams, grads)
         # the parameter gradients can only be postponed when they go to sinks (autograd gets None for them either way)
-        defer = bool(config.defer_param_grads) and all(r is None for r in rets)
+        defer = step_plan.current().hold_params and all(r is None for r in rets)
         cfg, ws, fold = ctx.cfg, ctx.ws, ctx.fold
         dKV_h = None
         if _bf16_dataflow(cfg.precision, cfg.d):
@@ -612,7 +591,7 @@ class MMFXAttnQFn(torch.autograd.Function):
                 check(lib.immtsf_mmf_xattn_q_backward_params(C.byref(cfg), C.byref(ps), ptr(keep[0]), ptr(keep[1]), ptr(fold), ptr(ws),
                                                              ws.numel(), ptr(sc), sc.numel(), C.byref(gs), stream_ptr()),
                       "mmf_xattn_q_backward_params")
-            _deferred.append(finish)
+            step_plan.current().defer_params(finish)
         return (dY, dKV, None, None, None, None, None, None, None, None, rets[0]) + tuple(rets[3:])
 
 
@@ -659,30 +638,22 @@ class MMFXRankPFn(torch.autograd.Function):
             if ho[1] and E_h is None:
                 raise _lib.ImmtsfError("Z was handed over as its bf16 image alone (config.z_handover) but the image is gone")
             ctx.lowrank = bool(lib.immtsf_ttf_t2v_xattn_accepts_lowrank(C.byref(ho[0]), pw))
-        # the fold depends on parameters only: with config.fold_stream (immtsf.train.FlagStep) it runs on that stream, beside the
+        # the fold depends on parameters only: in a step that offers a fold stream (immtsf.train.FlagStep) it runs there, beside the
         # text side's own forward, and this stream picks it up just before the projection
-        L = config.fold_stream
-        if L is not None:
-            cur = torch.cuda.current_stream()
-            ws.record_stream(L)
-            bHO.record_stream(L)
+        def fold(stream):
             if proj is not None:
                 check(lib.immtsf_mmf_xrank_fold_z(C.byref(cfg), C.byref(ps), ptr(proj[0]), ptr(proj[1]), ptr(bHO), ptr(ws), ws.numel(),
-                                                  L.cuda_stream), "mmf_xrank_fold_z")
+                                                  stream), "mmf_xrank_fold_z")
             else:
-                check(lib.immtsf_mmf_xrank_fold(C.byref(cfg), C.byref(ps), ptr(bHO), ptr(ws), ws.numel(), L.cuda_stream), "mmf_xrank_fold")
-            if config.fold_flag is not None:      # hand-over through a device flag (no graph edge): (flag address, time-out report address)
-                check(lib.immtsf_flag_set(config.fold_flag[0], L.cuda_stream), "flag_set")
-                check(lib.immtsf_flag_wait(config.fold_flag[0], config.fold_flag[1], 50, cur.cuda_stream), "flag_wait")
-            else:
-                cur.wait_stream(L)
+                check(lib.immtsf_mmf_xrank_fold(C.byref(cfg), C.byref(ps), ptr(bHO), ptr(ws), ws.numel(), stream), "mmf_xrank_fold")
+        folded = 1 if step_plan.current().fold(fold, ws, bHO) else 0
         if proj is not None:
             _need_gpu(*proj)
             check(lib.immtsf_mmf_xrank_p_forward_z(C.byref(cfg), C.byref(ps), ptr(proj[0]), ptr(proj[1]), ptr(E), ptr(P), ptr(bHO), ptr(ws),
-                                                   ws.numel(), 0 if L is None else 1, stream_ptr()), "mmf_xrank_p_forward_z")
+                                                   ws.numel(), folded, stream_ptr()), "mmf_xrank_p_forward_z")
         else:
             check(lib.immtsf_mmf_xrank_p_forward(C.byref(cfg), C.byref(ps), ptr(E), ptr(P), ptr(bHO), ptr(ws), ws.numel(),
-                                                 0 if L is None else 1, stream_ptr()), "mmf_xrank_p_forward")
+                                                 folded, stream_ptr()), "mmf_xrank_p_forward")
         ctx.cfg, ctx.ws = cfg, ws
         ctx.sinks = _sinks_of(params)
         ctx.done_hook = done_hook          # the block's gradients are final once THIS half's backward has run
@@ -722,10 +693,14 @@ class MMFXRankPFn(torch.autograd.Function):
 
         ws0 = ctx.ws
 
-        def pre(stream):           # "_z" form: the parameter-only step in front of the chain (dW_fold from dWc; proj_out's gradients)
-            if proj is not None:
+        def params_chain(stream, first=0, last=3, keep=(params, grads)):
+            # launches first..last of the parameter chain; "_z" form: the parameter-only step in front of it (dW_fold from dWc;
+            # proj_out's gradients) with the first
+            if proj is not None and first == 0:
                 check(lib.immtsf_mmf_xrank_p_backward_pre_z(C.byref(cfg), ptr(proj[0]), ptr(proj[1]), ptr(ws0), ws0.numel(), ptr(sc), sc.numel(),
                                                             ptr(pgrads[0]), ptr(pgrads[1]), stream), "mmf_xrank_p_backward_pre_z")
+            check(lib.immtsf_mmf_xrank_p_backward_params(C.byref(cfg), C.byref(ps), ptr(dbHO), ptr(ws0), ws0.numel(), ptr(sc), sc.numel(),
+                                                         C.byref(gs), first, last, stream), "mmf_xrank_p_backward_params")
 
         def data_half(part=0, stream=None):
             # part 0: dZ and the chain's seeds; "_z" form only: BWD_PHASE_A = dZ alone, BWD_WGRAD_A = the seeds (dWc, dbc) alone
@@ -739,40 +714,27 @@ class MMFXRankPFn(torch.autograd.Function):
             else:
                 check(lib.immtsf_mmf_xrank_p_backward_data(C.byref(cfg), C.byref(ps), ptr(E), ptr(dP), ptr(dE), ptr(ctx.ws), ctx.ws.numel(), ptr(sc),
                                                            sc.numel(), stream_ptr()), "mmf_xrank_p_backward_data")
-        tail = config.param_tail
-        if tail is not None and all(r is None for r in rets[:9]) and tail["defer"] > 0:
+        plan = step_plan.current()
+        if all(r is None for r in rets[:9]) and plan.defer > 0:
             # every gradient goes straight to its sink: the last `defer` launches of the parameter chain are left to the other branch
-            k = 3 - min(3, int(tail["defer"]))
+            k = 3 - min(3, int(plan.defer))
             # the "_z" form with the whole chain deferred: this stream (the text side's dependent chain) only forms dZ; the chain's
             # seeds dWc = dP^T Z -- parameter-gradient work too -- open the other branch's jobs
             seeds_later = proj is not None and k == 0
             data_half(_lib.BWD_PHASE_A if seeds_later else 0)
             if seeds_later:
-                tail["jobs"].append(lambda stream, keep=(E, dP): data_half(_lib.BWD_WGRAD_A, stream))
-            ws = ctx.ws
-
-            def run_params(stream, first, last, cfg=cfg, ps=ps, gs=gs, dbHO=dbHO, ws=ws, sc=sc, keep=(params, grads)):
-                check(lib.immtsf_mmf_xrank_p_backward_params(C.byref(cfg), C.byref(ps), ptr(dbHO), ptr(ws), ws.numel(), ptr(sc), sc.numel(),
-                                                             C.byref(gs), first, last, stream), "mmf_xrank_p_backward_params")
-
+                plan.jobs.append(lambda stream, keep=(E, dP): data_half(_lib.BWD_WGRAD_A, stream))
             if k > 0:
-                pre(stream_ptr())
-                run_params(stream_ptr(), 0, k)
-            check(lib.immtsf_flag_set(tail["flag"][0], stream_ptr()), "flag_set")
-            tail["flag_set"] = True          # (the branch that runs the jobs waits for the flag only when somebody set it)
-            if k > 0:
-                tail["jobs"].append(lambda stream: run_params(stream, k, 3))
-            else:
-                tail["jobs"].append(lambda stream: (pre(stream), run_params(stream, 0, 3)))
+                params_chain(stream_ptr(), 0, k)
+            plan.set_tail()
+            plan.jobs.append(lambda stream: params_chain(stream, k, 3))
             # the block's gradients are final behind the LAST of those launches: its hook (data parallel: the bucket's announcement)
             # fires there, on the stream that runs them
             hook, ctx.done_hook = ctx.done_hook, None
-            tail["jobs"].append(lambda stream, hook=hook: _fire(hook))
+            plan.jobs.append(lambda stream, hook=hook: _fire(hook))
         else:
             data_half()
-            pre(stream_ptr())
-            check(lib.immtsf_mmf_xrank_p_backward_params(C.byref(cfg), C.byref(ps), ptr(dbHO), ptr(ctx.ws), ctx.ws.numel(), ptr(sc), sc.numel(),
-                                                         C.byref(gs), 0, 3, stream_ptr()), "mmf_xrank_p_backward_params")
+            params_chain(stream_ptr())
         if dE_h is not None:
             _shadow_put(dE, dE_h)
         if lowrank:
@@ -868,11 +830,8 @@ class MMFXRankQLossFn(torch.autograd.Function):
             dP_h = torch.empty(dP.shape, dtype=torch.bfloat16, device=dP.device)
             cfg.out_h = dP_h.data_ptr()
         # immtsf.train.FlagStep: the device flag the backbone's stream waits on before its backward is published by this kernel as
-        # soon as dY_ts is complete (config.head_done_flag is consumed: the caller sees None and skips its own flag_set)
-        flag = None
-        if y_dense and config.head_done_flag is not None:
-            flag, config.head_done_flag = config.head_done_flag, None
-            config.head_dy_ptr = dY.data_ptr()
+        # soon as dY_ts is complete (the step's head flag is taken: the caller skips its own flag_set)
+        flag = step_plan.current().take_head_flag(dY) if y_dense else None
         check(lib.immtsf_mmf_xrank_q_train(C.byref(cfg), ptr(ln_w), ptr(ln_b), ptr(Y), ptr(P), ptr(bHO), ptr(M_u8), ptr(truth), ptr(mask),
                                            ptr(cnt), 1.0, None, ptr(loss), ptr(dY), ptr(dP), ptr(dbHO), ptr(grads[0]), ptr(grads[1]),
                                            ptr(sc), sc.numel(), ptr(_xq_ticket(Y.device)), flag, stream_ptr()), "mmf_xrank_q_train")
@@ -1032,10 +991,8 @@ class MMFGRQLossFn(torch.autograd.Function):
         dY, dP = torch.empty_like(Y), torch.empty_like(P)
         loss = torch.empty((), dtype=torch.float32, device=Y.device)
         scratch = torch.empty(B, dtype=torch.float32, device=Y.device)
-        flag = None
-        if y_dense and config.head_done_flag is not None:      # immtsf.train.FlagStep: dY_ts is published by the kernel itself
-            flag, config.head_done_flag = config.head_done_flag, None
-            config.head_dy_ptr = dY.data_ptr()
+        # immtsf.train.FlagStep: dY_ts is published by the kernel itself
+        flag = step_plan.current().take_head_flag(dY) if y_dense else None
         ps, gs = _struct(GRParams, params), _struct(GRParams, bufs)
         check(lib.immtsf_mmf_gr_q_train(C.byref(cfg), hidden, C.byref(ps), ptr(Y), ptr(P), ptr(M_u8), ptr(truth), ptr(mask), ptr(cnt), 1.0, None,
                                         ptr(loss), ptr(dY), ptr(dP), C.byref(gs), ptr(scratch), ptr(_xq_ticket(Y.device)[8:]), flag, stream_ptr()),
@@ -1115,11 +1072,9 @@ class TTCNPatchEncodeFn(torch.autograd.Function):
         grads, rets = _grad_buffers(params, ctx.sinks)
         sc = _bytes(lib.immtsf_ttcn_scratch_bytes(P, L, te_dim, K), x.device)
         ps, gs = _struct(TTCNParams, params), _struct(TTCNParams, grads)
-        g = config.sched_gate
-        if g is not None and config.sched_armed is not None and config.sched_armed != torch.cuda.current_stream().cuda_stream:
-            # parameter gradients only, chip-filling, nothing but the optimizer waits for them: go behind the text side's row-bound
-            # backward kernels (a hint: the spin gives up after 50 ms and the call proceeds)
-            check(lib.immtsf_flag_wait(g[0], g[1], 50, stream_ptr()), "flag_wait")
+        # parameter gradients only, chip-filling, nothing but the optimizer waits for them: go behind the text side's row-bound
+        # backward kernels (a hint: the spin gives up after 50 ms and the call proceeds)
+        step_plan.current().wait_gate()
         check(lib.immtsf_ttcn_backward(P, L, te_dim, K, precision, ptr(x), ptr(tt), ptr(mask), C.byref(ps), ptr(out), ptr(dout), ld,
                                        ptr(ctx.ws), ctx.ws.numel(), ptr(sc), sc.numel(), C.byref(gs), 1 if te_acc else 0, stream_ptr()),
               "ttcn_backward")
@@ -1350,18 +1305,12 @@ class FFNBlockFn(torch.autograd.Function):
             return rc
         # a step with a parameter-only branch (immtsf.train.FlagStep): the two weight-gradient products leave this stream's dependent chain
         # (LinearBf16Fn.backward has the why); only when every gradient goes straight to a pre-zeroed sink and the library takes the phases
-        tail = config.param_tail
-        flags = tail.get("wgrad_flags") if tail is not None else None
-        if pz and flags and all(r is None for r in rets):
+        plan = step_plan.current()
+        if pz and plan.wgrad_open and all(r is None for r in rets):
             rc = call(2, stream_ptr())
             if rc == 0:
-                flag, err = flags.pop()
-                check(lib.immtsf_flag_set(flag, stream_ptr()), "flag_set")
-
-                def job(stream, keep=(x2, dout, dx, ws, sc, params, grads, ps, gs)):
-                    check(lib.immtsf_flag_wait(flag, err, 50, stream), "flag_wait")
-                    check(call(4, stream), "ffn_block_backward")
-                tail["jobs_b"].append(job)
+                plan.defer_wgrad(lambda stream: check(call(4, stream), "ffn_block_backward"),
+                                 keep=(x2, dout, dx, ws, sc, params, grads, ps, gs))
                 return (dx.view(ctx.shape),) + (None,) * 7 + tuple(rets)
             if rc != -3:          # (IMMTSF_EUNSUPPORTED: nothing was launched -- the one-call form below)
                 check(rc, "ffn_block_backward")
@@ -1608,16 +1557,9 @@ class InceptionPeriodsFn(torch.autograd.Function):
         call(1, stream_ptr())
         # a step with a parameter-only branch: the kernels' gradients -- an im2col image, the summed product, the un-merge; nothing in the
         # backward waits for them -- leave this stream's dependent chain (needs every kernel on a gradient sink: nothing is returned)
-        tail = config.param_tail
-        flags = tail.get("wgrad_flags") if tail is not None else None
-        if flags and all(r is None for r in rets):
-            flag, err = flags.pop()
-            check(lib.immtsf_flag_set(flag, stream_ptr()), "flag_set")
-
-            def job(stream):
-                check(lib.immtsf_flag_wait(flag, err, 50, stream), "flag_wait")
-                wgrad(stream)
-            tail["jobs_b"].append(job)
+        plan = step_plan.current()
+        if plan.wgrad_open and all(r is None for r in rets):
+            plan.defer_wgrad(wgrad)
         else:
             wgrad(stream_ptr())
         return (dx,) + (None,) * 7 + tuple(rets)
@@ -1925,28 +1867,21 @@ class LinearBf16Fn(torch.autograd.Function):
                     db[i] = rb[i] = flat[i * per + N * K:(i + 1) * per]
         dy16 = torch.empty(nl * M * N, dtype=torch.bfloat16, device=dev)
         arr = lambda ts: (C.c_void_p * nl)(*[None if t is None else t.data_ptr() for t in ts])      # noqa: E731
-        # a step with a parameter-only branch (immtsf.train.FlagStep): the weight gradients -- nothing in the backward waits for them --
-        # leave this stream's dependent chain: the data gradient (and the casts) here, then a flag; the grouped weight-gradient launch
-        # runs on that branch behind the flag.  Only when every gradient goes straight to a pre-zeroed sink (nothing is returned).
-        tail = config.param_tail
-        flags = tail.get("wgrad_flags") if tail is not None else None
-        if need_w and ctx.pre and flags and dx is not None:
-            check(lib.immtsf_linear_bf16_backward(nl, ptr(x16), arr(Ws), arr(ctx.w16), arr(dys), ptr(dy16), ptr(dx), None, None, M, N, K, 1,
-                                                  stream_ptr()), "linear_bf16_backward")
-            flag, err = flags.pop()
-            check(lib.immtsf_flag_set(flag, stream_ptr()), "flag_set")
-            keep = (x16, Ws, ctx.w16, dys, dy16, dW, db)          # the job runs later, on another stream: everything it touches stays alive
+        w16 = ctx.w16
 
-            def job(stream, keep=keep, flag=flag, err=err, nl=nl, M=M, N=N, K=K):
-                x16_, Ws_, w16_, dys_, dy16_, dW_, db_ = keep
-                arr_ = lambda ts: (C.c_void_p * nl)(*[None if t is None else t.data_ptr() for t in ts])      # noqa: E731
-                check(lib.immtsf_flag_wait(flag, err, 50, stream), "flag_wait")
-                check(lib.immtsf_linear_bf16_backward(nl, ptr(x16_), arr_(Ws_), arr_(w16_), arr_(dys_), ptr(dy16_), None, arr_(dW_), arr_(db_), M, N, K,
-                                                      3, stream), "linear_bf16_backward")
-            tail["jobs_b"].append(job)
+        def launch(stream, dx_, wgrads, mode):          # wgrads: (dW, db) or None  (the closure keeps every buffer it reads alive)
+            dW_, db_ = (arr(wgrads[0]), arr(wgrads[1])) if wgrads else (None, None)
+            check(lib.immtsf_linear_bf16_backward(nl, ptr(x16), arr(Ws), arr(w16), arr(dys), ptr(dy16), ptr(dx_), dW_, db_, M, N, K, mode, stream),
+                  "linear_bf16_backward")
+        # a step with a parameter-only branch (immtsf.train.FlagStep): the weight gradients -- nothing in the backward waits for them --
+        # leave this stream's dependent chain (the data gradient and the casts stay).  Only when every gradient goes straight to a
+        # pre-zeroed sink (nothing is returned).
+        plan = step_plan.current()
+        if need_w and ctx.pre and plan.wgrad_open and dx is not None:
+            launch(stream_ptr(), dx, None, 1)
+            plan.defer_wgrad(lambda stream: launch(stream, None, (dW, db), 3))
             return (dx.view(ctx.shape), None, None) + tuple(rW) + tuple(rb)
-        check(lib.immtsf_linear_bf16_backward(nl, ptr(x16), arr(Ws), arr(ctx.w16), arr(dys), ptr(dy16), ptr(dx), arr(dW) if need_w else None,
-                                              arr(db) if need_w else None, M, N, K, 1, stream_ptr()), "linear_bf16_backward")
+        launch(stream_ptr(), dx, (dW, db) if need_w else None, 1)
         return ((dx.view(ctx.shape) if dx is not None else None), None, None) + tuple(rW) + tuple(rb)
 
 

@@ -19,7 +19,8 @@ import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, step_plan
+from .step_plan import StepPlan
 
 
 def shard_range(n_items: int, rank: int, world: int):
@@ -252,9 +253,9 @@ class FlatTrainer:
         """backward hook of a sink bucket: start its all-reduce now -- only while overlapping is on.  (A caller that turns
         `overlap` off after construction, e.g. GraphedStep without captured collectives, must not get collectives issued
         from inside the backward: under graph capture they would be captured AND repeated eagerly afterwards.)"""
-        cap = getattr(self, "_capture_hook", None)
-        if cap is not None:          # FlagStep's capture of the data-parallel step: announce the bucket by a device flag instead
-            cap(bi, burst)
+        announce = step_plan.current().announce
+        if announce is not None:          # FlagStep's capture of the data-parallel step: announce the bucket by a device flag instead
+            announce(bi, burst)
             return
         if self.overlap:
             self._bucket_ready(bi)
@@ -619,20 +620,18 @@ class GraphedStep:
     def _fwd_bwd(self):
         # (the 32 MB gradient memset as a third parallel branch of graph A, beside the forward, was measured: the step
         # got 5 % SLOWER -- 1.18 vs 1.12 ms -- so it stays in front of the forward)
-        from . import config
         self.trainer.zero_grad()
+        plan = StepPlan()
         if self.sched is not None:
-            # scheduling gate (config.sched_gate): the patch encoder's backward -- parameter gradients only, but a kernel that fills
+            # scheduling gate (StepPlan.gate): the patch encoder's backward -- parameter gradients only, but a kernel that fills
             # every CU's LDS for a millisecond at thousands of windows -- starts when the text side's row-bound backward kernels are
             # through, beside its small-launch tail, instead of beside them (4096 windows: a 19 us reduction took 0.7 ms in its shade)
             fp = self.sched.data_ptr()
             _lib.check(_lib.load().immtsf_flags_clear(fp, 2, torch.cuda.current_stream().cuda_stream), "flags_clear")
-            config.sched_gate, config.sched_armed = (fp, fp + 4), None
-        try:
+            plan.gate = (fp, fp + 4)
+        with step_plan.install(plan):
             loss = self.loss_fn()
             ops.backward_unit(loss)
-        finally:
-            config.sched_gate = config.sched_armed = None
         self.trainer.collect_grads()
         return loss
 
@@ -670,6 +669,8 @@ class PhasedStep:
     FlatTrainer(device_step=True).  world > 1: one eager all-reduce of the flat gradient in front of O (like
     GraphedStep without captured collectives)."""
 
+    head_published = False      # FlagStep: the head's kernel publishes "dY_ts is ready" itself (StepPlan.take_head_flag)
+
     def __init__(self, trainer: FlatTrainer, text_fn, backbone_fn, head_fn, warmup: int = 3):
         if not trainer.device_step:
             raise ValueError("PhasedStep needs FlatTrainer(device_step=True): host-side step counters would freeze in the graphs")
@@ -697,15 +698,15 @@ class PhasedStep:
             outs = text_fn()
         with torch.cuda.graph(self.gB1, pool=poolB, stream=self.B):
             pred = backbone_fn()
-        with torch.cuda.graph(self.gT2, pool=poolT, stream=self.T):
-            py, cuts, loss = self._head(pred, outs)
-            dpy = py.grad
-            dcuts = [c.grad if (torch.is_tensor(c) and c.requires_grad) else None for c in cuts]
-        with torch.cuda.graph(self.gB2, pool=poolB, stream=self.B):
-            torch.autograd.backward([pred], [dpy])
-            trainer.collect_grads()
-        with torch.cuda.graph(self.gT3, pool=poolT, stream=self.T):
-            self._text_backward(outs, dcuts)
+        with step_plan.install(StepPlan()) as plan:       # (the head's parameter gradients wait for the text-side backward)
+            with torch.cuda.graph(self.gT2, pool=poolT, stream=self.T):
+                py, cuts, loss, dcuts = self._head(plan, pred, outs)
+                dpy = py.grad
+            with torch.cuda.graph(self.gB2, pool=poolB, stream=self.B):
+                torch.autograd.backward([pred], [dpy])
+                trainer.collect_grads()
+            with torch.cuda.graph(self.gT3, pool=poolT, stream=self.T):
+                self._text_backward(plan, outs, dcuts)
         # the optimizer as a graph -- unless it holds collectives (sharded: norm all-reduce + parameter all-gather), which stay eager
         # like GraphedStep's (capture_collectives is the only path that puts RCCL calls into a graph)
         self.opt_eager = bool(trainer.sharded and trainer.collective)
@@ -717,25 +718,22 @@ class PhasedStep:
         self.eB1, self.eT2, self.eB2, self.eO = (torch.cuda.Event() for _ in range(4))
         self.eO.record(self.T)
 
-    def _head(self, pred, outs):
-        from . import config
+    def _head(self, plan, pred, outs):
         py = pred.detach().requires_grad_(True)
         cuts = [o.detach().requires_grad_(True) if (torch.is_tensor(o) and o.requires_grad) else o for o in outs]
         loss = self.head_fn(py, *cuts)
-        config.defer_param_grads = True       # the head's parameter gradients are enqueued behind the text-side backward (T3)
-        try:
-            ops.backward_unit(loss)
-        finally:
-            config.defer_param_grads = False
-        return py, cuts, loss
+        plan.hold_params = True       # the head's parameter gradients are enqueued behind the text-side backward (T3)
+        ops.backward_unit(loss)
+        plan.hold_params = False
+        return py, cuts, loss, [c.grad if (torch.is_tensor(c) and c.requires_grad) else None for c in cuts]
 
     @staticmethod
-    def _text_backward(outs, dcuts):
+    def _text_backward(plan, outs, dcuts):
         ts = [o for o, g in zip(outs, dcuts) if g is not None]
         gs = [g for g in dcuts if g is not None]
         if ts:
             torch.autograd.backward(ts, gs)
-        ops.run_deferred()
+        plan.run_params()
 
     def _eager_step(self):
         t = self.trainer
@@ -746,15 +744,15 @@ class PhasedStep:
         with torch.cuda.stream(self.B):
             pred = self.backbone_fn()
         self.T.wait_stream(self.B)
-        with torch.cuda.stream(self.T):
-            py, cuts, loss = self._head(pred, outs)
-            dcuts = [c.grad if (torch.is_tensor(c) and c.requires_grad) else None for c in cuts]
-        self.B.wait_stream(self.T)
-        with torch.cuda.stream(self.B):
-            torch.autograd.backward([pred], [py.grad])
-            t.collect_grads()
-        with torch.cuda.stream(self.T):
-            self._text_backward(outs, dcuts)
+        with step_plan.install(StepPlan()) as plan:
+            with torch.cuda.stream(self.T):
+                py, cuts, loss, dcuts = self._head(plan, pred, outs)
+            self.B.wait_stream(self.T)
+            with torch.cuda.stream(self.B):
+                torch.autograd.backward([pred], [py.grad])
+                t.collect_grads()
+            with torch.cuda.stream(self.T):
+                self._text_backward(plan, outs, dcuts)
         self.T.wait_stream(self.B)
         with torch.cuda.stream(self.T):
             t._reduced = [False] * len(t.buckets)
@@ -960,8 +958,7 @@ class FlagStep(PhasedStep):
 
         self.graph = torch.cuda.CUDAGraph()
         B, P = self.B, self.P
-        from . import config
-        try:
+        with step_plan.install(StepPlan(err=F_ERR)) as plan:
             with torch.cuda.graph(self.graph):
                 T = torch.cuda.current_stream()
                 trainer._grad_zeroed_by_step = True       # (the Adam passes below leave every range zero)
@@ -982,76 +979,57 @@ class FlagStep(PhasedStep):
                         P.wait_stream(T)              # (behind T's own update: the two large updates do not share the HBM)
                         with torch.cuda.stream(P):
                             adam(adam_split[2])
-                config.fold_stream = P                # parameter-only work of the text side: on its own branch (or at the head of the backbone's)
-                config.fold_flag = (W(self._FOLD), F_ERR) if fold_by_flag else None
+                plan.fold_stream = P                  # parameter-only work of the text side: on its own branch (or at the head of the backbone's)
+                plan.fold_flag = W(self._FOLD) if fold_by_flag else None
                 # scheduling hint (GraphedStep._fwd_bwd has the why): its time-out goes to its own word -- NOT the guard word, a hint
                 # that expires costs nothing but the overlap it was after
-                config.sched_gate, config.sched_armed = ((W(self._SCHED), W(self._SCHED_TO)) if sched_gate else None), None
-                try:
-                    outs = text_fn()
-                finally:
-                    config.fold_stream = None
-                    config.fold_flag = None
+                plan.gate = (W(self._SCHED), W(self._SCHED_TO)) if sched_gate else None
+                outs = text_fn()
+                plan.fold_stream = plan.fold_flag = None
                 with torch.cuda.stream(B):
                     pred = backbone_fn()
                     fset(F_B1, B)
                 fwait(F_B1, T)
-                config.head_done_flag = F_T2 if head_flag else None
-                try:
-                    py, cuts, loss = self._head(pred, outs)
-                    taken = config.head_done_flag is None and head_flag
-                finally:
-                    config.head_done_flag = None      # (never leave the address of this step's flag behind for an unrelated call)
+                plan.head_flag = F_T2 if head_flag else None
+                py, cuts, loss, dcuts = self._head(plan, pred, outs)
+                self.head_published = plan.head_dy_ptr is not None
                 dpy = py.grad
-                dcuts = [c.grad if (torch.is_tensor(c) and c.requires_grad) else None for c in cuts]
-                if not taken:
-                    fset(F_T2, T)                     # (a head that publishes the flag itself -- MMFXRankQLossFn -- has consumed it)
-                elif dpy is None or dpy.data_ptr() != config.head_dy_ptr:
+                if not self.head_published:
+                    fset(F_T2, T)                     # (a head that publishes the flag itself -- MMFXRankQLossFn -- has taken it)
+                elif dpy is None or dpy.data_ptr() != plan.head_dy_ptr:
                     raise RuntimeError("FlagStep: the head published its dY flag early, but autograd did not hand that buffer on as the "
                                        "backbone's output gradient (head_flag=False disables the early flag)")
-                # parameter-gradient tails (work only the optimizer waits for) go to the parameter branch: the text side's behind the TAIL
-                # flag (their inputs exist), a backbone's large linear layers' weight gradients (immtsf.ops.LinearBf16Fn: PatchTST's
-                # projections and feed-forward products) each behind a flag of its own from the spare words 9..15
-                tail = {"flag": (W(self._TAIL), F_ERR), "jobs": [], "jobs_b": [], "defer": self._defer,
-                        "ttf_flag": (W(self._TTF), F_ERR) if (ttf_wgrad_tail and P is not B) else None,
-                        "wgrad_flags": [(W(i), F_ERR) for i in range(15, 8, -1)] if (backbone_wgrad_tail and P is not B) else []}
+                # parameter-gradient tails (work only the optimizer waits for) go to the parameter branch: a backbone's large linear layers'
+                # weight gradients (immtsf.ops.LinearBf16Fn: PatchTST's projections and feed-forward products) each behind a flag of its
+                # own from the spare words 9..15, the text side's behind the TAIL flag (their inputs exist)
+                if backbone_wgrad_tail and P is not B:
+                    plan.wgrad_flags = [W(i) for i in range(15, 8, -1)]
                 with torch.cuda.stream(B):
                     fwait(F_T2, B)
-                    config.param_tail = {"jobs_b": tail["jobs_b"], "wgrad_flags": tail["wgrad_flags"]} if tail["wgrad_flags"] else None
-                    try:
-                        torch.autograd.backward([pred], [dpy])
-                    finally:
-                        config.param_tail = None
+                    torch.autograd.backward([pred], [dpy])
                     trainer.collect_grads()
-                    if self.dist and not tail["jobs_b"]:
+                    if self.dist and not plan.jobs_b:
                         branch_now[0] = "B"
                         for bi in backbone_buckets:
                             announce(bi)
-                tail["wgrad_flags"] = []              # (the text side's own products stay where they are)
-                config.param_tail = tail if self._defer > 0 else None
-                trainer._capture_hook = announce if self.dist else None
+                plan.wgrad_flags = []                 # (the text side's own products stay where they are)
+                plan.defer, plan.tail_flag = self._defer, W(self._TAIL)
+                plan.ttf_flag = W(self._TTF) if (ttf_wgrad_tail and P is not B and self._defer > 0) else None
+                plan.announce = announce if self.dist else None
                 branch_now[0] = "T"
-                try:
-                    self._text_backward(outs, dcuts)
-                finally:
-                    config.param_tail = None
-                    trainer._capture_hook = None
-                trainer._capture_hook = announce if self.dist else None
+                self._text_backward(plan, outs, dcuts)
                 branch_now[0] = "P"
-                try:
-                    with torch.cuda.stream(P):
-                        for job in tail["jobs_b"]:            # the backbone's deferred weight gradients, each behind its own flag
+                with torch.cuda.stream(P):
+                    for job in plan.jobs_b:               # the backbone's deferred weight gradients, each behind its own flag
+                        job(sp(P))
+                    if self.dist and plan.jobs_b:         # (the backbone's buckets are complete here, not at the end of its branch)
+                        for bi in backbone_buckets:
+                            announce(bi)
+                    if plan.jobs:
+                        if plan.tail_set:
+                            fwait(W(self._TAIL), P)
+                        for job in plan.jobs:
                             job(sp(P))
-                        if self.dist and tail["jobs_b"]:      # (the backbone's buckets are complete here, not at the end of its branch)
-                            for bi in backbone_buckets:
-                                announce(bi)
-                        if tail["jobs"]:
-                            if tail.get("flag_set"):
-                                fwait(W(self._TAIL), P)
-                            for job in tail["jobs"]:
-                                job(sp(P))
-                finally:
-                    trainer._capture_hook = None
                 with torch.cuda.stream(P):
                     if P is not B:
                         fset(F_P2, P)
@@ -1073,8 +1051,6 @@ class FlagStep(PhasedStep):
                         announce_range(lo, hi, [b for b in rest if lo <= trainer.ranges[b][0] and trainer.ranges[b][1] <= hi])
                     announced.update(rest)
                 _lib.check(lib.immtsf_flags_clear_set(fp, 16, self._f_pending, sp(T)), "flags_clear_set")
-        finally:
-            config.sched_gate = config.sched_armed = None
         self._order_segments()
         self.comm = None
         if self.dist:

@@ -111,3 +111,40 @@ def test_t2v_form_selection_is_a_host_decision():
     assert folded(64, 4096, 33, 4096, 768, 1, True, 3) == 0         # T > 32: outside both folded forms
     assert folded(4, 16, 8, 64, 32, 1, True, 3) == 1                # form 3 at any N inside its limits
     assert folded(4, 16, 8, 64, 32, 1, True, 1) == 0
+
+
+def test_step_plan_lives_for_one_step_only():
+    """immtsf.step_plan: the hand-overs between a step engine and the ops.  A plan is uninstalled when the step raises, and the
+    parameter-gradient work it holds goes with it (a later step never launches a closure over a failed step's buffers); a second plan
+    cannot be installed over the first; the head's "dY is ready" flag is handed out once.  No kernel is called."""
+    from immtsf import step_plan
+    from immtsf.step_plan import StepPlan
+    ran = []
+    plan = StepPlan()
+    with pytest.raises(ValueError):
+        with step_plan.install(plan):
+            assert step_plan.current() is plan
+            with pytest.raises(RuntimeError):
+                with step_plan.install(StepPlan()):
+                    pass
+            assert step_plan.current() is plan                   # (the refused install left the first one in place)
+            plan.hold_params = True
+            plan.defer_params(lambda: ran.append("stale"))
+            raise ValueError("a backward raised")
+    assert step_plan.current() is not plan
+    plan.run_params()
+    with step_plan.install(StepPlan()) as fresh:
+        fresh.run_params()
+    assert ran == []
+
+    plan = StepPlan()
+    plan.head_flag = 0x1000
+    dY = torch.zeros(3)
+    assert plan.take_head_flag(dY) == 0x1000
+    assert plan.take_head_flag(torch.zeros(3)) is None
+    assert plan.head_dy_ptr == dY.data_ptr()
+
+    idle = step_plan.current()                                   # outside an engine: nothing is offered
+    assert idle.take_head_flag(dY) is None and idle.arm_gate() is None and not idle.hold_params
+    assert not idle.wgrad_open and idle.ttf_flag is None and idle.defer == 0 and idle.announce is None
+    assert idle.fold(lambda stream: ran.append("fold")) is False and ran == []
