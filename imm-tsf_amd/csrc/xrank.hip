@@ -27,9 +27,11 @@
 #include "tail.hpp"
 #include "block_util.hpp"
 #include "t2v_fold.hpp"
+#include "eval.hpp"
 #include <math.h>
 #include <algorithm>
 #include <vector>
+#include <type_traits>
 
 namespace {
 
@@ -613,19 +615,40 @@ __device__ __forceinline__ void drop_row(const DropL& d, uint64_t o0, int C, flo
         }
 }
 
+// What the evaluation form of the forward adds to it: the truth / mask rows it scores the fused forecast against and the thread's
+// partial sums es[statistic][c] of the five evaluation terms (eval.hpp), which the caller reduces.  XQNoEval: the plain forward.
+struct XQNoEval {};
 template <int CM>
-__global__ __launch_bounds__(256) void xrank_q_fwd_kernel(XQDims q, const float* __restrict__ Y, const float* __restrict__ P,
-                                                           const float* __restrict__ bHO, const unsigned char* __restrict__ mtxt,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float* __restrict__ Yout, float* __restrict__ lse,
-                                                           float* __restrict__ xhat, float* __restrict__ rstd, unsigned int* ticket, DropCfg drop) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
+struct XQEvalRows {
+    const float* __restrict__ truth;
+    const float* __restrict__ tmask;
+    float es[EVAL_STATS][CM];
+};
+
+// The forward of a workgroup's windows.  With XQEvalRows (immtsf_mmf_xrank_q_eval) nothing is kept for a backward (lse / xhat / rstd /
+// ticket are not touched) and Yout is optional.
+template <int CM, class EV>
+__device__ __forceinline__ void xrank_q_fwd_rows(float* lds, XQDims q, const float* __restrict__ Y, const float* __restrict__ P,
+                                                 const float* __restrict__ bHO, const unsigned char* __restrict__ mtxt,
+                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                 float* __restrict__ Yout, float* __restrict__ lse,
+                                                 float* __restrict__ xhat, float* __restrict__ rstd, unsigned int* ticket, DropCfg drop,
+                                                 EV& ev) {
+    constexpr bool EVAL = !std::is_same<EV, XQNoEval>::value;
     const int T = q.T, C = q.C, H = q.H, PW = q.PW, parts = q.parts, psh = q.psh, nch = (T + 3) >> 2;
     const int b0 = blockIdx.x * q.wpb, nw = min(q.wpb, q.B - b0), rows = nw * T;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0u;       // the backward's last-workgroup ticket starts at zero
+    if constexpr (!EVAL)
+        if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0u;       // the backward's last-workgroup ticket starts at zero
     {   // the windows' P rows are contiguous
         const float4* src = reinterpret_cast<const float4*>(P + (size_t)b0 * T * PW);
         for (int i = threadIdx.x; i < rows * PW / 4; i += 256) reinterpret_cast<float4*>(lds)[i] = src[i];
+    }
+    // EVAL: the windows' truth / mask rows behind the P rows (2 C floats per row: within xq_lds_floats), read when the row's result exists
+    float* Ts = lds + (size_t)q.wpb * T * PW;
+    float* Ms = Ts + (size_t)q.wpb * T * C;
+    if constexpr (EVAL) {
+        const size_t e0 = (size_t)b0 * T * C;
+        for (int i = threadIdx.x; i < rows * C; i += 256) { Ts[i] = ev.truth[e0 + i]; Ms[i] = ev.tmask[e0 + i]; }
     }
     const DropL dl = drop_local(drop);
     float gm[CM], bt[CM], bh[CM];
@@ -688,7 +711,8 @@ __global__ __launch_bounds__(256) void xrank_q_fwd_kernel(XQDims q, const float*
                 }
                 sum = group_sum(sum, parts);
                 const float is = 1.f / sum;
-                if (part == 0) lse[grow * H + h] = mx + __logf(sum);
+                if constexpr (!EVAL)
+                    if (part == 0) lse[grow * H + h] = mx + __logf(sum);
 #pragma unroll
                 for (int c = 0; c < CM; ++c)
                     if (c < C) delta[c] = fmaf(group_sum(acc[c], parts), is, delta[c]);
@@ -705,7 +729,7 @@ __global__ __launch_bounds__(256) void xrank_q_fwd_kernel(XQDims q, const float*
         for (int c = 0; c < CM; ++c)
             if (c < C) { const float tt = delta[c] - mu; var = fmaf(tt, tt, var); }
         const float rs = 1.0f / sqrtf(var / (float)C + 1e-5f);
-        rstd[grow] = rs;
+        if constexpr (!EVAL) rstd[grow] = rs;
         float ds[CM];
         if (live) drop_row<CM>(dl, (uint64_t)grow * C, C, ds);
 #pragma unroll
@@ -713,11 +737,76 @@ __global__ __launch_bounds__(256) void xrank_q_fwd_kernel(XQDims q, const float*
             if (c < C) {
                 const float hh = (delta[c] - mu) * rs;
                 const size_t o = grow * C + c;
-                xhat[o] = hh;
+                if constexpr (!EVAL) xhat[o] = hh;
                 const float v = live ? fmaf(hh, gm[c], bt[c]) * ds[c] : 0.f;
-                Yout[o] = (y[c] + q.kappa * v) * inv;
+                const float yo = (y[c] + q.kappa * v) * inv;
+                if constexpr (EVAL) {
+                    if (Yout) Yout[o] = yo;
+                    float e[EVAL_STATS];
+                    eval_terms(Ts[row * C + c], yo, Ms[row * C + c], e);
+#pragma unroll
+                    for (int k = 0; k < EVAL_STATS; ++k) ev.es[k][c] += e[k];
+                } else {
+                    Yout[o] = yo;
+                }
             }
     }
+}
+
+template <int CM>
+__global__ __launch_bounds__(256) void xrank_q_fwd_kernel(XQDims q, const float* __restrict__ Y, const float* __restrict__ P,
+                                                           const float* __restrict__ bHO, const unsigned char* __restrict__ mtxt,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           float* __restrict__ Yout, float* __restrict__ lse,
+                                                           float* __restrict__ xhat, float* __restrict__ rstd, unsigned int* ticket, DropCfg drop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    XQNoEval none;
+    xrank_q_fwd_rows<CM>(lds, q, Y, P, bHO, mtxt, gamma, beta, Yout, lse, xhat, rstd, ticket, drop, none);
+}
+
+// Evaluation of the Q half in ONE launch: the forward above and the five per-variable metric sums of immtsf_eval_metrics_accum over
+// the fused forecast, which never has to be written.  Per-thread sums (a thread sees a row or two) -> wave (DPP) -> workgroup -> an
+// fp64 slab per workgroup; the last workgroup to finish (ticket) folds the slabs in index order into the fp64 accumulator.
+template <int CM>
+__global__ __launch_bounds__(256) void xrank_q_eval_kernel(XQDims q, const float* __restrict__ Y, const float* __restrict__ P,
+                                                            const float* __restrict__ bHO, const unsigned char* __restrict__ mtxt,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const float* __restrict__ truth, const float* __restrict__ tmask,
+                                                            float* __restrict__ Yout, double* __restrict__ slabs, unsigned int* ticket,
+                                                            double* __restrict__ acc, DropCfg drop) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    __shared__ float red[4][EVAL_STATS * CM];
+    __shared__ int s_last;
+    XQEvalRows<CM> ev;
+    ev.truth = truth; ev.tmask = tmask;
+#pragma unroll
+    for (int k = 0; k < EVAL_STATS; ++k)
+#pragma unroll
+        for (int c = 0; c < CM; ++c) ev.es[k][c] = 0.f;
+    xrank_q_fwd_rows<CM>(lds, q, Y, P, bHO, mtxt, gamma, beta, Yout, nullptr, nullptr, nullptr, nullptr, drop, ev);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, C = q.C, NV = EVAL_STATS * C;
+#pragma unroll
+    for (int k = 0; k < EVAL_STATS; ++k)
+#pragma unroll
+        for (int c = 0; c < CM; ++c) {
+            const float v = wave_sum(ev.es[k][c]);
+            if (lane == 0 && c < C) red[wave][k * C + c] = v;
+        }
+    __syncthreads();
+    if ((int)threadIdx.x < NV)
+        slabs[(size_t)blockIdx.x * NV + threadIdx.x] = ((double)red[0][threadIdx.x] + (double)red[1][threadIdx.x]) +
+                                                       ((double)red[2][threadIdx.x] + (double)red[3][threadIdx.x]);
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        s_last = (atomicAdd(ticket, 1u) == gridDim.x - 1) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    eval_fold_slabs(slabs, (int)gridDim.x, NV, acc);
+    if (threadIdx.x == 0) *ticket = 0u;
 }
 
 template <int CM>
@@ -1764,6 +1853,39 @@ int immtsf_mmf_xrank_q_forward(const immtsf_fusion_cfg* cfg, const float* ln_w, 
     else
         hipLaunchKernelGGL(xrank_q_fwd_kernel<16>, dim3(grid), dim3(256), lds, s, q, Y_ts, P, bHO, M_txt, ln_w, ln_b, Y_out, w.lse, w.xhat, w.rstd,
                            w.ticket, drop);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
+size_t immtsf_mmf_xrank_q_eval_scratch_bytes(const immtsf_fusion_cfg* cfg) {
+    if (!xr_supported(cfg)) return 0;
+    const XRDims x = xr_dims(cfg);
+    return (size_t)cdiv(x.B, xq_wpb(x)) * EVAL_STATS * x.C * sizeof(double) + 256;
+}
+
+/* q_forward + the metric sums of immtsf_eval_metrics_accum over its result in one launch (evaluation: no dropout).  Y_out may be NULL.
+ * acc: fp64 [5][C], ADDED to; ticket: one zero-initialised device word that the call leaves zero. */
+int immtsf_mmf_xrank_q_eval(const immtsf_fusion_cfg* cfg, const float* ln_w, const float* ln_b, const float* Y_ts, const float* P,
+                            const float* bHO, const uint8_t* M_txt, float* Y_out, void* workspace, size_t workspace_bytes,
+                            const float* truth, const float* mask, double* acc, void* scratch, size_t scratch_bytes, uint32_t* ticket,
+                            immtsf_stream_t stream) {
+    (void)workspace; (void)workspace_bytes;      // nothing is kept for a backward
+    if (bad_cfg(cfg) || !ln_w || !ln_b || !Y_ts || !P || !bHO || !M_txt || !truth || !mask || !acc || !scratch || !ticket) return IMMTSF_EINVAL;
+    if (cfg->training != 0) return IMMTSF_EINVAL;
+    if (!xr_supported(cfg)) return IMMTSF_EUNSUPPORTED;
+    if (scratch_bytes < immtsf_mmf_xrank_q_eval_scratch_bytes(cfg)) return IMMTSF_EWORKSPACE;
+    const XQDims q = xq_dims(cfg);
+    const DropCfg drop = drop_of(cfg);
+    const size_t lds = (size_t)q.wpb * q.T * (q.PW + 2 * q.C) * sizeof(float);      // P rows | truth rows | mask rows
+    const int grid = cdiv(q.B, q.wpb);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* slabs = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(scratch) + 255) & ~uintptr_t(255));
+    if (q.C <= 8)
+        hipLaunchKernelGGL(xrank_q_eval_kernel<8>, dim3(grid), dim3(256), lds, s, q, Y_ts, P, bHO, M_txt, ln_w, ln_b, truth, mask, Y_out, slabs, ticket,
+                           acc, drop);
+    else
+        hipLaunchKernelGGL(xrank_q_eval_kernel<16>, dim3(grid), dim3(256), lds, s, q, Y_ts, P, bHO, M_txt, ln_w, ln_b, truth, mask, Y_out, slabs, ticket,
+                           acc, drop);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
 }

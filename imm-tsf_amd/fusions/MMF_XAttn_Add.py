@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from fusions._common import f32, resolve_precision
 from immtsf import config
-from immtsf.ops import MMFXAttnKVFn, MMFXAttnQFn, MMFXRankPFn, MMFXRankQFn, MMFXRankQLossFn, masked_mse, mmf_xattn_q_fold, mmf_xrank_pw
+from immtsf.ops import MMFXAttnKVFn, MMFXAttnQFn, MMFXRankPFn, MMFXRankQFn, MMFXRankQLossFn, eval_metrics_accum, masked_mse, mmf_xattn_q_fold, mmf_xrank_pw, mmf_xrank_q_eval
 
 
 class MMF_XAttn_Add(nn.Module):
@@ -106,6 +106,24 @@ class MMF_XAttn_Add(nn.Module):
         p = self._params()
         return MMFXRankQLossFn.apply(f32(Y_ts), P, bHO, M_u8, f32(truth), f32(mask), global_cnt, self.d_attn, self.n_heads, float(self.kappa),
                                      self.p_drop, training, resolve_precision(self), self.last_seed, p[9], p[10])
+
+    def forward_metrics(self, Y_ts, E_txt, M_txt, truth, mask, acc, kv=None, scratch=None):
+        """evaluation: immtsf.ops.eval_metrics_accum(forward(Y_ts, E_txt, M_txt, kv), truth, mask, acc) -- the five per-variable metric
+        sums of lib.evaluation.evaluation() added to acc (float64 (5, C)).  In the low-rank form the head and the sums are one launch
+        (immtsf.ops.mmf_xrank_q_eval) and the fused forecast is never written; otherwise the two calls.  Evaluation mode only.  scratch: the
+        caller's immtsf.ops.EvalScratch (None: the device's shared default)."""
+        if self.training:
+            raise RuntimeError("MMF_XAttn_Add.forward_metrics: evaluation mode only (call .eval() first)")
+        with torch.no_grad():
+            if not self._rank(Y_ts.shape[1]):
+                return eval_metrics_accum(self.forward(Y_ts, E_txt, M_txt, kv=kv), truth, mask, acc, scratch)
+            B = Y_ts.shape[0]
+            M_u8 = M_txt.reshape(B).to(torch.bool).view(torch.uint8)
+            P, bHO = self.project_kv(E_txt) if (kv is None or kv[1] is None) else kv
+            p = self._params()
+            mmf_xrank_q_eval(f32(Y_ts), P, bHO, M_u8, truth, mask, acc, self.d_attn, self.n_heads, float(self.kappa), resolve_precision(self),
+                             p[9], p[10], scratch=scratch)
+            return acc
 
 
 from immtsf.dropin import reexport_missing as _reexport_missing  # noqa: E402

@@ -5,3 +5,10 @@ in torch.autograd.Functions; the drop-in modules live in the sibling packages `f
 (same import paths as the reference, so its main.py runs unchanged with this directory first on sys.path).
 """
 from . import config  # noqa: F401
+
+
+def __getattr__(name):      # immtsf.EvalStep without importing torch-side modules at package import
+    if name == "EvalStep":
+        from .evalstep import EvalStep
+        return EvalStep
+    raise AttributeError(f"module 'immtsf' has no attribute {name!r}")

@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libimmtsf_hip.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 FORM_NO_PROJ = 16        # immtsf_fusion_cfg.form bit (IMMTSF_FORM_NO_PROJ)
 FORM_HALF_OUT = 32       # ... IMMTSF_FORM_HALF_OUT: the fp32 output is not written, its bf16 image is all the consumer reads
 FORM_LOWRANK_OUT = 64    # ... IMMTSF_FORM_LOWRANK_OUT: dZ = dP Wc is not written, the producer's backward takes (dP, Wc)
@@ -157,6 +157,12 @@ _PROTOS = {
                                            C.c_size_t, c_stream]),
     "immtsf_mmf_xrank_q_backward": (C.c_int, [_P(FusionCfg), c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                             c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_mmf_xrank_q_eval_scratch_bytes": (C.c_size_t, [_P(FusionCfg)]),
+    "immtsf_mmf_xrank_q_eval": (C.c_int, [_P(FusionCfg), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, C.c_void_p, C.c_size_t,
+                                          c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, c_stream]),
+    "immtsf_eval_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "immtsf_eval_metrics_accum": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            c_stream]),
     "immtsf_mmf_xrank_q_train_scratch_bytes": (C.c_size_t, [_P(FusionCfg)]),
     "immtsf_mmf_xrank_q_train": (C.c_int, [_P(FusionCfg), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, C.c_float,
                                          c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, C.c_void_p,

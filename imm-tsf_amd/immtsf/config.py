@@ -115,3 +115,6 @@ z_handover = os.environ.get("IMMTSF_Z_HANDOVER", "1") != "0"
 # FullAttention over <= 32 positions with heads up to 256 wide as one kernel per direction (csrc/attn_mid.hip); False: batched GEMMs +
 # row softmax
 attn_mid = True
+# lib.evaluation.evaluation() on immtsf.EvalStep (forward + fused metric kernel per batch shape as a replayed hipGraph, one device -> host
+# copy per loader); False (the default): the eager forward and the metrics as torch ops
+eval_engine = os.environ.get("IMMTSF_EVAL_ENGINE", "0") == "1"

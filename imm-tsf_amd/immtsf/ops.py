@@ -2454,3 +2454,79 @@ def dropout_keep_mask(seed: int, site: int, n: int, p: float, device) -> torch.T
     out = torch.empty(n, dtype=torch.uint8, device=device)
     check(lib.immtsf_dropout_mask(int(seed) & 0xFFFFFFFFFFFFFFFF, site, n, float(p), ptr(out), stream_ptr()), "dropout_mask")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ evaluation metrics
+class EvalScratch:
+    """slab scratch (one buffer per size, kept: a captured graph keeps pointing at it) and the ticket word of the evaluation-metric
+    kernels.  The calls that share one must be ordered on their streams (the ticket is zero between calls): an immtsf.EvalStep owns
+    its own; callers that pass none share the device's default and are on their own stream at their own risk."""
+
+    def __init__(self, device):
+        self.device = device
+        self.ticket = torch.zeros(16, dtype=torch.int32, device=device)
+        self._bufs = {}
+
+    def take(self, nbytes):
+        b = self._bufs.get(int(nbytes))
+        if b is None:
+            b = self._bufs[int(nbytes)] = _bytes(nbytes, self.device)
+        return b, self.ticket
+
+
+_eval_default = {}
+
+
+def _eval_scratch(device, nbytes, scratch=None):
+    if scratch is None:
+        key = (device.type, device.index)
+        scratch = _eval_default.get(key)
+        if scratch is None:
+            scratch = _eval_default[key] = EvalScratch(device)
+    elif scratch.device != device:
+        raise _lib.ImmtsfError(f"EvalScratch of {scratch.device} used on {device}")
+    return scratch.take(nbytes)
+
+
+def _eval_acc_ok(acc, Cc):
+    if acc.dtype != torch.float64 or tuple(acc.shape) != (5, Cc) or not acc.is_contiguous() or not acc.is_cuda:
+        raise _lib.ImmtsfError(f"evaluation accumulator must be a contiguous float64 (5, {Cc}) tensor on the GPU")
+
+
+def eval_metrics_accum(pred, truth, mask, acc, scratch=None):
+    """acc (5, C) float64 += per-variable sums of [(t-p)^2 m, |t-p| m, |t-p| / t (t != 0) m, m, (t != 0) m] over (..., C) tensors: ONE
+    launch (immtsf_eval_metrics_accum), each tensor read once, deterministic.  Enqueues only.  scratch: an EvalScratch (None: the
+    device's shared default)."""
+    lib = _lib.load()
+    Cc = pred.shape[-1]
+    if tuple(truth.shape) != tuple(pred.shape) or tuple(mask.shape) != tuple(pred.shape):
+        raise _lib.ImmtsfError("eval_metrics_accum: pred, truth and mask must have one shape")
+    pred, truth, mask = (_c(t.detach().to(torch.float32)) for t in (pred, truth, mask))
+    _need_gpu(pred, truth, mask)
+    _eval_acc_ok(acc, Cc)
+    rows = pred.numel() // Cc
+    sc, tk = _eval_scratch(pred.device, lib.immtsf_eval_metrics_scratch_bytes(rows, Cc), scratch)
+    check(lib.immtsf_eval_metrics_accum(ptr(truth), ptr(pred), ptr(mask), rows, Cc, ptr(acc), ptr(sc), sc.numel(), ptr(tk), stream_ptr()),
+          "eval_metrics_accum")
+    return acc
+
+
+def mmf_xrank_q_eval(Y, P, bHO, M_u8, truth, mask, acc, d, H, kappa, precision, ln_w, ln_b, want_out=False, scratch=None):
+    """Q half of MMF_XAttn_Add's low-rank form in evaluation mode + eval_metrics_accum over its result: ONE launch
+    (immtsf_mmf_xrank_q_eval).  Returns the fused forecast when want_out, else None (it is then never written)."""
+    lib = _lib.load()
+    Y, P, bHO, M_u8, ln_w, ln_b = (_c(t.detach()) for t in (Y, P, bHO, M_u8, ln_w, ln_b))
+    truth, mask = _c(truth.detach().to(torch.float32)), _c(mask.detach().to(torch.float32))
+    _need_gpu(Y, P, bHO, M_u8, truth, mask, ln_w, ln_b)
+    B, T, Cc = Y.shape
+    if tuple(truth.shape) != (B, T, Cc) or tuple(mask.shape) != (B, T, Cc):
+        raise _lib.ImmtsfError("mmf_xrank_q_eval: truth and mask must have the forecast's shape")
+    _eval_acc_ok(acc, Cc)
+    cfg = make_cfg(B, 0, T, Cc, 0, d, H, precision, False, 0.0, kappa, 0, Y.device)
+    if int(lib.immtsf_mmf_xrank_pw(C.byref(cfg))) != P.shape[2]:
+        raise _lib.ImmtsfError("MMF_XAttn_Add low-rank form: P does not have the row pitch of these dimensions")
+    sc, tk = _eval_scratch(Y.device, lib.immtsf_mmf_xrank_q_eval_scratch_bytes(C.byref(cfg)), scratch)
+    out = torch.empty_like(Y) if want_out else None
+    check(lib.immtsf_mmf_xrank_q_eval(C.byref(cfg), ptr(ln_w), ptr(ln_b), ptr(Y), ptr(P), ptr(bHO), ptr(M_u8), ptr(out), None, 0, ptr(truth),
+                                      ptr(mask), ptr(acc), ptr(sc), sc.numel(), ptr(tk), stream_ptr()), "mmf_xrank_q_eval")
+    return out

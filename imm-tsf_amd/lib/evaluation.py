@@ -110,6 +110,39 @@ def _pool_release(index):
         _pool_users.pop(index, None)
 
 
+def _pool_acquire(owner, dev):
+    """the memory pool every cached graph of a device captures into (seam graphs and immtsf.EvalStep's: they never replay concurrently);
+    `owner` counts as a user of it for as long as it lives"""
+    pool = _pool.get(dev.index)
+    if pool is None:
+        pool = _pool[dev.index] = torch.cuda.graph_pool_handle()
+    _pool_users[dev.index] = _pool_users.get(dev.index, 0) + 1
+    weakref.finalize(owner, _pool_release, dev.index)
+    return pool
+
+
+def _graph_cache_lookup(cache, seen, key, need, build):
+    """the caching policy of captured graphs (the seam's and immtsf.EvalStep's): a key is run eagerly at its first sighting (None) and
+    captured -- build() -- at the second; entries hold `.bytes` of static batch copies and are evicted least recently used first under
+    the count cap and the byte budget; `cache` keeps the most recently used entry last"""
+    g = cache.get(key)
+    if g is not None:
+        cache[key] = cache.pop(key)                              # most recently used last
+        return g
+    n = seen.get(key, 0)
+    if n < 1:
+        if len(seen) >= _SEEN_CAP:
+            seen.pop(next(iter(seen)))
+        seen[key] = n + 1
+        return None
+    if need > _GRAPH_BYTES:
+        return None
+    while cache and (len(cache) >= _GRAPH_CAP or sum(x.bytes for x in cache.values()) + need > _GRAPH_BYTES):
+        cache.pop(next(iter(cache)))                             # evict the least recently used shape
+    g = cache[key] = build()
+    return g
+
+
 class _SeamLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, g):
@@ -196,11 +229,7 @@ class _SeamGraph:
                 b_.copy_(s_)
             self.drop_dev.copy_(drop0)
         torch.cuda.synchronize()
-        pool = _pool.get(dev.index)
-        if pool is None:
-            pool = _pool[dev.index] = torch.cuda.graph_pool_handle()
-        _pool_users[dev.index] = _pool_users.get(dev.index, 0) + 1
-        weakref.finalize(self, _pool_release, dev.index)
+        pool = _pool_acquire(self, dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, pool=pool):
             self.loss, self.grads = run()
@@ -230,23 +259,8 @@ def _seam_lookup(model, fusion, batch_dict, names):
     if g is not None and g.fusion_ref() is not fusion:          # (the id was recycled by another fusion module)
         del cache[key]
         g = None
-    if g is not None:
-        cache[key] = cache.pop(key)                              # most recently used last
-        return g
-    seen = _seen.setdefault(model, {})
-    n = seen.get(key, 0)
-    if n < 1:
-        if len(seen) >= _SEEN_CAP:
-            seen.pop(next(iter(seen)))
-        seen[key] = n + 1
-        return None
     need = sum(batch_dict[k].numel() * batch_dict[k].element_size() for k in names)
-    if need > _GRAPH_BYTES:
-        return None
-    while cache and (len(cache) >= _GRAPH_CAP or sum(x.bytes for x in cache.values()) + need > _GRAPH_BYTES):
-        cache.pop(next(iter(cache)))                             # evict the least recently used shape
-    g = cache[key] = _SeamGraph(model, fusion, batch_dict, names)
-    return g
+    return _graph_cache_lookup(cache, _seen.setdefault(model, {}), key, need, lambda: _SeamGraph(model, fusion, batch_dict, names))
 
 
 # ---- deferred NaN guards ----------------------------------------------------------------------------------------------------------
@@ -337,12 +351,41 @@ def compute_all_losses(model, fusion, batch_dict, enable_text=True, use_text_emb
     return {"loss": mse, "mse": mse.item() if sync else mse.detach()}
 
 
+_eval_steps = weakref.WeakKeyDictionary()      # model -> {(id(fusion), enable_text): EvalStep} (an EvalStep holds its modules weakly)
+
+
+def _eval_step(model, fusion, enable_text):
+    """the immtsf.EvalStep of a (model, fusion): kept with the MODEL, like the seam's graphs; valid for the very fusion module"""
+    from immtsf.evalstep import EvalStep
+    steps = _eval_steps.setdefault(model, {})
+    key = (id(fusion), bool(enable_text))
+    ev = steps.get(key)
+    if ev is None or ev.fusion is not (fusion if enable_text else None):        # (the id was recycled by another fusion module)
+        ev = steps[key] = EvalStep(model, fusion, enable_text=enable_text)
+    return ev
+
+
 def evaluation(model, fusion, dataloader, enable_text=True, use_text_embeddings=True):
     """Test/validation metrics with the reference's definitions (lib/evaluation.py:192-283): per-variable sums of the
     squared / absolute / relative errors and of the observation counts over the whole loader, then mean over the
     variables that were observed.  Everything accumulates on the device; the only host syncs are the final `.item()`s
     (the reference syncs several times per batch).  Returns the same dict of python floats."""
     acc = None
+    if config.eval_engine and use_text_embeddings:
+        # opt-in: immtsf.EvalStep (replayed forward graph + fused metric kernel) for batches that live on the GPU
+        it = iter(dataloader)
+        first = next(it, None)
+        if first is None:
+            raise ValueError("evaluation(): empty dataloader")
+        if torch.is_tensor(first.get("tp_to_predict")) and first["tp_to_predict"].is_cuda:
+            ev = _eval_step(model, fusion, enable_text)
+            ev.reset()
+            ev(first)
+            for batch_dict in it:
+                ev(batch_dict)
+            return ev.result()
+        import itertools
+        dataloader = itertools.chain([first], it)
     if config.nan_check == "deferred":
         check_deferred_nan(fusion)
     with torch.no_grad():

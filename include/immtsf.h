@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define IMMTSF_ABI_VERSION 6
+#define IMMTSF_ABI_VERSION 7
 #define IMMTSF_T2V_FOLD_MIN_ROWS 8192 /* see immtsf_fusion_cfg.form */
 #define IMMTSF_FORM_NO_PROJ 16        /* immtsf_fusion_cfg.form bit, TTF_T2V_XAttn: leave proj_out to the consumer (E_txt := Z, dE_txt := dZ,
                                          which the backward overwrites in place; proj_out's gradients are not written) */
@@ -366,6 +366,19 @@ int immtsf_mmf_xrank_q_train(const immtsf_fusion_cfg* cfg, const float* ln_w, co
                              float* d_ln_b, void* scratch, size_t scratch_bytes, uint32_t* ticket, int32_t* done_flag,
                              immtsf_stream_t stream);
 
+/* Evaluation of the Q half in ONE launch (ABI 7): immtsf_mmf_xrank_q_forward and, over its result, the metric sums of
+ * immtsf_eval_metrics_accum against truth / mask (B*T, C), added to acc (fp64 [5][C]).  Y_out optional (NULL: the fused forecast is
+ * never written).  A workgroup's partial sums (the rows of its windows: a row or two per thread, then a wave and a 4-wave reduction) are
+ * fp32 sums of the fp32 terms; fp64 starts with the per-workgroup slab -- where immtsf_eval_metrics_accum is fp64 from the first add.
+ * workspace is not used (nothing is kept for a backward; may be NULL).  cfg->training != 0: IMMTSF_EINVAL (evaluation
+ * has no dropout); immtsf_mmf_xrank_pw(cfg) == 0: IMMTSF_EUNSUPPORTED.  scratch: ..._q_eval_scratch_bytes; ticket: one zero-initialised
+ * device word that the call leaves zero. */
+size_t immtsf_mmf_xrank_q_eval_scratch_bytes(const immtsf_fusion_cfg* cfg);
+int immtsf_mmf_xrank_q_eval(const immtsf_fusion_cfg* cfg, const float* ln_w, const float* ln_b, const float* Y_ts, const float* P,
+                            const float* bHO, const uint8_t* M_txt, float* Y_out, void* workspace, size_t workspace_bytes,
+                            const float* truth, const float* mask, double* acc, void* scratch, size_t scratch_bytes, uint32_t* ticket,
+                            immtsf_stream_t stream);
+
 /* ---- a9, short sequences with wide heads (round 3; csrc/attn_mid.hip): softmax(scale Q K^T) V per (batch, head) on (B, L, H, E) /
  * (B, S, H, E) / (B, S, H, D) tensors for L, S <= 32 and E, D <= 256 (multiples of 4) -- PatchTST's FullAttention over the patches
  * of a variable (layers/SelfAttention_Family.py:50-77).  One launch per direction instead of batched GEMMs + row softmax
@@ -560,6 +573,17 @@ int immtsf_masked_mse(const float* truth, const float* pred, const float* mask, 
 int immtsf_masked_mse_counted(const float* truth, const float* pred, const float* mask, int32_t rows, int32_t C,
                               const float* cnt_global, float* scratch, float* loss, float* dpred, float grad_scale,
                               immtsf_stream_t stream);
+
+/* ---- evaluation metrics (ABI 7; csrc/eval.hip): the five per-variable sums of lib/evaluation.py:192-283 over one batch in ONE launch,
+ * ADDED to acc, fp64 [5][C] = se, ae, ape, cnt, cnt_ape:  se += (t-p)^2 m, ae += |t-p| m, cnt += m;  m2 = (t != 0) m,
+ * ape += |t-p| / t * m2 (SIGNED divisor, as the reference has it), cnt_ape += m2.  truth / pred / mask: (rows, C) fp32, each read once;
+ * any C >= 1 (16-byte loads where the pointers allow); rows == 0: no launch.  Terms are formed in fp32 and summed in fp64 in an order
+ * fixed by the shape (no floating-point atomics): the same batches give the same bits.  acc lives across calls (a whole loader; a
+ * replayed graph keeps adding to it) and is zeroed by the caller.  scratch: ..._scratch_bytes; ticket: one zero-initialised device
+ * word that the call leaves zero (calls sharing scratch / ticket / acc must be ordered on their streams). */
+size_t immtsf_eval_metrics_scratch_bytes(int32_t rows, int32_t C);
+int immtsf_eval_metrics_accum(const float* truth, const float* pred, const float* mask, int32_t rows, int32_t C, double* acc,
+                              void* scratch, size_t scratch_bytes, uint32_t* ticket, immtsf_stream_t stream);
 
 /* ---- device-side batch builder: the reference's collate functions over a dataset that is
  * resident in HBM.  Replaces lib/parse_datasets.py:252-295 (variable_time_collate_fn), :298-366 +
