@@ -160,6 +160,10 @@ _PROTOS = {
     "immtsf_mmf_xrank_q_eval_scratch_bytes": (C.c_size_t, [_P(FusionCfg)]),
     "immtsf_mmf_xrank_q_eval": (C.c_int, [_P(FusionCfg), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_f32p, C.c_void_p, C.c_size_t,
                                           c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, c_stream]),
+    "immtsf_dlinear_supported": (C.c_int, [C.c_int32] * 5),
+    "immtsf_dlinear_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "immtsf_dlinear_forward": (C.c_int, [C.c_int32] * 8 + [c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "immtsf_dlinear_backward": (C.c_int, [C.c_int32] * 8 + [c_f32p] * 12 + [C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_eval_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "immtsf_eval_metrics_accum": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                             c_stream]),

@@ -118,3 +118,6 @@ attn_mid = True
 # lib.evaluation.evaluation() on immtsf.EvalStep (forward + fused metric kernel per batch shape as a replayed hipGraph, one device -> host
 # copy per loader); False (the default): the eager forward and the metrics as torch ops
 eval_engine = os.environ.get("IMMTSF_EVAL_ENGINE", "0") == "1"
+# DLinear.forecasting() as one HIP launch per direction (csrc/dlinear.hip) wherever immtsf_dlinear_supported allows; IMMTSF_DLINEAR_FUSED=0:
+# the composed path (torch element-wise ops around three immtsf.ops.linear calls) -- the cross-check.  fp32 in either precision mode
+dlinear_fused = os.environ.get("IMMTSF_DLINEAR_FUSED", "1") != "0"

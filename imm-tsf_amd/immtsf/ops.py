@@ -2530,3 +2530,79 @@ def mmf_xrank_q_eval(Y, P, bHO, M_u8, truth, mask, acc, d, H, kappa, precision, 
     check(lib.immtsf_mmf_xrank_q_eval(C.byref(cfg), ptr(ln_w), ptr(ln_b), ptr(Y), ptr(P), ptr(bHO), ptr(M_u8), ptr(out), None, 0, ptr(truth),
                                       ptr(mask), ptr(acc), ptr(sc), sc.numel(), ptr(tk), stream_ptr()), "mmf_xrank_q_eval")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ DLinear backbone
+_dl_tables = {}      # never emptied: a captured graph keeps reading the table it was captured with
+
+
+def dlinear_supported(S, P, Cc, k, individual):
+    """the limits of the fused DLinear path (immtsf_dlinear_supported): 1 <= S, P <= 128, odd k >= 1, any C >= 1"""
+    return bool(_lib.load().immtsf_dlinear_supported(int(S), int(P), int(Cc), int(k), 1 if individual else 0))
+
+
+def _dlinear_table(params, device):
+    """the device array of parameter pointers immtsf_dlinear_forward reads, [Ws | Wt | Wtau | bs | bt | btau][channel]: one host -> device
+    copy per distinct set of storages (so the first call with a new set has to be outside a stream capture, as every warm-up run is)"""
+    key = (device.type, device.index) + tuple(p.data_ptr() for p in params)
+    t = _dl_tables.get(key)
+    if t is None:
+        t = _dl_tables[key] = torch.tensor(key[2:], dtype=torch.int64, device=device)
+    return t
+
+
+class DLinearFn(torch.autograd.Function):
+    """DLinear.forecasting() (masked instance norm, moving-average decomposition, three Linear(S -> P) maps, de-normalisation) as ONE
+    launch; backward = the parameter gradients in TWO (immtsf_dlinear_forward / _backward, csrc/dlinear.hip).  data / mask (B, L, C) and
+    tp (B, L) are data: no gradient.  dims = (S, P, Lp, k, individual); params in the table's order, G = C (individual) or 1 tensors per
+    kind.  fp32 in either precision mode."""
+
+    @staticmethod
+    def forward(ctx, data, mask, tp, dims, table, *params):
+        lib = _lib.load()
+        S, P, Lp, k, individual = dims
+        data, mask, tp = _c(data), _c(mask), _c(tp)
+        _need_gpu(data, mask, tp, *params)
+        B, L, Cc = data.shape
+        y = torch.empty(B, Lp, Cc, dtype=torch.float32, device=data.device)
+        stats = torch.empty(2, B, Cc, dtype=torch.float32, device=data.device)      # mean, std: what the backward restages the rows with
+        check(lib.immtsf_dlinear_forward(B, L, Cc, S, P, Lp, k, individual, ptr(data), ptr(mask), ptr(tp), ptr(table), ptr(y),
+                                         ptr(stats[0]), ptr(stats[1]), stream_ptr()), "dlinear_forward")
+        ctx.dims = (B, L, Cc) + tuple(dims)
+        ctx.save_for_backward(data, mask, tp, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dY):
+        lib = _lib.load()
+        data, mask, tp, stats = ctx.saved_tensors
+        B, L, Cc, S, P, Lp, k, individual = ctx.dims
+        G = Cc if individual else 1
+        dY = dY.contiguous()
+        flat = torch.empty(3 * G * P * (S + 1), dtype=torch.float32, device=dY.device)      # every entry is written: no zero fill
+        dW = [flat[i * G * P * S:(i + 1) * G * P * S].view(G, P, S) for i in range(3)]
+        db = [flat[3 * G * P * S + i * G * P:3 * G * P * S + (i + 1) * G * P].view(G, P) for i in range(3)]
+        ws = _bytes(lib.immtsf_dlinear_workspace_bytes(B, S, P, Cc, individual), dY.device)
+        check(lib.immtsf_dlinear_backward(B, L, Cc, S, P, Lp, k, individual, ptr(data), ptr(mask), ptr(tp), ptr(stats[0]), ptr(stats[1]),
+                                          ptr(dY), ptr(dW[0]), ptr(dW[1]), ptr(dW[2]), ptr(db[0]), ptr(db[1]), ptr(db[2]), ptr(ws),
+                                          ws.numel(), stream_ptr()), "dlinear_backward")
+        rets = [t[g] for t in dW + db for g in range(G)]
+        return (None,) * 5 + tuple(r if need else None for r, need in zip(rets, ctx.needs_input_grad[5:]))
+
+
+def dlinear_forecast(data, mask, tp, Lp, S, P, k, seasonal, trend, time):
+    """data, mask (B, L <= S, C), tp (B, L) -> the de-normalised forecast (B, Lp <= P, C) of DLinear.  seasonal / trend / time: the
+    module's nn.Linear(S, P), or -- individual mode -- its nn.ModuleList of C of them."""
+    individual = not hasattr(seasonal, "weight")
+    B, L, Cc = data.shape
+    mods = [list(m) if individual else [m] for m in (seasonal, trend, time)]
+    params = [l.weight for m in mods for l in m] + [l.bias for m in mods for l in m]
+    G = Cc if individual else 1
+    if len(params) != 6 * G or any(not p.is_contiguous() or p.dtype != torch.float32 for p in params) or \
+            any(tuple(p.shape) != (P, S) for p in params[:3 * G]) or any(tuple(p.shape) != (P,) for p in params[3 * G:]):
+        raise _lib.ImmtsfError(f"dlinear_forecast: expected {G} contiguous fp32 Linear({S}, {P}) per map")
+    if not dlinear_supported(S, P, Cc, k, individual) or not (0 <= L <= S and 0 <= Lp <= P) or B < 1 or \
+            tuple(mask.shape) != (B, L, Cc) or tuple(tp.shape) != (B, L):
+        raise _lib.ImmtsfError(f"dlinear_forecast: shapes outside the fused kernel (B {B}, L {L}, C {Cc}, S {S}, P {P}, Lp {Lp}, k {k})")
+    return DLinearFn.apply(data, mask, tp, (int(S), int(P), int(Lp), int(k), 1 if individual else 0), _dlinear_table(params, data.device),
+                           *params)

@@ -585,6 +585,27 @@ size_t immtsf_eval_metrics_scratch_bytes(int32_t rows, int32_t C);
 int immtsf_eval_metrics_accum(const float* truth, const float* pred, const float* mask, int32_t rows, int32_t C, double* acc,
                               void* scratch, size_t scratch_bytes, uint32_t* ticket, immtsf_stream_t stream);
 
+/* ---- DLinear backbone (added within ABI 7: new functions only; csrc/dlinear.hip): forecasting() of reference models/DLinear.py:61-134 (masked instance norm, moving-average
+ * decomposition of layers/Autoformer_EncDec.py:21-52, three Linear(S -> P) maps on seasonal / trend / timestamps, de-normalisation) as ONE
+ * launch, and its parameter gradients as TWO (no input takes a gradient: everything after the normalisation is linear).  All fp32.
+ * S = input_len, P = pred_len, k = moving_avg; data / mask (B, L, C) and tp (B, L) are the UNPADDED history, L <= S (rows L..S-1 are zeros
+ * inside the kernel); y (B, Lp, C), Lp <= P, is written directly.  mean / stdev (B, C) are the forward's saved state: hand them to backward.
+ * params: a DEVICE array of 6 G pointers, G = individual ? C : 1, ordered [Ws | Wt | Wtau | bs | bt | btau][G] (weights (P, S), biases (P)).
+ * The six gradient buffers hold G stacked gradients each ((G, P, S) resp. (G, P)), overwritten; rows p >= Lp contribute nothing.  The sums
+ * over the B C rows run in an order fixed by the shape (per-workgroup slabs in `workspace`, folded in index order; no floating-point
+ * atomics, no zero-fill): the same inputs give the same bits.
+ * ..._supported: 1 <= S, P <= 128, C >= 1 (individual: C <= 65535), k odd, 1 <= k < 2^24 (k > S is fine); otherwise 0 and the compute calls
+ * return IMMTSF_EUNSUPPORTED.  ..._workspace_bytes: the backward's workspace (host arithmetic only; 0 for bad dimensions). */
+int immtsf_dlinear_supported(int32_t S, int32_t P, int32_t C, int32_t k, int32_t individual);
+size_t immtsf_dlinear_workspace_bytes(int32_t B, int32_t S, int32_t P, int32_t C, int32_t individual);
+int immtsf_dlinear_forward(int32_t B, int32_t L, int32_t C, int32_t S, int32_t P, int32_t Lp, int32_t k, int32_t individual,
+                           const float* data, const float* mask, const float* tp, const float* const* params, float* y, float* mean,
+                           float* stdev, immtsf_stream_t stream);
+int immtsf_dlinear_backward(int32_t B, int32_t L, int32_t C, int32_t S, int32_t P, int32_t Lp, int32_t k, int32_t individual,
+                            const float* data, const float* mask, const float* tp, const float* mean, const float* stdev, const float* dY,
+                            float* dWs, float* dWt, float* dWtau, float* dbs, float* dbt, float* dbtau, void* workspace,
+                            size_t workspace_bytes, immtsf_stream_t stream);
+
 /* ---- device-side batch builder: the reference's collate functions over a dataset that is
  * resident in HBM.  Replaces lib/parse_datasets.py:252-295 (variable_time_collate_fn), :298-366 +
  * lib/utils.py:359-413 (patch_variable_time_collate_fn / split_and_patch_batch) and :764-824 (multimodal wrapper).
