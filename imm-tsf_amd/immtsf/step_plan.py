@@ -11,8 +11,11 @@ from . import _lib
 
 
 class StepPlan:
-    def __init__(self, err=None):
-        self.err = err                  # time-out report address of the flag waits below (FlagStep's guard word)
+    # what an engine switches between the phases of a step, with offering()
+    OFFERS = ("fold_stream", "fold_flag", "gate", "head_flag", "hold_params", "wgrad_flags", "defer", "tail_flag", "ttf_flag", "announce")
+
+    def __init__(self, err=None, timeout_ms=50):
+        self.err, self.timeout_ms = err, timeout_ms     # the flag waits below: time-out report address (FlagStep's guard word), time-out
         # the text side's forward: MMF_XAttn_Add's fold (parameters only) on `fold_stream`, handed over by `fold_flag` or a stream wait
         self.fold_stream = self.fold_flag = None
         # scheduling gate, (flag, time-out report address): TTF_T2V_XAttn's backward sets it behind its row-bound kernels, the patch
@@ -27,11 +30,25 @@ class StepPlan:
         self.defer, self.tail_flag, self.ttf_flag, self.tail_set, self.jobs = 0, None, None, False, []
         self.announce = None            # FlagStep, data parallel: FlatTrainer's bucket hooks announce the bucket through this instead
 
-    def _set(self, flag, stream):
+    @contextlib.contextmanager
+    def offering(self, **fields):
+        """the named offers hold for the body; on the way out, raised or not, the previous values are back"""
+        if not set(fields) <= set(self.OFFERS):
+            raise AttributeError(f"StepPlan has no offer {sorted(set(fields) - set(self.OFFERS))[0]!r}")
+        before = {k: getattr(self, k) for k in fields}
+        self.__dict__.update(fields)
+        try:
+            yield self
+        finally:
+            self.__dict__.update(before)
+
+    def set(self, flag, stream):
+        """`stream` (raw handle) sets the device flag at address `flag`"""
         _lib.check(_lib.load().immtsf_flag_set(flag, stream), "flag_set")
 
-    def _wait(self, flag, stream, err=None):
-        _lib.check(_lib.load().immtsf_flag_wait(flag, self.err if err is None else err, 50, stream), "flag_wait")
+    def wait(self, flag, stream, err=None):
+        """`stream` spins on `flag`; after `timeout_ms` it gives up and reports to `err` (default: the plan's)"""
+        _lib.check(_lib.load().immtsf_flag_wait(flag, self.err if err is None else err, self.timeout_ms, stream), "flag_wait")
 
     def fold(self, launch, *uses):
         """run `launch(raw stream)` on the fold stream, hand its result (and `uses`) to the current stream; False: none offered"""
@@ -43,8 +60,8 @@ class StepPlan:
             t.record_stream(L)
         launch(L.cuda_stream)
         if self.fold_flag is not None:
-            self._set(self.fold_flag, L.cuda_stream)
-            self._wait(self.fold_flag, cur.cuda_stream)
+            self.set(self.fold_flag, L.cuda_stream)
+            self.wait(self.fold_flag, cur.cuda_stream)
         else:
             cur.wait_stream(L)
         return True
@@ -56,9 +73,9 @@ class StepPlan:
             return self.gate[0]
 
     def wait_gate(self):
-        """the current stream spins on the gate when a forward on ANOTHER stream armed it (a hint: it gives up after 50 ms)"""
+        """the current stream spins on the gate when a forward on ANOTHER stream armed it (a hint: it gives up after `timeout_ms`)"""
         if self.gate is not None and self._armed not in (None, torch.cuda.current_stream().cuda_stream):
-            self._wait(self.gate[0], _lib.stream_ptr(), err=self.gate[1])
+            self.wait(self.gate[0], _lib.stream_ptr(), err=self.gate[1])
 
     def take_head_flag(self, dY):
         """-> the head flag, handed out once (None: not offered); `dY`: the buffer the kernel publishes"""
@@ -83,15 +100,15 @@ class StepPlan:
         """a weight gradient `launch(raw stream)` leaves the current stream: a flag (the pool's next, or `ttf`: the TTF phase flag) is
         set here, and a job waits for it on the parameter branch, then launches.  `keep`: what the launch reads, held until then."""
         flag, jobs = (self.ttf_flag, self.jobs) if ttf else (self.wgrad_flags.pop(), self.jobs_b)
-        self._set(flag, _lib.stream_ptr())
+        self.set(flag, _lib.stream_ptr())
 
         def job(stream, keep=keep):
-            self._wait(flag, stream)
+            self.wait(flag, stream)
             launch(stream)
         jobs.append(job)
 
     def set_tail(self):
-        self._set(self.tail_flag, _lib.stream_ptr())
+        self.set(self.tail_flag, _lib.stream_ptr())
         self.tail_set = True            # (the parameter branch waits for the TAIL flag only when somebody set it)
 
 

@@ -13,14 +13,25 @@
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, List, Optional, Sequence
+from types import SimpleNamespace
+from typing import Iterable, Optional, Sequence
 
 import os
 
 import torch
 
 from . import _lib, ops, step_plan
+from .announce import Announcer, merge_tail, runs, static_order
 from .step_plan import StepPlan
+
+
+def _convert(src, dst):
+    """dst <- src between fp32 and bf16 (round to nearest even / exact widening): on the GPU the 16-byte conversion kernels"""
+    if not src.is_cuda:
+        dst.copy_(src)
+        return
+    name = "f32_to_bf16" if dst.dtype == torch.bfloat16 else "bf16_to_f32"
+    _lib.check(getattr(_lib.load(), "immtsf_" + name)(_lib.ptr(src), _lib.ptr(dst), src.numel(), _lib.stream_ptr()), name)
 
 
 def shard_range(n_items: int, rank: int, world: int):
@@ -157,7 +168,6 @@ class FlatTrainer:
         # hooks would sum the sink buckets twice and race with it on the communication stream)
         self.overlap = overlap and self.collective and dev.type == "cuda" and not self.sharded
         self.comm_stream = torch.cuda.Stream(device=dev) if self.overlap else None
-        self._pending: List = []
         self._reduced = [False] * len(self.buckets)
         if self.collective and dev.type == "cuda" and not self.sharded:
             for bi in self.sink_buckets:
@@ -183,12 +193,7 @@ class FlatTrainer:
         if self.master is not None:
             self.master.copy_(self.flat_param[self.shard[0]:self.shard[1]])
         if self.flat_twin is not None:
-            if self.flat_param.is_cuda:
-                lib = _lib.load()
-                _lib.check(lib.immtsf_f32_to_bf16(_lib.ptr(self.flat_param), _lib.ptr(self.flat_twin), self.flat_param.numel(),
-                                                  _lib.stream_ptr()), "f32_to_bf16")
-            else:
-                self.flat_twin.copy_(self.flat_param)
+            _convert(self.flat_param, self.flat_twin)
             if self.master is not None:
                 self.flat_param.copy_(self.flat_twin)
 
@@ -263,7 +268,6 @@ class FlatTrainer:
     def _bucket_ready(self, bi: int):
         if not self.collective or self.sharded or self._reduced[bi]:
             return
-        import torch.distributed as dist
         if bi not in self.sink_buckets:
             self._collect_autograd_grads()
         lo, hi = self.ranges[bi]
@@ -286,15 +290,9 @@ class FlatTrainer:
             dist.all_reduce(g, group=self.group)
             return
         w = self._wire[lo:hi]
-        if g.is_cuda:                   # 16-byte conversion kernels (round to nearest even / exact widening)
-            lib = _lib.load()
-            _lib.check(lib.immtsf_f32_to_bf16(_lib.ptr(g), _lib.ptr(w), g.numel(), _lib.stream_ptr()), "f32_to_bf16")
-            dist.all_reduce(w, group=self.group)
-            _lib.check(lib.immtsf_bf16_to_f32(_lib.ptr(w), _lib.ptr(g), g.numel(), _lib.stream_ptr()), "bf16_to_f32")
-        else:
-            w.copy_(g)
-            dist.all_reduce(w, group=self.group)
-            g.copy_(w)
+        _convert(g, w)
+        dist.all_reduce(w, group=self.group)
+        _convert(w, g)
 
     def sync_grads(self):
         """all-reduce (sum) whatever has not been reduced yet and join the communication stream.  The loss is
@@ -310,7 +308,6 @@ class FlatTrainer:
             return
         if self.collective:
             if not self.overlap and not any(self._reduced):
-                import torch.distributed as dist
                 self._all_reduce(0, self.flat_grad.numel())            # one collective for the whole flat buffer
                 self._reduced = [True] * len(self.buckets)
             for bi in range(len(self.buckets)):
@@ -327,22 +324,14 @@ class FlatTrainer:
         native = dist.get_backend(self.group) != "gloo"
         if self.grad_wire == "bf16":
             w = self._wire
-            if g.is_cuda:
-                lib = _lib.load()
-                _lib.check(lib.immtsf_f32_to_bf16(_lib.ptr(g), _lib.ptr(w), g.numel(), _lib.stream_ptr()), "f32_to_bf16")
-            else:
-                w.copy_(g)
+            _convert(g, w)
             if native:
                 dist.reduce_scatter_tensor(self._wire_shard, w, group=self.group)
                 src = self._wire_shard
             else:
                 dist.all_reduce(w, group=self.group)
                 src = w[lo:hi]
-            if g.is_cuda:
-                lib = _lib.load()
-                _lib.check(lib.immtsf_bf16_to_f32(_lib.ptr(src), _lib.ptr(g[lo:hi]), hi - lo, _lib.stream_ptr()), "bf16_to_f32")
-            else:
-                g[lo:hi].copy_(src)
+            _convert(src, g[lo:hi])
         elif native:
             dist.reduce_scatter_tensor(self._grad_shard, g, group=self.group)
             g[lo:hi].copy_(self._grad_shard)
@@ -379,16 +368,7 @@ class FlatTrainer:
             sq = (g * g).sum().reshape(1)
             if self.collective:
                 dist.all_reduce(sq, group=self.group)
-            gg = g
-            if self.max_norm and self.max_norm > 0:
-                gg = g * torch.clamp(self.max_norm / (sq.sqrt() + 1e-6), max=1.0)
-            if self.wd:
-                gg = gg + self.wd * p
-            b1, b2 = self.betas
-            self.exp_avg.mul_(b1).add_(gg, alpha=1 - b1)
-            self.exp_avg_sq.mul_(b2).addcmul_(gg, gg, value=1 - b2)
-            bc1, bc2 = 1 - b1 ** self.step_count, 1 - b2 ** self.step_count
-            p.addcdiv_(self.exp_avg, self.exp_avg_sq.sqrt() / (bc2 ** 0.5) + self.eps, value=-self.lr / bc1)
+            self._adam_cpu(p, g, sq.sqrt())
             if self.flat_twin is not None:
                 self.flat_twin[lo:hi].copy_(p)
         if not self.collective:          # rank-local leg: the other ranks' shards simply keep their values
@@ -397,12 +377,7 @@ class FlatTrainer:
             return
         if self.param_wire == "bf16":
             self._all_gather(self.flat_twin, self.flat_twin[lo:hi])
-            if self.flat_param.is_cuda:
-                lib = _lib.load()
-                _lib.check(lib.immtsf_bf16_to_f32(_lib.ptr(self.flat_twin), _lib.ptr(self.flat_param), self.flat_param.numel(),
-                                                  _lib.stream_ptr()), "bf16_to_f32")
-            else:
-                self.flat_param.copy_(self.flat_twin)
+            _convert(self.flat_twin, self.flat_param)
         else:
             self._all_gather(self.flat_param, self.flat_param[lo:hi])
             self.refresh_twins()
@@ -412,44 +387,38 @@ class FlatTrainer:
         if self.sharded:
             self._step_sharded()
             return
-        if self.flat_param.is_cuda and self.device_step and getattr(self, "step_guard", None):
-            # behind a guard word (FlagStep's time-out report): a non-zero word drops the step on the device -- no update from
-            # gradients a missed hand-over may have left incomplete (csrc/tail.hip sqnorm_partial_kernel / adam_kernel)
-            lib = _lib.load()
-            zero = getattr(self, "zero_in_step", False)
-            self._grad_zeroed_by_step = bool(zero)
-            _lib.check(lib.immtsf_adam_step_guarded(_lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), _lib.ptr(self.exp_avg),
-                                                    _lib.ptr(self.exp_avg_sq), self.flat_param.numel(), self.lr, self.betas[0],
-                                                    self.betas[1], self.eps, self.wd, _lib.ptr(self.step_dev), self.max_norm,
-                                                    _lib.ptr(self.norm_scratch), _lib.ptr(self.drop_dev), int(self.step_guard),
-                                                    1 if zero else 0, _lib.stream_ptr()), "adam_step_guarded")
-        elif self.flat_param.is_cuda and self.device_step:
-            lib = _lib.load()
-            zero = getattr(self, "zero_in_step", False)
-            fn = lib.immtsf_adam_step_dev_zero if zero else lib.immtsf_adam_step_dev
-            self._grad_zeroed_by_step = bool(zero)
-            _lib.check(fn(_lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), _lib.ptr(self.exp_avg),
-                                                _lib.ptr(self.exp_avg_sq), self.flat_param.numel(), self.lr, self.betas[0],
-                                                self.betas[1], self.eps, self.wd, _lib.ptr(self.step_dev), self.max_norm,
-                                                _lib.ptr(self.norm_scratch), _lib.ptr(self.drop_dev), _lib.stream_ptr()),
-                       "adam_step_dev")
+        if self.flat_param.is_cuda and self.device_step:
+            lib, zero = _lib.load(), bool(getattr(self, "zero_in_step", False))
+            self._grad_zeroed_by_step = zero
+            args = (_lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq),
+                    self.flat_param.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.wd, _lib.ptr(self.step_dev),
+                    self.max_norm, _lib.ptr(self.norm_scratch), _lib.ptr(self.drop_dev))
+            if getattr(self, "step_guard", None):
+                # behind a guard word (FlagStep's time-out report): a non-zero word drops the step on the device -- no update from
+                # gradients a missed hand-over may have left incomplete (csrc/tail.hip sqnorm_partial_kernel / adam_kernel)
+                _lib.check(lib.immtsf_adam_step_guarded(*args, int(self.step_guard), 1 if zero else 0, _lib.stream_ptr()), "adam_step_guarded")
+            else:
+                fn = lib.immtsf_adam_step_dev_zero if zero else lib.immtsf_adam_step_dev
+                _lib.check(fn(*args, _lib.stream_ptr()), "adam_step_dev")
         elif self.flat_param.is_cuda:
-            lib = _lib.load()
-            _lib.check(lib.immtsf_adam_step(_lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), _lib.ptr(self.exp_avg),
-                                            _lib.ptr(self.exp_avg_sq), self.flat_param.numel(), self.lr, self.betas[0],
-                                            self.betas[1], self.eps, self.wd, self.step_count, self.max_norm,
-                                            _lib.ptr(self.norm_scratch), _lib.stream_ptr()), "adam_step")
-        else:   # CPU (gloo tests of the DP logic only): same arithmetic in torch ops
-            g = self.flat_grad
-            if self.max_norm and self.max_norm > 0:
-                g = g * torch.clamp(self.max_norm / (g.norm() + 1e-6), max=1.0)
-            if self.wd:
-                g = g + self.wd * self.flat_param
-            b1, b2 = self.betas
-            self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
-            self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
-            bc1, bc2 = 1 - b1 ** self.step_count, 1 - b2 ** self.step_count
-            self.flat_param.addcdiv_(self.exp_avg, self.exp_avg_sq.sqrt() / (bc2 ** 0.5) + self.eps, value=-self.lr / bc1)
+            _lib.check(_lib.load().immtsf_adam_step(_lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), _lib.ptr(self.exp_avg),
+                                                    _lib.ptr(self.exp_avg_sq), self.flat_param.numel(), self.lr, self.betas[0],
+                                                    self.betas[1], self.eps, self.wd, self.step_count, self.max_norm,
+                                                    _lib.ptr(self.norm_scratch), _lib.stream_ptr()), "adam_step")
+        else:
+            self._adam_cpu(self.flat_param, self.flat_grad, self.flat_grad.norm())
+
+    def _adam_cpu(self, p, g, norm):
+        """CPU (gloo tests of the DP logic only): the kernels' arithmetic in torch ops; `norm`: the whole gradient's"""
+        if self.max_norm and self.max_norm > 0:
+            g = g * torch.clamp(self.max_norm / (norm + 1e-6), max=1.0)
+        if self.wd:
+            g = g + self.wd * p
+        b1, b2 = self.betas
+        self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
+        self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
+        bc1, bc2 = 1 - b1 ** self.step_count, 1 - b2 ** self.step_count
+        p.addcdiv_(self.exp_avg, self.exp_avg_sq.sqrt() / (bc2 ** 0.5) + self.eps, value=-self.lr / bc1)
 
     def adam_prepare(self, pending=None, err=None, skip_out=None, from_wire=False, guard=False):
         """first half of clip + Adam as launches the caller places (include/immtsf.h immtsf_adam_prepare): the squared norm of the whole
@@ -496,12 +465,7 @@ class FlatTrainer:
             self.step_dev.copy_(s["step_dev"])
             self.drop_dev.copy_(s["drop_dev"])
         if self.flat_twin is not None:
-            if self.flat_param.is_cuda:
-                lib = _lib.load()
-                _lib.check(lib.immtsf_f32_to_bf16(_lib.ptr(self.flat_param), _lib.ptr(self.flat_twin), self.flat_param.numel(),
-                                                  _lib.stream_ptr()), "f32_to_bf16")
-            else:
-                self.flat_twin.copy_(self.flat_param)
+            _convert(self.flat_param, self.flat_twin)
 
     def flush(self):
         """apply an optimizer step a step engine still holds back (FlagStep runs clip + Adam of step k at the head of replay k + 1): a
@@ -564,6 +528,18 @@ class FlatTrainer:
         return self.flat_grad.numel() * 4
 
 
+def _warm_up(trainer, eager_step, warmup, restore=True):
+    """`warmup` REAL steps (allocator pools, lazy inits, RCCL channels); `restore`: parameters, moments and the step / dropout counters
+    are put back afterwards, so that the first replay is training step 1 from the caller's weights"""
+    snap = trainer.snapshot() if restore else None
+    for _ in range(warmup):
+        eager_step()
+    torch.cuda.synchronize()
+    if snap is not None:
+        trainer.restore(snap)
+        torch.cuda.synchronize()
+
+
 class GraphedStep:
     """One training step as two hipGraphs (HIP streams + graphs instead of a tracing compiler):
         graph A = zero-grad, forward, loss, backward, gradient collection into the flat buffer
@@ -593,19 +569,14 @@ class GraphedStep:
             trainer.zero_in_step = True
         side = torch.cuda.Stream(device=trainer.flat_param.device)
         side.wait_stream(torch.cuda.current_stream())
-        # the warm-up runs REAL steps (allocator pools, lazy inits, RCCL channels): parameters, moments and the step / dropout
-        # counters are put back afterwards, so that the first replay is training step 1 from the caller's weights
-        snap = trainer.snapshot() if restore_after_warmup else None
+
+        def eager_step():
+            self._fwd_bwd()
+            trainer.sync_grads()
+            trainer.step()
         with torch.cuda.stream(side):           # off the default stream
-            for _ in range(warmup):
-                self._fwd_bwd()
-                trainer.sync_grads()
-                trainer.step()
+            _warm_up(trainer, eager_step, warmup, restore_after_warmup)
         torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        if snap is not None:
-            trainer.restore(snap)
-            torch.cuda.synchronize()
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_a):
             self.loss = self._fwd_bwd()
@@ -621,15 +592,15 @@ class GraphedStep:
         # (the 32 MB gradient memset as a third parallel branch of graph A, beside the forward, was measured: the step
         # got 5 % SLOWER -- 1.18 vs 1.12 ms -- so it stays in front of the forward)
         self.trainer.zero_grad()
-        plan = StepPlan()
+        plan, gate = StepPlan(), None
         if self.sched is not None:
             # scheduling gate (StepPlan.gate): the patch encoder's backward -- parameter gradients only, but a kernel that fills
             # every CU's LDS for a millisecond at thousands of windows -- starts when the text side's row-bound backward kernels are
             # through, beside its small-launch tail, instead of beside them (4096 windows: a 19 us reduction took 0.7 ms in its shade)
             fp = self.sched.data_ptr()
             _lib.check(_lib.load().immtsf_flags_clear(fp, 2, torch.cuda.current_stream().cuda_stream), "flags_clear")
-            plan.gate = (fp, fp + 4)
-        with step_plan.install(plan):
+            gate = (fp, fp + 4)
+        with step_plan.install(plan), plan.offering(gate=gate):
             loss = self.loss_fn()
             ops.backward_unit(loss)
         self.trainer.collect_grads()
@@ -650,81 +621,31 @@ class GraphedStep:
         return self.loss
 
 
-class PhasedStep:
-    """One training step as SIX single-stream hipGraphs replayed on TWO HIP streams, with HIP events between them.
-
-    The step has two chains that only meet at the modality fusion: the text side (TTF + the key/value half of MMF) and
-    the backbone.  Captured as parallel branches of ONE hipGraph they are at the mercy of the graph executor: on
-    ROCm 7.2 the branch that is not the capturing stream's continuation started 200-400 us after its inputs were ready
-    (r02 traces: the forward overlapped, the two backward branches ran one after the other although the captured
-    dependencies were exactly fork -> join).  Here every graph is a plain chain, the parallelism is two real streams, and
-    the dependencies are event waits the host enqueues between graph launches:
-
-        stream T (text):      T1 zero-grad, TTF fwd, MMF k|v fwd ........ T2 MMF query half fwd, loss, its backward ... T3 k|v + TTF bwd .. O clip+Adam
-        stream B (backbone):  B1 backbone fwd ............................(waits T2) B2 backbone bwd, gradient collection ..........^
-                                          T2 waits B1                                                      O waits B2
-
-    text_fn() -> tuple of tensors (those that require grad are cut: the head sees detached copies and their gradients
-    are fed back into T3); backbone_fn() -> pred_y; head_fn(pred_y, *text_out) -> scalar loss.  Needs
-    FlatTrainer(device_step=True).  world > 1: one eager all-reduce of the flat gradient in front of O (like
-    GraphedStep without captured collectives)."""
+class _SplitStep:
+    """What the engines that split the step (text side | backbone | head) share: two streams, the eager step, the head, the text backward."""
 
     head_published = False      # FlagStep: the head's kernel publishes "dY_ts is ready" itself (StepPlan.take_head_flag)
 
-    def __init__(self, trainer: FlatTrainer, text_fn, backbone_fn, head_fn, warmup: int = 3):
+    def __init__(self, trainer: FlatTrainer, text_fn, backbone_fn, head_fn):
         if not trainer.device_step:
-            raise ValueError("PhasedStep needs FlatTrainer(device_step=True): host-side step counters would freeze in the graphs")
+            raise ValueError(f"{type(self).__name__} needs FlatTrainer(device_step=True): host-side step counters would freeze in the graphs")
         self.trainer = trainer
         self.text_fn, self.backbone_fn, self.head_fn = text_fn, backbone_fn, head_fn
         if trainer.collective:
-            trainer.overlap = False
-        dev = trainer.flat_param.device
-        self.T, self.B = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
-        cur = torch.cuda.current_stream()
-        self.T.wait_stream(cur)
-        self.B.wait_stream(cur)
-        snap = trainer.snapshot()
-        for _ in range(warmup):       # eager REAL steps on the two streams (allocator pools, lazy inits, RCCL channels) ...
-            self._eager_step()
-        torch.cuda.synchronize()
-        trainer.restore(snap)         # ... undone: the first replay is training step 1 from the caller's weights
-        torch.cuda.synchronize()
-        G = torch.cuda.CUDAGraph
-        self.gT1, self.gB1, self.gT2, self.gB2, self.gT3, self.gO = G(), G(), G(), G(), G(), G()
-        # one memory pool per stream: graphs that replay concurrently must never be handed each other's freed blocks
-        poolT, poolB = torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle()
-        with torch.cuda.graph(self.gT1, pool=poolT, stream=self.T):
-            trainer.zero_grad()
-            outs = text_fn()
-        with torch.cuda.graph(self.gB1, pool=poolB, stream=self.B):
-            pred = backbone_fn()
-        with step_plan.install(StepPlan()) as plan:       # (the head's parameter gradients wait for the text-side backward)
-            with torch.cuda.graph(self.gT2, pool=poolT, stream=self.T):
-                py, cuts, loss, dcuts = self._head(plan, pred, outs)
-                dpy = py.grad
-            with torch.cuda.graph(self.gB2, pool=poolB, stream=self.B):
-                torch.autograd.backward([pred], [dpy])
-                trainer.collect_grads()
-            with torch.cuda.graph(self.gT3, pool=poolT, stream=self.T):
-                self._text_backward(plan, outs, dcuts)
-        # the optimizer as a graph -- unless it holds collectives (sharded: norm all-reduce + parameter all-gather), which stay eager
-        # like GraphedStep's (capture_collectives is the only path that puts RCCL calls into a graph)
-        self.opt_eager = bool(trainer.sharded and trainer.collective)
-        if not self.opt_eager:
-            with torch.cuda.graph(self.gO, pool=poolT, stream=self.T):
-                trainer.step()
-        self.loss = loss
-        self._keep = (outs, pred, py, cuts, dpy, dcuts)          # boundary tensors live in the graphs' pools: keep them referenced
-        self.eB1, self.eT2, self.eB2, self.eO = (torch.cuda.Event() for _ in range(4))
-        self.eO.record(self.T)
+            trainer.overlap = False           # no collectives from inside a captured backward
+        self.T, self.B = self._stream(), self._stream()
+
+    def _stream(self):
+        s = torch.cuda.Stream(device=self.trainer.flat_param.device)
+        s.wait_stream(torch.cuda.current_stream())
+        return s
 
     def _head(self, plan, pred, outs):
         py = pred.detach().requires_grad_(True)
         cuts = [o.detach().requires_grad_(True) if (torch.is_tensor(o) and o.requires_grad) else o for o in outs]
         loss = self.head_fn(py, *cuts)
-        plan.hold_params = True       # the head's parameter gradients are enqueued behind the text-side backward (T3)
-        ops.backward_unit(loss)
-        plan.hold_params = False
+        with plan.offering(hold_params=True):     # the head's parameter gradients are enqueued behind the text-side backward (T3)
+            ops.backward_unit(loss)
         return py, cuts, loss, [c.grad if (torch.is_tensor(c) and c.requires_grad) else None for c in cuts]
 
     @staticmethod
@@ -759,6 +680,58 @@ class PhasedStep:
             t.sync_grads()
             t.step()
         return loss
+
+
+class PhasedStep(_SplitStep):
+    """One training step as SIX single-stream hipGraphs replayed on TWO HIP streams, with HIP events between them.
+
+    The step has two chains that only meet at the modality fusion: the text side (TTF + the key/value half of MMF) and
+    the backbone.  Captured as parallel branches of ONE hipGraph they are at the mercy of the graph executor: on
+    ROCm 7.2 the branch that is not the capturing stream's continuation started 200-400 us after its inputs were ready
+    (r02 traces: the forward overlapped, the two backward branches ran one after the other although the captured
+    dependencies were exactly fork -> join).  Here every graph is a plain chain, the parallelism is two real streams, and
+    the dependencies are event waits the host enqueues between graph launches:
+
+        stream T (text):      T1 zero-grad, TTF fwd, MMF k|v fwd ........ T2 MMF query half fwd, loss, its backward ... T3 k|v + TTF bwd .. O clip+Adam
+        stream B (backbone):  B1 backbone fwd ............................(waits T2) B2 backbone bwd, gradient collection ..........^
+                                          T2 waits B1                                                      O waits B2
+
+    text_fn() -> tuple of tensors (those that require grad are cut: the head sees detached copies and their gradients
+    are fed back into T3); backbone_fn() -> pred_y; head_fn(pred_y, *text_out) -> scalar loss.  Needs
+    FlatTrainer(device_step=True).  world > 1: one eager all-reduce of the flat gradient in front of O (like
+    GraphedStep without captured collectives)."""
+
+    def __init__(self, trainer: FlatTrainer, text_fn, backbone_fn, head_fn, warmup: int = 3):
+        super().__init__(trainer, text_fn, backbone_fn, head_fn)
+        _warm_up(trainer, self._eager_step, warmup)       # (eager steps on the two streams)
+        G = torch.cuda.CUDAGraph
+        self.gT1, self.gB1, self.gT2, self.gB2, self.gT3, self.gO = G(), G(), G(), G(), G(), G()
+        # one memory pool per stream: graphs that replay concurrently must never be handed each other's freed blocks
+        poolT, poolB = torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle()
+        with torch.cuda.graph(self.gT1, pool=poolT, stream=self.T):
+            trainer.zero_grad()
+            outs = text_fn()
+        with torch.cuda.graph(self.gB1, pool=poolB, stream=self.B):
+            pred = backbone_fn()
+        with step_plan.install(StepPlan()) as plan:       # (the head's parameter gradients wait for the text-side backward)
+            with torch.cuda.graph(self.gT2, pool=poolT, stream=self.T):
+                py, cuts, loss, dcuts = self._head(plan, pred, outs)
+                dpy = py.grad
+            with torch.cuda.graph(self.gB2, pool=poolB, stream=self.B):
+                torch.autograd.backward([pred], [dpy])
+                trainer.collect_grads()
+            with torch.cuda.graph(self.gT3, pool=poolT, stream=self.T):
+                self._text_backward(plan, outs, dcuts)
+        # the optimizer as a graph -- unless it holds collectives (sharded: norm all-reduce + parameter all-gather), which stay eager
+        # like GraphedStep's (capture_collectives is the only path that puts RCCL calls into a graph)
+        self.opt_eager = bool(trainer.sharded and trainer.collective)
+        if not self.opt_eager:
+            with torch.cuda.graph(self.gO, pool=poolT, stream=self.T):
+                trainer.step()
+        self.loss = loss
+        self._keep = (outs, pred, py, cuts, dpy, dcuts)          # boundary tensors live in the graphs' pools: keep them referenced
+        self.eB1, self.eT2, self.eB2, self.eO = (torch.cuda.Event() for _ in range(4))
+        self.eO.record(self.T)
 
     def __call__(self):
         t, T, B = self.trainer, self.T, self.B
@@ -795,7 +768,7 @@ class PhasedStep:
         return self.loss
 
 
-class FlagStep(PhasedStep):
+class FlagStep(_SplitStep):
     """PhasedStep's decomposition (text / backbone / head) as ONE hipGraph per step whose branches have NO edges between the fork at the
     start of the step and the join at its end: where a branch needs another's result it spins on a device flag (csrc/sync.hip) instead
     of waiting on an event.
@@ -828,15 +801,18 @@ class FlagStep(PhasedStep):
     peers' same collective, which sits behind the peers' own spins; graph k + 1 waits (one eager spin on S) for the communication
     stream's last bump of step k.
 
-    Fail-safe.  Every spin gives up after `timeout_ms` and sets the guard word flags[8].  The step decision reads it -- and, data
+    Fail-safe.  Every spin gives up after `timeout_ms` and sets the guard word (_ERR).  The step decision reads it -- and, data
     parallel, the ranks' guard words SUMMED by the step's last collective (a slot behind the last bucket), so EVERY rank drops the same
     step (no update, step not counted, gradient zeroed) and the replicas stay identical; the word is sticky until clear_error().
     `check()` raises on every rank; `check_every` > 0 makes __call__ do that every so many steps."""
 
-    # flag words (int32 offsets into self.flags)
-    _B1, _T2, _B2, _FOLD, _TAIL, _P2, _SCHED, _SCHED_TO, _TTF = range(9)        # hand-over flags: cleared at the end of every replay
-    _COUNT0 = 16                            # one counting flag per announced bucket
-    _ERR, _PENDING, _SKIP, _COMM_DONE = 40, 41, 42, 43      # guard word, gradient pending, step decision, collectives done
+    # the flag buffer: _WORDS int32 words (offsets into self.flags)
+    _B1, _T2, _B2, _FOLD, _TAIL, _P2, _SCHED, _SCHED_TO, _TTF = range(9)        # hand-over flags
+    _CLEARED = 16                               # the hand-over flags and the spare words behind them are cleared at the end of every replay
+    _SPARE = range(_CLEARED - 1, _TTF, -1)      # 15 .. 9, highest first: one per weight gradient that backbone_wgrad_tail defers
+    _COUNT0, _COUNTS = _CLEARED, 24             # counting flags (never cleared): one per announced segment
+    _ERR, _PENDING, _SKIP, _COMM_DONE = range(_COUNT0 + _COUNTS, _COUNT0 + _COUNTS + 4)     # guard word, gradient pending, step decision, collectives done
+    _WORDS = 48
 
     def __init__(self, trainer: FlatTrainer, text_fn, backbone_fn, head_fn, warmup: int = 3, param_tail: Optional[int] = None,
                  fold_by_flag: bool = True, head_flag: bool = True, param_branch: bool = True, sched_gate: bool = True,
@@ -856,215 +832,174 @@ class FlagStep(PhasedStep):
         feed-forward projections) leave the backbone's dependent chain the same way: the data gradient stays, the grouped weight-gradient
         launch runs on the parameter branch behind a flag of its own (up to seven layers per step; needs param_branch and gradient
         sinks).  The backbone's buckets are then announced on that branch."""
-        if not trainer.device_step:
-            raise ValueError("FlagStep needs FlatTrainer(device_step=True)")
+        super().__init__(trainer, text_fn, backbone_fn, head_fn)
         if trainer.sharded:
             raise ValueError("FlagStep reduces whole buckets: use GraphedStep / PhasedStep with a sharded optimizer")
-        self.trainer = trainer
-        self.text_fn, self.backbone_fn, self.head_fn = text_fn, backbone_fn, head_fn
-        dev = trainer.flat_param.device
-        lib = _lib.load()
-        self.dist = bool(trainer.collective)
+        self.dist = bool(trainer.collective)          # (the bucket hooks bump flags instead of starting collectives)
         self.timeout_ms, self.comm_timeout_ms, self.check_every = int(timeout_ms), int(comm_timeout_ms), int(check_every)
-        self.T, self.B = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
         # parameter-only work (MMF_XAttn_Add's fold in front, its parameter-gradient chain behind) on a THIRD branch of the graph
-        self.P = torch.cuda.Stream(device=dev) if param_branch else self.B
+        self.P = self._stream() if param_branch else self.B
         # launches of MMF_XAttn_Add's parameter chain left to the parameter branch (without one, data parallel: none -- the bucket's
         # hook must fire behind its LAST gradient write, on the branch that announces it)
-        self._defer = (3 if param_branch else (0 if self.dist else 1)) if param_tail is None else int(param_tail)
-        if self.dist:
-            trainer.overlap = False           # no collectives from inside the captured backward (the hooks bump flags instead)
-            if not param_branch:
-                self._defer = 0
-        nb = len(trainer.buckets)
+        self._defer = 0 if (self.dist and not param_branch) else ((3 if param_branch else 1) if param_tail is None else int(param_tail))
         if adam_split is not None:
             listed = sorted(b for grp in adam_split for b in grp)
-            if len(adam_split) != 3 or listed != list(range(nb)):
+            if len(adam_split) != 3 or listed != list(range(len(trainer.buckets))):
                 raise ValueError("adam_split must be three lists that hold every bucket index exactly once")
             if not param_branch and adam_split[2]:
                 adam_split = (list(adam_split[0]), list(adam_split[1]) + list(adam_split[2]), [])
-        cur = torch.cuda.current_stream()
-        self.T.wait_stream(cur)
-        self.B.wait_stream(cur)
-        self.P.wait_stream(cur)
         # (before the warm-up: its last Adam pass then leaves the gradient buffer zero, and the captured zero_grad() holds no fill)
         trainer.zero_in_step = True
-        snap = trainer.snapshot()
-        for _ in range(warmup):
-            self._eager_step()
-        torch.cuda.synchronize()
-        trainer.restore(snap)
+        _warm_up(trainer, self._eager_step, warmup)
         trainer.flat_grad.zero_()
         torch.cuda.synchronize()
-        self.flags = torch.zeros(48, dtype=torch.int32, device=dev)
-        fp = self.flags.data_ptr()
-        W = lambda i: fp + 4 * i        # noqa: E731
-        F_B1, F_T2, F_B2, F_P2, F_ERR = W(self._B1), W(self._T2), W(self._B2), W(self._P2), W(self._ERR)
-        self._f_err, self._f_pending, self._f_skip, self._f_comm = F_ERR, W(self._PENDING), W(self._SKIP), W(self._COMM_DONE)
-        sp = lambda st: st.cuda_stream        # noqa: E731
-        tmo = self.timeout_ms
-
-        def fset(flag, st):
-            _lib.check(lib.immtsf_flag_set(flag, sp(st)), "flag_set")
-
-        def fwait(flag, st):
-            _lib.check(lib.immtsf_flag_wait(flag, F_ERR, tmo, sp(st)), "flag_wait")
-
-        bf16_wire = self.dist and trainer._wire is not None
-        self._from_wire = bf16_wire
-        # data parallel: counting flags (never cleared), one per announced bucket
-        self.segments = []                    # [dict(flag, lo, hi, buckets, branch)]
-        announced = set()
-        branch_now = ["T"]
-
-        def announce_range(lo, hi, buckets, burst=None):
-            if hi == lo:
-                return
-            k = len(self.segments)
-            if self._COUNT0 + k >= self._ERR:
-                raise RuntimeError("FlagStep: more than 24 announced buckets")
-            flag = W(self._COUNT0 + k)
-            st = torch.cuda.current_stream().cuda_stream
-            if bf16_wire:       # the wire image, written where the bucket completes: no conversion kernel around the collective.  (As ONE
-                # launch with the announcement -- the last workgroup to finish bumps the flag -- it was slower: every workgroup's
-                # release fence is an L2 write-back on this part, 0.63 vs 0.49 ms per step; the kernel boundary does it once.)
-                _lib.check(lib.immtsf_f32_to_bf16(_lib.ptr(trainer.flat_grad[lo:hi]), _lib.ptr(trainer._wire[lo:hi]), hi - lo, st), "f32_to_bf16")
-            _lib.check(lib.immtsf_flag_bump(flag, st), "flag_bump")
-            self.segments.append({"flag": flag, "flags": [flag], "lo": lo, "hi": hi, "buckets": tuple(buckets), "branch": branch_now[0] * len(buckets)})
-
-        bursts = {}
-
-        def announce(bi, burst=None):
-            if bi in announced:
-                return
-            announced.add(bi)
-            if burst is None or not merge_adjacent:
-                announce_range(*trainer.ranges[bi], (bi,))
-                return
-            # a burst: hooks fired back to back (the buckets complete at the same moment): its members that are neighbours in the flat
-            # buffer get ONE wire image, ONE flag and ONE collective -- emitted when the burst's last member has reported
-            token, i, cnt = burst
-            bursts.setdefault(id(token), []).append(bi)
-            if i + 1 < cnt:
-                return
-            members = sorted(bursts.pop(id(token)), key=lambda b_: trainer.ranges[b_][0])
-            for lo, hi in _runs([trainer.ranges[b_] for b_ in members]):
-                announce_range(lo, hi, [b_ for b_ in members if lo <= trainer.ranges[b_][0] and trainer.ranges[b_][1] <= hi and
-                                        trainer.ranges[b_][1] > trainer.ranges[b_][0]])
-
-        def adam(buckets):
-            for lo, hi in _runs([trainer.ranges[b] for b in sorted(buckets)]):
-                trainer.adam_range(lo, hi, skip=self._f_skip, from_wire=bf16_wire)
-
+        self.flags = torch.zeros(self._WORDS, dtype=torch.int32, device=trainer.flat_param.device)
+        self._f_err, self._f_pending, self._f_skip, self._f_comm = (self._w(i) for i in (self._ERR, self._PENDING, self._SKIP, self._COMM_DONE))
+        self._from_wire = self.dist and trainer._wire is not None       # bf16 wire: Adam reads the reduced wire image
         self.graph = torch.cuda.CUDAGraph()
-        B, P = self.B, self.P
-        with step_plan.install(StepPlan(err=F_ERR)) as plan:
-            with torch.cuda.graph(self.graph):
-                T = torch.cuda.current_stream()
-                trainer._grad_zeroed_by_step = True       # (the Adam passes below leave every range zero)
-                trainer.zero_grad()
-                # ---- the previous replay's optimizer step: norm + decision, then the buckets on the branches that read them first
-                trainer.adam_prepare(pending=self._f_pending, err=F_ERR, skip_out=self._f_skip, from_wire=bf16_wire, guard=self.dist)
-                if adam_split is None:
-                    adam(range(nb))
-                    B.wait_stream(T)                  # fork (satisfied when B gets there: nothing runs on B before it)
-                    if P is not B:
-                        P.wait_stream(T)
-                else:
-                    B.wait_stream(T)
-                    with torch.cuda.stream(B):
-                        adam(adam_split[1])
-                    adam(adam_split[0])
-                    if P is not B:
-                        P.wait_stream(T)              # (behind T's own update: the two large updates do not share the HBM)
-                        with torch.cuda.stream(P):
-                            adam(adam_split[2])
-                plan.fold_stream = P                  # parameter-only work of the text side: on its own branch (or at the head of the backbone's)
-                plan.fold_flag = W(self._FOLD) if fold_by_flag else None
-                # scheduling hint (GraphedStep._fwd_bwd has the why): its time-out goes to its own word -- NOT the guard word, a hint
-                # that expires costs nothing but the overlap it was after
-                plan.gate = (W(self._SCHED), W(self._SCHED_TO)) if sched_gate else None
-                outs = text_fn()
-                plan.fold_stream = plan.fold_flag = None
-                with torch.cuda.stream(B):
-                    pred = backbone_fn()
-                    fset(F_B1, B)
-                fwait(F_B1, T)
-                plan.head_flag = F_T2 if head_flag else None
-                py, cuts, loss, dcuts = self._head(plan, pred, outs)
-                self.head_published = plan.head_dy_ptr is not None
-                dpy = py.grad
-                if not self.head_published:
-                    fset(F_T2, T)                     # (a head that publishes the flag itself -- MMFXRankQLossFn -- has taken it)
-                elif dpy is None or dpy.data_ptr() != plan.head_dy_ptr:
-                    raise RuntimeError("FlagStep: the head published its dY flag early, but autograd did not hand that buffer on as the "
-                                       "backbone's output gradient (head_flag=False disables the early flag)")
-                # parameter-gradient tails (work only the optimizer waits for) go to the parameter branch: a backbone's large linear layers'
-                # weight gradients (immtsf.ops.LinearBf16Fn: PatchTST's projections and feed-forward products) each behind a flag of its
-                # own from the spare words 9..15, the text side's behind the TAIL flag (their inputs exist)
-                if backbone_wgrad_tail and P is not B:
-                    plan.wgrad_flags = [W(i) for i in range(15, 8, -1)]
-                with torch.cuda.stream(B):
-                    fwait(F_T2, B)
-                    torch.autograd.backward([pred], [dpy])
-                    trainer.collect_grads()
-                    if self.dist and not plan.jobs_b:
-                        branch_now[0] = "B"
-                        for bi in backbone_buckets:
-                            announce(bi)
-                plan.wgrad_flags = []                 # (the text side's own products stay where they are)
-                plan.defer, plan.tail_flag = self._defer, W(self._TAIL)
-                plan.ttf_flag = W(self._TTF) if (ttf_wgrad_tail and P is not B and self._defer > 0) else None
-                plan.announce = announce if self.dist else None
-                branch_now[0] = "T"
-                self._text_backward(plan, outs, dcuts)
-                branch_now[0] = "P"
-                with torch.cuda.stream(P):
-                    for job in plan.jobs_b:               # the backbone's deferred weight gradients, each behind its own flag
-                        job(sp(P))
-                    if self.dist and plan.jobs_b:         # (the backbone's buckets are complete here, not at the end of its branch)
-                        for bi in backbone_buckets:
-                            announce(bi)
-                    if plan.jobs:
-                        if plan.tail_set:
-                            fwait(W(self._TAIL), P)
-                        for job in plan.jobs:
-                            job(sp(P))
-                with torch.cuda.stream(P):
-                    if P is not B:
-                        fset(F_P2, P)
-                with torch.cuda.stream(B):
-                    fset(F_B2, B)
-                # join: both branches as dependencies of ONE node (the flags_clear_set below).  A stream join costs 7 - 10 us on this stack
-                # even when the joined branch ended long ago (profiles/r05_flag_timeline.txt); with a flag wait in front of each -- the
-                # round-4 form: "the flag says so" -- the two joins were two barriers in a row behind the last branch: 18 us of a 440 us
-                # step.  Back to back they become one barrier with two signals: same box, three alternating pairs of 40-step timelines,
-                # median 425.6 us against 442.0.  (The two flags are still set: the timeline tool reads them.)
-                if P is not B:
-                    T.wait_stream(P)
-                T.wait_stream(B)
-                if self.dist:
-                    # what nobody announced is complete now: contiguous runs of the remaining buckets, announced behind the join
-                    branch_now[0] = "J"
-                    rest = [bi for bi in range(nb) if bi not in announced]
-                    for lo, hi in _runs([trainer.ranges[b] for b in rest]):
-                        announce_range(lo, hi, [b for b in rest if lo <= trainer.ranges[b][0] and trainer.ranges[b][1] <= hi])
-                    announced.update(rest)
-                _lib.check(lib.immtsf_flags_clear_set(fp, 16, self._f_pending, sp(T)), "flags_clear_set")
-        self._order_segments()
-        self.comm = None
-        if self.dist:
-            # A stream of its own at DEFAULT priority.  HIP deals the streams of one priority round-robin onto a handful of hardware
-            # queues, so this stream may share one with a branch of the graph and then run its spins behind that branch instead of
-            # beside it (seen once: every bucket's wait entered 3 us after the step's last kernel, the collectives exposed in front of
-            # the next step) -- slower, never wrong: the graph does not wait for this stream.  A HIGH-priority stream gets queues of
-            # its own, but a spin kernel on a high-priority queue slowed the graph's text branch THREEFOLD (1.36 vs 0.51 ms per step:
-            # profiles/r05_dist_ab.txt), so that is not the default.
-            self.comm = torch.cuda.Stream(device=dev, priority=int(os.environ.get("IMMTSF_COMM_PRIO", "0")))
+        self._capture(adam_split, fold_by_flag, head_flag, sched_gate, backbone_buckets, ttf_wgrad_tail, merge_adjacent, backbone_wgrad_tail)
+        # The collectives' stream (data parallel), at DEFAULT priority.  HIP deals the streams of one priority round-robin onto a handful of
+        # hardware queues, so this stream may share one with a branch of the graph and then run its spins behind that branch instead of
+        # beside it (seen once: every bucket's wait entered 3 us after the step's last kernel, the collectives exposed in front of
+        # the next step) -- slower, never wrong: the graph does not wait for this stream.  A HIGH-priority stream gets queues of
+        # its own, but a spin kernel on a high-priority queue slowed the graph's text branch THREEFOLD (1.36 vs 0.51 ms per step:
+        # profiles/r05_dist_ab.txt), so that is not the default.
+        prio = int(os.environ.get("IMMTSF_COMM_PRIO", "0"))
+        self.comm = torch.cuda.Stream(device=trainer.flat_param.device, priority=prio) if self.dist else None
         self._epoch = 0
-        self.loss = loss
-        self._keep = (outs, pred, py, cuts, dpy, dcuts)
         trainer._flush_cb = self.flush
+
+    def _w(self, i):        # device address of flag word i
+        return self.flags.data_ptr() + 4 * i
+
+    # ---- the captured step program: one method per segment of the class docstring's timeline; `c` carries what the phases share
+    def _capture(self, adam_split, fold_by_flag, head_flag, sched_gate, backbone_buckets, ttf_wgrad_tail, merge_adjacent, backbone_wgrad_tail):
+        W, P, B = self._w, self.P, self.B
+        ann = Announcer(self.trainer.ranges, self._emit, merge_adjacent, capacity=self._COUNTS)
+        # scheduling hint (GraphedStep._fwd_bwd has the why): its time-out goes to its own word -- NOT the guard word, a hint
+        # that expires costs nothing but the overlap it was after
+        gate = (W(self._SCHED), W(self._SCHED_TO)) if sched_gate else None
+        ttf_flag = W(self._TTF) if (ttf_wgrad_tail and P is not B and self._defer > 0) else None
+        with step_plan.install(StepPlan(err=self._f_err, timeout_ms=self.timeout_ms)) as plan, torch.cuda.graph(self.graph), plan.offering(gate=gate):
+            c = SimpleNamespace(plan=plan, ann=ann, T=torch.cuda.current_stream())
+            self._cap_optimizer_head(c, adam_split)       # (trainer launches only: no op looks at the plan)
+            self._cap_forward(c, fold_by_flag)
+            self._cap_head(c, head_flag)
+            self._cap_backbone_backward(c, backbone_buckets, backbone_wgrad_tail)
+            # the text side's parameter tail leaves behind the TAIL flag (its inputs exist); the bucket hooks announce through the plan
+            with plan.offering(defer=self._defer, tail_flag=W(self._TAIL), ttf_flag=ttf_flag, announce=ann.announce if self.dist else None):
+                ann.branch = "T"
+                self._text_backward(plan, c.outs, c.dcuts)
+                self._cap_param_branch(c, backbone_buckets)
+                self._cap_join(c)
+        self.segments = static_order(ann.segments)        # [dict(flag, flags, lo, hi, buckets, branch)]; single process: none
+        self.loss, self._keep = c.loss, (c.outs, c.pred, c.py, c.cuts, c.dpy, c.dcuts)
+
+    def _emit(self, k, lo, hi):
+        """Announcer's emit: flat_grad[lo:hi] is final on the current stream -> the k-th counting flag, bumped behind it"""
+        t, lib, st = self.trainer, _lib.load(), torch.cuda.current_stream().cuda_stream
+        if self._from_wire:     # the wire image, written where the bucket completes: no conversion kernel around the collective.  (As ONE
+            # launch with the announcement -- the last workgroup to finish bumps the flag -- it was slower: every workgroup's
+            # release fence is an L2 write-back on this part, 0.63 vs 0.49 ms per step; the kernel boundary does it once.)
+            _lib.check(lib.immtsf_f32_to_bf16(_lib.ptr(t.flat_grad[lo:hi]), _lib.ptr(t._wire[lo:hi]), hi - lo, st), "f32_to_bf16")
+        _lib.check(lib.immtsf_flag_bump(self._w(self._COUNT0 + k), st), "flag_bump")
+        return self._w(self._COUNT0 + k)
+
+    def _adam(self, buckets):
+        for lo, hi in runs([self.trainer.ranges[b] for b in sorted(buckets)]):
+            self.trainer.adam_range(lo, hi, skip=self._f_skip, from_wire=self._from_wire)
+
+    def _cap_optimizer_head(self, c, adam_split):
+        """the previous replay's optimizer step: norm + decision on T, then the buckets on the branches that read them first"""
+        t, T, B, P = self.trainer, c.T, self.B, self.P
+        t._grad_zeroed_by_step = True       # (the Adam passes below leave every range zero)
+        t.zero_grad()
+        t.adam_prepare(pending=self._f_pending, err=self._f_err, skip_out=self._f_skip, from_wire=self._from_wire, guard=self.dist)
+        if adam_split is None:
+            self._adam(range(len(t.buckets)))
+            B.wait_stream(T)                  # fork (satisfied when B gets there: nothing runs on B before it)
+            if P is not B:
+                P.wait_stream(T)
+            return
+        B.wait_stream(T)
+        with torch.cuda.stream(B):
+            self._adam(adam_split[1])
+        self._adam(adam_split[0])
+        if P is not B:
+            P.wait_stream(T)                  # (behind T's own update: the two large updates do not share the HBM)
+            with torch.cuda.stream(P):
+                self._adam(adam_split[2])
+
+    def _cap_forward(self, c, fold_by_flag):
+        """T: text forward, its parameter-only work on P (a branch of its own, or the head of the backbone's); B: backbone forward, set(B1)"""
+        with c.plan.offering(fold_stream=self.P, fold_flag=self._w(self._FOLD) if fold_by_flag else None):
+            c.outs = self.text_fn()
+        with torch.cuda.stream(self.B):
+            c.pred = self.backbone_fn()
+            c.plan.set(self._w(self._B1), self.B.cuda_stream)
+
+    def _cap_head(self, c, head_flag):
+        """T: wait(B1), head forward + backward, set(T2)"""
+        plan, F_T2 = c.plan, self._w(self._T2)
+        plan.wait(self._w(self._B1), c.T.cuda_stream)
+        with plan.offering(head_flag=F_T2 if head_flag else None):
+            c.py, c.cuts, c.loss, c.dcuts = self._head(plan, c.pred, c.outs)
+        self.head_published = plan.head_dy_ptr is not None
+        c.dpy = c.py.grad
+        if not self.head_published:
+            plan.set(F_T2, c.T.cuda_stream)       # (a head that publishes the flag itself -- MMFXRankQLossFn -- has taken it)
+        elif c.dpy is None or c.dpy.data_ptr() != plan.head_dy_ptr:
+            raise RuntimeError("FlagStep: the head published its dY flag early, but autograd did not hand that buffer on as the "
+                               "backbone's output gradient (head_flag=False disables the early flag)")
+
+    def _cap_backbone_backward(self, c, backbone_buckets, backbone_wgrad_tail):
+        """B: wait(T2), backbone backward, gradient collection.  Parameter-gradient tails (work only the optimizer waits for) go to the
+        parameter branch: a backbone's large linear layers' weight gradients (immtsf.ops.LinearBf16Fn: PatchTST's projections and
+        feed-forward products) each behind a flag of its own from the spare words (the text side's own products stay where they are)"""
+        plan, B = c.plan, self.B
+        spare = [self._w(i) for i in self._SPARE] if (backbone_wgrad_tail and self.P is not B) else []
+        with plan.offering(wgrad_flags=spare), torch.cuda.stream(B):
+            plan.wait(self._w(self._T2), B.cuda_stream)
+            torch.autograd.backward([c.pred], [c.dpy])
+            self.trainer.collect_grads()
+            if self.dist and not plan.jobs_b:
+                c.ann.branch = "B"
+                for bi in backbone_buckets:
+                    c.ann.announce(bi)
+
+    def _cap_param_branch(self, c, backbone_buckets):
+        """P: the deferred parameter-gradient chains, set(P2)"""
+        plan, P = c.plan, self.P
+        c.ann.branch = "P"
+        with torch.cuda.stream(P):
+            for job in plan.jobs_b:               # the backbone's deferred weight gradients, each behind its own flag
+                job(P.cuda_stream)
+            if self.dist and plan.jobs_b:         # (the backbone's buckets are complete here, not at the end of its branch)
+                for bi in backbone_buckets:
+                    c.ann.announce(bi)
+            if plan.jobs:
+                if plan.tail_set:
+                    plan.wait(self._w(self._TAIL), P.cuda_stream)
+                for job in plan.jobs:
+                    job(P.cuda_stream)
+            if P is not self.B:
+                plan.set(self._w(self._P2), P.cuda_stream)
+
+    def _cap_join(self, c):
+        """set(B2); T: join(P, B), what nobody announced, clear"""
+        T, B, P = c.T, self.B, self.P
+        c.plan.set(self._w(self._B2), B.cuda_stream)
+        # join: both branches as dependencies of ONE node (the flags_clear_set below).  A stream join costs 7 - 10 us on this stack
+        # even when the joined branch ended long ago (profiles/r05_flag_timeline.txt); with a flag wait in front of each -- the
+        # round-4 form: "the flag says so" -- the two joins were two barriers in a row behind the last branch: 18 us of a 440 us
+        # step.  Back to back they become one barrier with two signals: same box, three alternating pairs of 40-step timelines,
+        # median 425.6 us against 442.0.  (The two flags are still set: the timeline tool reads them.)
+        if P is not B:
+            T.wait_stream(P)
+        T.wait_stream(B)
+        if self.dist:
+            c.ann.finish()                        # what nobody announced is complete now: announced behind the join
+        _lib.check(_lib.load().immtsf_flags_clear_set(self._w(0), self._CLEARED, self._f_pending, T.cuda_stream), "flags_clear_set")
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def timed_out(self) -> bool:
@@ -1093,18 +1028,11 @@ class FlagStep(PhasedStep):
         self.flags[self._PENDING:self._PENDING + 1].zero_()
         self.trainer.flat_grad.zero_()
 
-    def _order_segments(self):
-        """the communication order before any measurement: the text side's buckets but its last, the parameter branch's, the text side's
-        last, the backbone's, the join's; the SAME on every rank (calibrate_comm_order replaces it by the measured completion order)"""
-        tseg = [g for g in self.segments if g["branch"][0] == "T"]
-        self.segments = (tseg[:-1] + [g for g in self.segments if g["branch"][0] == "P"] + tseg[-1:] +
-                         [g for g in self.segments if g["branch"][0] == "B"] + [g for g in self.segments if g["branch"][0] == "J"])
-
     def calibrate_comm_order(self, replays: int = 3, merge_tail_us: float = 60.0):
         """order the communication stream's collectives by when their buckets ACTUALLY complete: `replays` replays under the flag
         kernels' own trace (immtsf_flag_trace: device wall clock, nothing serialised), the completion time of every segment (its last
         flag, relative to the previous step's clear) averaged over the replays and -- so that every rank ends up with the SAME order --
-        over the ranks.  The static order of _order_segments is a guess from the program's structure; a collective that waits for a
+        over the ranks.  The static order (announce.static_order) is a guess from the program's structure; a collective that waits for a
         late bucket while earlier-finished ones queue behind it leaves them all exposed at the end of the step (measured: three
         collectives behind the last flag, 37 us in front of the next step; ordered by completion: one).  The replays are real training
         steps: callers undo them (bench.flag_step restores its snapshot).  A collective call when the trainer has a process group."""
@@ -1127,27 +1055,13 @@ class FlagStep(PhasedStep):
                 t_clear = t
             elif kind == 0 and t_clear is not None:
                 acc.setdefault(off, []).append((t - t_clear) / 100.0)
-        times = []
-        for g in self.segments:
-            ts = acc.get(g["flag"] - base)
-            times.append(sum(ts) / len(ts) if ts else float("inf"))
-        tt = torch.tensor(times, dtype=torch.float64, device=self.flags.device)
-        tt = torch.where(torch.isfinite(tt), tt, torch.full_like(tt, 1e9))
+        seen = [acc.get(g["flag"] - base) for g in self.segments]
+        tt = torch.tensor([sum(ts) / len(ts) if ts else 1e9 for ts in seen], dtype=torch.float64, device=self.flags.device)
         import torch.distributed as dist
         dist.all_reduce(tt, group=self.trainer.group)
         order = sorted(range(len(self.segments)), key=lambda i: (float(tt[i]), i))
         segs = [dict(self.segments[i], done_us=float(tt[i]) / self.trainer.world) for i in order]
-        # the buckets that complete within `merge_tail_us` of the LAST one, when they are one contiguous range of the flat buffer, go out
-        # as ONE collective behind one wait on all their flags: every collective in the exposed tail costs its full latency (three
-        # collectives behind the last flag: +37 us at one rank, ~3 x the RCCL latency at eight); an earlier bucket keeps its own
-        tail = [g for g in segs if segs[-1]["done_us"] - g["done_us"] <= merge_tail_us]
-        if len(tail) > 1:
-            lo, hi = min(g["lo"] for g in tail), max(g["hi"] for g in tail)
-            if sum(g["hi"] - g["lo"] for g in tail) == hi - lo:
-                merged = {"flag": tail[-1]["flag"], "flags": [f for g in tail for f in g["flags"]], "lo": lo, "hi": hi,
-                          "buckets": tuple(b for g in sorted(tail, key=lambda g_: g_["lo"]) for b in g["buckets"]),
-                          "branch": "".join(g["branch"] for g in sorted(tail, key=lambda g_: g_["lo"])), "done_us": tail[-1]["done_us"]}
-                segs = segs[:len(segs) - len(tail)] + [merged]
+        segs = merge_tail(segs, merge_tail_us)
         self.segments = segs
         self.completion_us = [round(g["done_us"], 1) for g in segs]
 
@@ -1208,13 +1122,3 @@ class FlagStep(PhasedStep):
             self.check()
         return self.loss
 
-
-def _runs(ranges):
-    """contiguous runs of (lo, hi) ranges (sorted by lo; empty ones dropped)"""
-    out = []
-    for lo, hi in sorted(r for r in ranges if r[1] > r[0]):
-        if out and out[-1][1] == lo:
-            out[-1] = (out[-1][0], hi)
-        else:
-            out.append((lo, hi))
-    return out

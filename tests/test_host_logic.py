@@ -148,3 +148,125 @@ def test_step_plan_lives_for_one_step_only():
     assert idle.take_head_flag(dY) is None and idle.arm_gate() is None and not idle.hold_params
     assert not idle.wgrad_open and idle.ttf_flag is None and idle.defer == 0 and idle.announce is None
     assert idle.fold(lambda stream: ran.append("fold")) is False and ran == []
+
+
+_RANGES = [(0, 4), (4, 8), (8, 8), (8, 12), (20, 24)]       # bucket 2 is empty; bucket 4 is no neighbour of the others
+
+
+def _announcer(**kw):
+    from immtsf.announce import Announcer
+    emitted = []
+
+    def emit(k, lo, hi):
+        emitted.append((k, lo, hi))
+        return 1000 + 4 * k
+    return Announcer(_RANGES, emit, **kw), emitted
+
+
+def _spans(a):
+    return [(g["lo"], g["hi"]) for g in a.segments]
+
+
+def test_announcer_single_buckets_and_bursts():
+    """immtsf.announce.Announcer: which buckets of a data-parallel FlagStep share a flag.  Host logic only (a fake emit)."""
+    from immtsf import announce
+    assert not hasattr(announce, "torch") and not hasattr(announce, "_lib")
+    a, emitted = _announcer()
+    a.announce(1)
+    assert a.segments == [{"flag": 1000, "flags": [1000], "lo": 4, "hi": 8, "buckets": (1,), "branch": "T"}]
+    a.announce(1)                                                # a second announcement adds nothing
+    assert len(a.segments) == 1 and emitted == [(0, 4, 8)]
+
+    for merge, want in ((True, [(0, 12)]), (False, [(0, 4), (4, 8), (8, 12)])):
+        a, emitted = _announcer(merge_adjacent=merge)
+        token = object()
+        for i, bi in enumerate((0, 1)):
+            a.announce(bi, (token, i, 3))
+            assert merge == (emitted == [])                      # a burst emits nothing before its last member
+        a.announce(3, (token, 2, 3))
+        assert _spans(a) == want and [k for k, _, _ in emitted] == list(range(len(want)))
+        if merge:
+            assert a.segments[0]["buckets"] == (0, 1, 3) and a.segments[0]["branch"] == "TTT" and a.segments[0]["flags"] == [1000]
+        else:
+            assert [g["buckets"] for g in a.segments] == [(0,), (1,), (3,)]
+
+    a, _ = _announcer()
+    token = object()
+    a.announce(0, (token, 0, 2))
+    a.announce(4, (token, 1, 2))
+    assert _spans(a) == [(0, 4), (20, 24)] and [g["flag"] for g in a.segments] == [1000, 1004]
+
+
+def test_announcer_finish_leaves_no_bucket_behind():
+    a, _ = _announcer()
+    a.finish()                                                   # nothing announced: everything behind the join, as contiguous runs
+    assert _spans(a) == [(0, 12), (20, 24)] and [g["branch"] for g in a.segments] == ["JJJ", "J"]
+    assert [g["buckets"] for g in a.segments] == [(0, 1, 3), (4,)]            # (the empty bucket is in no segment)
+
+    # a burst whose LAST member was announced before it: the burst never closes by itself -- finish() emits its other members
+    a, _ = _announcer()
+    a.branch = "B"
+    a.announce(3)
+    a.branch = "T"
+    token = object()
+    for i, bi in enumerate((0, 1, 3)):
+        a.announce(bi, (token, i, 3))
+    assert _spans(a) == [(8, 12)]
+    a.finish()
+    assert _spans(a) == [(8, 12), (0, 8), (20, 24)]
+    held = sorted(b for g in a.segments for b in g["buckets"])
+    assert held == [0, 1, 3, 4]                                  # every non-empty bucket in exactly one segment
+    covered = sorted(_spans(a))
+    assert all(x[1] <= y[0] for x, y in zip(covered, covered[1:]))            # disjoint ranges
+    assert all(len(g["branch"]) == len(g["buckets"]) for g in a.segments)
+
+
+def test_announcer_capacity_and_orders():
+    from immtsf.announce import Announcer, merge_tail, static_order
+    a = Announcer([(8 * i, 8 * i + 4) for i in range(30)], lambda k, lo, hi: 1000 + 4 * k)      # no two are neighbours
+    for bi in range(24):
+        a.announce(bi)
+    assert len(a.segments) == 24
+    with pytest.raises(RuntimeError):
+        a.announce(24)                                           # the 25th segment
+    a = Announcer([(0, 4), (8, 12)], lambda k, lo, hi: k, capacity=1)
+    with pytest.raises(RuntimeError):
+        a.finish()
+
+    segs = [{"branch": b, "n": i} for i, b in enumerate(["J", "T", "B", "TT", "P", "T", "PP"])]
+    assert [g["n"] for g in static_order(segs)] == [1, 3, 4, 6, 5, 2, 0]    # T's but the last, P's, T's last, B's, J's
+    assert static_order([]) == []
+
+    def seg(k, lo, hi, buckets, branch, done):
+        return {"flag": 1000 + 4 * k, "flags": [1000 + 4 * k], "lo": lo, "hi": hi, "buckets": buckets, "branch": branch, "done_us": done}
+    early, b, c, d = seg(0, 0, 4, (0,), "T", 100.0), seg(1, 12, 20, (3, 4), "PP", 390.0), seg(2, 4, 12, (1, 2), "TT", 400.0), seg(3, 20, 24, (5,), "J", 430.0)
+    out = merge_tail([early, b, c, d], 60.0)
+    assert out[0] is early and len(out) == 2                     # an earlier bucket keeps its own segment
+    assert out[1] == {"flag": 1012, "flags": [1004, 1008, 1012], "lo": 4, "hi": 24, "buckets": (1, 2, 3, 4, 5), "branch": "TTPPJ", "done_us": 430.0}
+    gap = [seg(0, 0, 4, (0,), "T", 400.0), seg(1, 8, 12, (2,), "T", 430.0)]
+    assert merge_tail(gap, 60.0) == gap                          # a tail that is not one contiguous range is left alone
+    assert merge_tail([early, d], 60.0) == [early, d]            # nothing finished near the last one
+
+
+def test_step_plan_offering_is_scoped():
+    from immtsf.step_plan import StepPlan
+    plan = StepPlan()
+    assert plan.timeout_ms == 50 and StepPlan(timeout_ms=20).timeout_ms == 20
+    with plan.offering(defer=3, tail_flag=0x40):
+        assert (plan.defer, plan.tail_flag, plan.hold_params) == (3, 0x40, False)
+        with plan.offering(hold_params=True, defer=1):           # it nests
+            assert (plan.defer, plan.tail_flag, plan.hold_params) == (1, 0x40, True)
+        assert (plan.defer, plan.tail_flag, plan.hold_params) == (3, 0x40, False)
+    assert (plan.defer, plan.tail_flag) == (0, None)
+    with pytest.raises(ValueError):
+        with plan.offering(wgrad_flags=[1, 2], gate=(8, 12)):
+            assert plan.wgrad_open
+            raise ValueError("a backward raised")
+    assert plan.wgrad_flags == [] and plan.gate is None          # restored after an exception too
+    with pytest.raises(AttributeError):
+        with plan.offering(jobs=[1]):                            # held work is no offer
+            pass
+    with pytest.raises(AttributeError):
+        with plan.offering(defer=2, no_such_offer=1):
+            pass
+    assert plan.defer == 0 and plan.jobs == []
