@@ -164,6 +164,13 @@ _PROTOS = {
     "immtsf_dlinear_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
     "immtsf_dlinear_forward": (C.c_int, [C.c_int32] * 8 + [c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, c_stream]),
     "immtsf_dlinear_backward": (C.c_int, [C.c_int32] * 8 + [c_f32p] * 12 + [C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_timemixer_supported": (C.c_int, [C.c_int32] * 8),
+    "immtsf_timemixer_grad_layout": (C.c_int32, [C.c_int32] * 7 + [c_i32p, C.c_int32]),
+    "immtsf_timemixer_workspace_bytes": (C.c_size_t, [C.c_int32] * 8),
+    "immtsf_timemixer_forward": (C.c_int, [C.c_int32] * 11 + [c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_float, C.c_uint64, C.c_uint64,
+                                           C.c_void_p, c_stream]),
+    "immtsf_timemixer_backward": (C.c_int, [C.c_int32] * 11 + [c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_float, C.c_uint64,
+                                            C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_eval_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "immtsf_eval_metrics_accum": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                             c_stream]),

@@ -121,3 +121,7 @@ eval_engine = os.environ.get("IMMTSF_EVAL_ENGINE", "0") == "1"
 # DLinear.forecasting() as one HIP launch per direction (csrc/dlinear.hip) wherever immtsf_dlinear_supported allows; IMMTSF_DLINEAR_FUSED=0:
 # the composed path (torch element-wise ops around three immtsf.ops.linear calls) -- the cross-check.  fp32 in either precision mode
 dlinear_fused = os.environ.get("IMMTSF_DLINEAR_FUSED", "1") != "0"
+# TimeMixer.forecasting() as one HIP launch forward and two backward (csrc/timemixer.hip) wherever the options are the reference's defaults
+# and immtsf_timemixer_supported allows; IMMTSF_TIMEMIXER_FUSED=0: the composed path (one embedding kernel per scale, torch element-wise
+# ops around immtsf.ops.linear calls) -- the cross-check.  fp32 in either precision mode
+timemixer_fused = os.environ.get("IMMTSF_TIMEMIXER_FUSED", "1") != "0"

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import config, ops
+from . import config, ops, step_plan
 
 KEYS = ("loss", "mse", "mae", "rmse", "mape")
 _TS = ("tp_to_predict", "observed_data", "observed_tp", "observed_mask", "data_to_predict", "mask_predicted_data")
@@ -59,6 +59,7 @@ class _EvalGraph:
         torch.cuda.synchronize()
         pool = _pool_acquire(self, dev)
         self.graph = torch.cuda.CUDAGraph()
+        step_plan.collect_before_capture()
         with torch.cuda.graph(self.graph, pool=pool):
             step._enqueue(self.static, step.acc)
 
@@ -119,7 +120,7 @@ class EvalStep:
         mods = [m for m in (self.model, self.fusion) if m is not None]
         sig = tuple(p.data_ptr() for m in mods for p in m.parameters())
         return (config.precision, config.t2v_form, config.fuse_tail, config.xattn_rank, config.attn_mid, config.note_index, config.gr_split,
-                config.dlinear_fused, sig, tuple((k, tuple(b[k].shape), b[k].dtype) for k in names))
+                config.dlinear_fused, config.timemixer_fused, sig, tuple((k, tuple(b[k].shape), b[k].dtype) for k in names))
 
     def __call__(self, batch):
         model, fusion = self.model, self.fusion

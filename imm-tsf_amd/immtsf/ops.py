@@ -2606,3 +2606,124 @@ def dlinear_forecast(data, mask, tp, Lp, S, P, k, seasonal, trend, time):
         raise _lib.ImmtsfError(f"dlinear_forecast: shapes outside the fused kernel (B {B}, L {L}, C {Cc}, S {S}, P {P}, Lp {Lp}, k {k})")
     return DLinearFn.apply(data, mask, tp, (int(S), int(P), int(Lp), int(k), 1 if individual else 0), _dlinear_table(params, data.device),
                            *params)
+
+
+# ------------------------------------------------------------------------------------------------ TimeMixer backbone
+SITE_TIMEMIXER_EMBED = SITE_LAYER_BASE + 42      # the embedding's dropout inside csrc/timemixer.hip: element ((off_i B + b T_i + t) d + f)
+_tm_tables = {}      # never emptied: a captured graph keeps reading the table it was captured with
+_tm_layouts = {}
+
+
+def timemixer_supported(S, P, Cc, d_model, d_ff, e_layers, down_layers, moving_avg):
+    """the limits of the fused TimeMixer path (immtsf_timemixer_supported): 2 <= S <= 64, P <= 64, d_model <= 32, d_ff <= 64,
+    e_layers <= 4, down_layers <= 6, 2C+1 <= 64, odd moving_avg"""
+    return bool(_lib.load().immtsf_timemixer_supported(int(S), int(P), int(Cc), int(d_model), int(d_ff), int(e_layers), int(down_layers),
+                                                       int(moving_avg)))
+
+
+def timemixer_params(model):
+    """the module's tensors in the order of immtsf_timemixer_forward's pointer table (the last block's trend mixers included: the
+    kernels never read them and they get no gradient)"""
+    n = model.down_layers
+    ps = [model.enc_embedding.value_embedding.tokenConv.weight, model.enc_embedding.position_embedding.pe]
+    for blk in model.pdm_blocks:
+        seqs = list(blk.mix_season.down_sampling_layers) + [blk.mix_trend.up_sampling_layers[n - 1 - i] for i in range(n)] + [blk.out_layer]
+        for seq in seqs:
+            ps += [seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias]
+    head = model.predict_layers[n]
+    return ps + [head.weight, head.bias, model.projection.weight, model.projection.bias]
+
+
+def _timemixer_layout(dims):
+    """-> (float offset of every table entry in the flat gradient, -1 = none; the flat gradient's length)"""
+    got = _tm_layouts.get(dims)
+    if got is None:
+        S, P, Cc, d, dff, E, n, _ = dims
+        offs = torch.full((2 + E * (8 * n + 4) + 4,), -1, dtype=torch.int32)
+        nv = int(_lib.load().immtsf_timemixer_grad_layout(S, P, Cc, d, dff, E, n, offs.data_ptr(), offs.numel()))
+        if nv < 0:
+            raise _lib.ImmtsfError(f"timemixer: dimensions outside the fused kernel {dims}")
+        got = _tm_layouts[dims] = (offs.tolist(), nv)
+    return got
+
+
+class TimeMixerFn(torch.autograd.Function):
+    """TimeMixer.forecasting() as ONE launch; backward = the parameter gradients in TWO (immtsf_timemixer_forward / _backward,
+    csrc/timemixer.hip), written into one flat buffer whose slices are handed to autograd (a parameter's FlatTrainer sink receives its
+    slice through AccumulateGrad, as with DLinearFn).  data / mask (B, L, C) and tp (B, L) are data: no gradient.  dims = (S, P, C, d,
+    d_ff, e_layers, n, k); drop = (p, seed, site, device counter).  params in the table's order.  fp32 in either precision mode."""
+
+    @staticmethod
+    def forward(ctx, data, mask, tp, Lp, dims, drop, table, *params):
+        lib = _lib.load()
+        S, P, Cc, d, dff, E, n, k = dims
+        data, mask, tp = _c(data), _c(mask), _c(tp)
+        _need_gpu(data, mask, tp, *params)
+        B, L, _ = data.shape
+        p, seed, site, cnt = drop
+        y = torch.empty(B, Lp, Cc, dtype=torch.float32, device=data.device)
+        check(lib.immtsf_timemixer_forward(B, L, Cc, S, P, Lp, d, dff, E, n, k, ptr(data), ptr(mask), ptr(tp), ptr(table), ptr(y), p, seed,
+                                           site, cnt, stream_ptr()), "timemixer_forward")
+        ctx.cfg = (B, L, Lp, dims, drop)
+        ctx.table = table
+        ctx.shapes = [tuple(q.shape) for q in params]
+        # the backward recomputes the forward from the parameters: saved (no copy), so that autograd's version check covers them
+        ctx.save_for_backward(data, mask, tp, *params)
+        return y
+
+    @staticmethod
+    def backward(ctx, dY):
+        lib = _lib.load()
+        data, mask, tp = ctx.saved_tensors[:3]
+        B, L, Lp, dims, (p, seed, site, cnt) = ctx.cfg
+        S, P, Cc, d, dff, E, n, k = dims
+        offs, nv = _timemixer_layout(dims)
+        flat = torch.empty(nv, dtype=torch.float32, device=dY.device)      # every entry is written: no zero fill
+        ws = _bytes(lib.immtsf_timemixer_workspace_bytes(B, S, P, Cc, d, dff, E, n), dY.device)
+        check(lib.immtsf_timemixer_backward(B, L, Cc, S, P, Lp, d, dff, E, n, k, ptr(data), ptr(mask), ptr(tp), ptr(ctx.table),
+                                            ptr(dY.contiguous()), ptr(flat), p, seed, site, cnt, ptr(ws), ws.numel(), stream_ptr()),
+              "timemixer_backward")
+        rets = []
+        for o, shape, need in zip(offs, ctx.shapes, ctx.needs_input_grad[7:]):
+            numel = 1
+            for s in shape:
+                numel *= s
+            rets.append(flat[o:o + numel].view(shape) if need and o >= 0 else None)
+        return (None,) * 7 + tuple(rets)
+
+
+def timemixer_forecast(model, data, mask, tp, Lp):
+    """data, mask (B, L <= input_len, C), tp (B, L) -> the de-normalised forecast (B, Lp <= pred_len, C) of a models.TimeMixer.TimeMixer
+    at the reference's default options.  In training mode with dropout > 0 the embedding's dropout is drawn inside the kernel: one
+    config.next_seed() per call, site SITE_TIMEMIXER_EMBED, the device counter of config.enable_device_counters honoured."""
+    c = model.configs
+    n = model.down_layers
+    dims = (int(model.input_len), int(model.pred_len), int(model.C), int(c.d_model), int(c.d_ff), int(model.layers), int(n),
+            int(c.moving_avg))
+    S, P, Cc, d, dff, E, _, k = dims
+    B, L, _ = data.shape
+    params = timemixer_params(model)
+    if not timemixer_supported(*dims) or not (0 <= L <= S and 0 <= Lp <= P) or B < 1 or tuple(data.shape) != (B, L, Cc) or \
+            tuple(mask.shape) != (B, L, Cc) or tuple(tp.shape) != (B, L):
+        raise _lib.ImmtsfError(f"timemixer_forecast: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, dims {dims})")
+    T = [S >> i for i in range(n + 1)]
+    want = [(d, 2 * Cc + 1, 3), None]
+    for j in range(E):
+        for i in range(n):
+            want += [(T[i + 1], T[i]), (T[i + 1],), (T[i + 1], T[i + 1]), (T[i + 1],)]
+        for i in range(n):
+            want += [(T[i], T[i + 1]), (T[i],), (T[i], T[i]), (T[i],)]
+        want += [(dff, d), (dff,), (d, dff), (d,)]
+    want += [(P, T[n]), (P,), (Cc, d), (Cc,)]
+    pe = params[1]
+    if any(not q.is_contiguous() or q.dtype != torch.float32 for q in params) or pe.dim() != 3 or pe.shape[1] < S or pe.shape[2] != d or \
+            any(w is not None and tuple(q.shape) != w for q, w in zip(params, want)):
+        raise _lib.ImmtsfError("timemixer_forecast: the module's parameters are not the contiguous fp32 tensors of these dimensions")
+    key = (data.device.type, data.device.index) + tuple(q.data_ptr() for q in params)
+    table = _tm_tables.get(key)
+    if table is None:      # one host -> device copy per distinct set of storages: outside a stream capture, as every warm-up run is
+        table = _tm_tables[key] = torch.tensor(key[2:], dtype=torch.int64, device=data.device)
+    p = float(model.enc_embedding.dropout.p) if model.training else 0.0
+    drop = (p, config.next_seed() if p > 0 else 0, SITE_TIMEMIXER_EMBED, config.dropout_counter_ptr(data.device) if p > 0 else None)
+    model._last_drop = drop      # (p, seed, site, counter pointer) of this module's latest fused call: what dropout_keep_mask reproduces
+    return TimeMixerFn.apply(data, mask, tp, int(Lp), dims, drop, table, *params)

@@ -4,10 +4,20 @@ An engine installs one StepPlan per step it runs or captures and switches what t
 `current()` through the named operations below and never sees the flag words.  Outside an engine `current()` offers nothing.  One
 process-wide slot, not a thread-local: the backward of a GPU graph runs on autograd's device worker thread."""
 import contextlib
+import gc
 
 import torch
 
 from . import _lib
+
+
+def collect_before_capture():
+    """Called in front of every capture of the project's own (the step engines, the seam graph, EvalStep).  On ROCm the destructor of a
+    torch.cuda.CUDAGraph synchronises the device, which is illegal while a stream captures: a dead engine that still sits in a reference
+    cycle (FlagStep <-> FlatTrainer._flush_cb) and is collected INSIDE the next engine's capture throws from that destructor and the
+    process aborts -- whenever the collector's counters happen to trip there.  torch.cuda.graph() collected on entry by itself up to
+    torch 2.8; this is that collection, for these captures only."""
+    gc.collect()
 
 
 class StepPlan:

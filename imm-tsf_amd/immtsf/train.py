@@ -578,6 +578,7 @@ class GraphedStep:
             _warm_up(trainer, eager_step, warmup, restore_after_warmup)
         torch.cuda.current_stream().wait_stream(side)
         self.graph_a, self.graph_b = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        step_plan.collect_before_capture()
         with torch.cuda.graph(self.graph_a):
             self.loss = self._fwd_bwd()
             if self.captured_comm:
@@ -708,6 +709,7 @@ class PhasedStep(_SplitStep):
         self.gT1, self.gB1, self.gT2, self.gB2, self.gT3, self.gO = G(), G(), G(), G(), G(), G()
         # one memory pool per stream: graphs that replay concurrently must never be handed each other's freed blocks
         poolT, poolB = torch.cuda.graph_pool_handle(), torch.cuda.graph_pool_handle()
+        step_plan.collect_before_capture()
         with torch.cuda.graph(self.gT1, pool=poolT, stream=self.T):
             trainer.zero_grad()
             outs = text_fn()
@@ -880,6 +882,7 @@ class FlagStep(_SplitStep):
         # that expires costs nothing but the overlap it was after
         gate = (W(self._SCHED), W(self._SCHED_TO)) if sched_gate else None
         ttf_flag = W(self._TTF) if (ttf_wgrad_tail and P is not B and self._defer > 0) else None
+        step_plan.collect_before_capture()
         with step_plan.install(StepPlan(err=self._f_err, timeout_ms=self.timeout_ms)) as plan, torch.cuda.graph(self.graph), plan.offering(gate=gate):
             c = SimpleNamespace(plan=plan, ann=ann, T=torch.cuda.current_stream())
             self._cap_optimizer_head(c, adam_split)       # (trainer launches only: no op looks at the plan)

@@ -606,6 +606,40 @@ int immtsf_dlinear_backward(int32_t B, int32_t L, int32_t C, int32_t S, int32_t 
                             float* dWs, float* dWt, float* dWtau, float* dbs, float* dbt, float* dbtau, void* workspace,
                             size_t workspace_bytes, immtsf_stream_t stream);
 
+/* ---- TimeMixer backbone (added within ABI 7: new functions only; csrc/timemixer.hip): forecasting() of reference models/TimeMixer.py:268-326 at its default options
+ * (moving-average decomposition with an odd window, channel independence, average pooling, window 2) as ONE launch, and its parameter
+ * gradients as TWO (no input takes a gradient).  All fp32.  S = input_len, P = pred_len, down_layers = n = the constructor's clipped
+ * down_sampling_layers (scale lengths T_i = S >> i, i = 0..n); data / mask (B, L, C) and tp (B, L) are the UNPADDED history, L <= S; y
+ * (B, Lp, C), Lp <= P, is written directly.
+ * params: a DEVICE array of 2 + e_layers (8 n + 4) + 4 pointers: [tokenConv.weight (d, 2C+1, 3), pe (>= S rows of d)], then per block j
+ * [season i = 0..n-1: W1 (T_i+1, T_i), b1, W2 (T_i+1, T_i+1), b2 | trend by scale i = 0..n-1 (= up_sampling_layers[n-1-i]): W1 (T_i, T_i+1),
+ * b1, W2 (T_i, T_i), b2 | out_layer W1 (d_ff, d), b1, W2 (d, d_ff), b2], then [predict_layers[n] weight (P, T_n), bias, projection weight
+ * (C, d), bias].  The LAST block's trend entries are never read.
+ * Dropout of the embedding (p_drop > 0): Philox key seed (+ *seed_step_dev if given), one site, element index
+ * ((off_i B + b T_i + t) d_model + f) with off_i = T_0 + .. + T_i-1 -- the scales' (B, T_i, d_model) arrays one after the other; backward
+ * must get the forward's p_drop / seed / site and redraws the bits.
+ * ..._grad_layout: the float offset of every table entry's gradient in the flat `grads` buffer of backward (-1: the entry has none: pe,
+ * the last block's trend entries); returns the buffer's length in floats, -1 for unsupported dimensions.  backward overwrites all of it.
+ * The sums over the windows run in an order fixed by the shape (per-workgroup slabs in `workspace`, folded in index order; no
+ * floating-point atomics, no zero-fill): the same inputs give the same bits.
+ * ..._supported: 2 <= S <= 64, 1 <= P <= 64, 2C+1 <= 64, d_model <= 32, d_ff <= 64, 1 <= e_layers <= 4, 1 <= n <= 6 with S >> n >= 1,
+ * moving_avg odd, 1 <= moving_avg < 2^24, and the window's LDS image within a workgroup's share; otherwise 0 and the compute calls return
+ * IMMTSF_EUNSUPPORTED.  ..._workspace_bytes: the backward's workspace (host arithmetic only; 0 for bad dimensions). */
+int immtsf_timemixer_supported(int32_t S, int32_t P, int32_t C, int32_t d_model, int32_t d_ff, int32_t e_layers, int32_t down_layers,
+                               int32_t moving_avg);
+int32_t immtsf_timemixer_grad_layout(int32_t S, int32_t P, int32_t C, int32_t d_model, int32_t d_ff, int32_t e_layers, int32_t down_layers,
+                                     int32_t* offsets, int32_t n_offsets);
+size_t immtsf_timemixer_workspace_bytes(int32_t B, int32_t S, int32_t P, int32_t C, int32_t d_model, int32_t d_ff, int32_t e_layers,
+                                        int32_t down_layers);
+int immtsf_timemixer_forward(int32_t B, int32_t L, int32_t C, int32_t S, int32_t P, int32_t Lp, int32_t d_model, int32_t d_ff, int32_t e_layers,
+                             int32_t down_layers, int32_t moving_avg, const float* data, const float* mask, const float* tp,
+                             const float* const* params, float* y, float p_drop, uint64_t seed, uint64_t site, const uint64_t* seed_step_dev,
+                             immtsf_stream_t stream);
+int immtsf_timemixer_backward(int32_t B, int32_t L, int32_t C, int32_t S, int32_t P, int32_t Lp, int32_t d_model, int32_t d_ff,
+                              int32_t e_layers, int32_t down_layers, int32_t moving_avg, const float* data, const float* mask, const float* tp,
+                              const float* const* params, const float* dY, float* grads, float p_drop, uint64_t seed, uint64_t site,
+                              const uint64_t* seed_step_dev, void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
+
 /* ---- device-side batch builder: the reference's collate functions over a dataset that is
  * resident in HBM.  Replaces lib/parse_datasets.py:252-295 (variable_time_collate_fn), :298-366 +
  * lib/utils.py:359-413 (patch_variable_time_collate_fn / split_and_patch_batch) and :764-824 (multimodal wrapper).
