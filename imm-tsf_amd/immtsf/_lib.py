@@ -171,6 +171,14 @@ _PROTOS = {
                                            C.c_void_p, c_stream]),
     "immtsf_timemixer_backward": (C.c_int, [C.c_int32] * 11 + [c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_float, C.c_uint64,
                                             C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,
+                                           C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, c_stream]),
+    "immtsf_ttm_mixer_backward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float] +
+                                  [c_f32p] * 10 + [C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_ttm_gate_forward": (C.c_int, [C.c_int64, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "immtsf_ttm_gate_backward": (C.c_int, [C.c_int64, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "immtsf_eval_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "immtsf_eval_metrics_accum": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                             c_stream]),

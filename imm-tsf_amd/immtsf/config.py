@@ -125,3 +125,7 @@ dlinear_fused = os.environ.get("IMMTSF_DLINEAR_FUSED", "1") != "0"
 # and immtsf_timemixer_supported allows; IMMTSF_TIMEMIXER_FUSED=0: the composed path (one embedding kernel per scale, torch element-wise
 # ops around immtsf.ops.linear calls) -- the cross-check.  fp32 in either precision mode
 timemixer_fused = os.environ.get("IMMTSF_TIMEMIXER_FUSED", "1") != "0"
+# TTM's narrow mixer blocks (patch / channel) as one HIP launch forward and two backward, and the feature mixer's gate + residual as one
+# launch per direction (csrc/ttm.hip), block by block wherever immtsf_ttm_mixer_supported allows; IMMTSF_TTM_FUSED=0: the composed path
+# (torch element-wise ops and permutes around immtsf.ops.linear / layer_norm calls) -- the cross-check.  The kernels are fp32 in either mode
+ttm_fused = os.environ.get("IMMTSF_TTM_FUSED", "1") != "0"

@@ -2727,3 +2727,121 @@ def timemixer_forecast(model, data, mask, tp, Lp):
     drop = (p, config.next_seed() if p > 0 else 0, SITE_TIMEMIXER_EMBED, config.dropout_counter_ptr(data.device) if p > 0 else None)
     model._last_drop = drop      # (p, seed, site, counter pointer) of this module's latest fused call: what dropout_keep_mask reproduces
     return TimeMixerFn.apply(data, mask, tp, int(Lp), dims, drop, table, *params)
+
+
+# ------------------------------------------------------------------------------------------------ TTM backbone
+SITE_TTM_MIXER = SITE_LAYER_BASE + 43      # drop1 of a narrow mixer block inside csrc/ttm.hip; its drop2 is SITE_TTM_MIXER + 1
+_TTM_MODES = {"patch": 0, "channel": 1}
+
+
+def _ttm_view(mode, shape):
+    """x (B, M, N, D) -> (mode code, outer, inner, F, D) of immtsf_ttm_mixer_*: the block mixes F at every (outer, inner, column)"""
+    B, M, N, D = shape
+    return (0, B * M, 1, N, D) if mode == "patch" else (1, B, N, M, D)
+
+
+def ttm_mixer_supported(mode, shape):
+    """the limits of the narrow mixer kernel (immtsf_ttm_mixer_supported) for x of `shape` (B, M, N, D): mode patch / channel,
+    mixed axis F <= 32, D <= 65536, fewer than 2^31 elements"""
+    if mode not in _TTM_MODES or len(shape) != 4 or min(shape) < 1:
+        return False
+    return bool(_lib.load().immtsf_ttm_mixer_supported(*[int(v) for v in _ttm_view(mode, shape)]))
+
+
+def ttm_mixer_params(block):
+    """a layers.MLP.TTMMixerBlock's tensors in the kernel's order: gamma, beta, W1, b1, W2, b2, Wg, bg"""
+    return (block.norm.weight, block.norm.bias, block.mlp.fc1.weight, block.mlp.fc1.bias, block.mlp.fc2.weight, block.mlp.fc2.bias,
+            block.gating_block.attn_layer.weight, block.gating_block.attn_layer.bias)
+
+
+class TTMMixerFn(torch.autograd.Function):
+    """One TTMMixerBlock in mode patch / channel on a contiguous x (B, M, N, D) as ONE launch; backward = dx and the eight parameter
+    gradients in TWO (immtsf_ttm_mixer_forward / _backward, csrc/ttm.hip), recomputed from x: nothing else is saved.  drop = (p, seed,
+    site, device counter).  The kernel OVERWRITES its gradient buffers, so they are a fresh allocation whose slices are handed to
+    autograd: a parameter's FlatTrainer sink (pre-zeroed, shared or not) receives its slice through AccumulateGrad, as with DLinearFn
+    and TimeMixerFn, and a block called twice before one backward accumulates.  fp32 in either precision mode."""
+
+    @staticmethod
+    def forward(ctx, x, mode, drop, eps, *params):
+        lib = _lib.load()
+        x = _c(x)
+        _need_gpu(x, *params)
+        view = _ttm_view(mode, x.shape)
+        p, seed, site, cnt = drop
+        out = torch.empty_like(x)
+        check(lib.immtsf_ttm_mixer_forward(*view, ptr(x), *[ptr(q) for q in params], eps, ptr(out), p, seed, site, cnt, stream_ptr()),
+              "ttm_mixer_forward")
+        ctx.cfg = (view, drop, eps)
+        ctx.save_for_backward(x, *params)      # the parameters: saved (no copy), so that autograd's version check covers them
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        x, params = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        view, (p, seed, site, cnt), eps = ctx.cfg
+        dout = dout.contiguous()
+        dx = torch.empty_like(x)
+        need = ctx.needs_input_grad[4:]
+        bufs, rets = [None] * 8, [None] * 8
+        if any(need):
+            bufs, rets = _grad_buffers([q if n else None for q, n in zip(params, need)])      # overwritten by the fold
+        g = dict(zip(("gamma", "beta", "W1", "b1", "W2", "b2", "Wg", "bg"), bufs))
+        ws = _bytes(lib.immtsf_ttm_mixer_workspace_bytes(*view), dout.device)
+        check(lib.immtsf_ttm_mixer_backward(*view, ptr(x), *[ptr(q) for q in params], eps, ptr(dout), ptr(dx), ptr(g["gamma"]), ptr(g["beta"]),
+                                            ptr(g["W1"]), ptr(g["b1"]), ptr(g["W2"]), ptr(g["b2"]), ptr(g["Wg"]), ptr(g["bg"]), p, seed, site,
+                                            cnt, ptr(ws), ws.numel(), stream_ptr()), "ttm_mixer_backward")
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None) + tuple(rets)
+
+
+class TTMGateFn(torch.autograd.Function):
+    """out = res + u softmax(g) over the last axis, one launch; backward = du, dg in one (immtsf_ttm_gate_forward / _backward); the
+    residual's gradient is the upstream gradient itself"""
+
+    @staticmethod
+    def forward(ctx, res, u, g):
+        lib = _lib.load()
+        res, u, g = _c(res), _c(u), _c(g)
+        _need_gpu(res, u, g)
+        d = u.shape[-1]
+        out = torch.empty_like(u)
+        check(lib.immtsf_ttm_gate_forward(u.numel() // d, d, ptr(res), ptr(u), ptr(g), ptr(out), stream_ptr()), "ttm_gate_forward")
+        ctx.save_for_backward(u, g)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        u, g = ctx.saved_tensors
+        d = u.shape[-1]
+        dout = dout.contiguous()
+        du, dg = torch.empty_like(u), torch.empty_like(u)
+        check(lib.immtsf_ttm_gate_backward(u.numel() // d, d, ptr(u), ptr(g), ptr(dout), ptr(du), ptr(dg), stream_ptr()), "ttm_gate_backward")
+        return dout, du, dg
+
+
+def ttm_mixer(block, x, mode, training):
+    """a layers.MLP.TTMMixerBlock in mode "patch" / "channel" on a contiguous fp32 x (B, M, N, D) -> x + gate(mlp(norm(x) along the mixed
+    axis)).  In training mode with dropout > 0 both dropouts are drawn inside the kernel: one config.next_seed() per call, sites
+    SITE_TTM_MIXER / + 1, the device counter of config.enable_device_counters honoured; block._last_drop keeps what dropout_keep_mask
+    reproduces them from."""
+    params = ttm_mixer_params(block)
+    F_ = x.shape[2] if mode == "patch" else x.shape[1]
+    want = [(x.shape[3],), (x.shape[3],), (2 * F_, F_), (2 * F_,), (F_, 2 * F_), (F_,), (F_, F_), (F_,)]
+    if not ttm_mixer_supported(mode, tuple(x.shape)) or not x.is_contiguous() or x.dtype != torch.float32:
+        raise _lib.ImmtsfError(f"ttm_mixer: x {tuple(x.shape)} in mode {mode} is outside the kernel")
+    if any(not q.is_contiguous() or q.dtype != torch.float32 or tuple(q.shape) != w for q, w in zip(params, want)):
+        raise _lib.ImmtsfError("ttm_mixer: the block's parameters are not the contiguous fp32 tensors of these dimensions")
+    p = float(block.mlp.dropout1.p) if training else 0.0
+    if p > 0 and float(block.mlp.dropout2.p) != p:
+        raise _lib.ImmtsfError("ttm_mixer: the two dropouts of a block share one probability")
+    drop = (p, config.next_seed() if p > 0 else 0, SITE_TTM_MIXER, config.dropout_counter_ptr(x.device) if p > 0 else None)
+    block._last_drop = drop
+    return TTMMixerFn.apply(x, mode, drop, float(block.norm.eps), *params)
+
+
+def ttm_gate(res, u, g):
+    """res + u * softmax(g, -1), fp32 tensors of one shape on the GPU"""
+    if not (res.shape == u.shape == g.shape) or u.dim() < 1 or u.shape[-1] < 1:
+        raise _lib.ImmtsfError(f"ttm_gate: shapes {tuple(res.shape)}, {tuple(u.shape)}, {tuple(g.shape)}")
+    return TTMGateFn.apply(res.float(), u.float(), g.float())

@@ -640,6 +640,40 @@ int immtsf_timemixer_backward(int32_t B, int32_t L, int32_t C, int32_t S, int32_
                               const float* const* params, const float* dY, float* grads, float p_drop, uint64_t seed, uint64_t site,
                               const uint64_t* seed_step_dev, void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
 
+/* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
+ * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
+ * launch per direction.  All fp32.
+ * Narrow block: x, out, dout, dx are contiguous (outer, F, inner, D) tensors and the block mixes the F axis at every (group g = outer
+ * index * inner + inner index, column c < D).  mode 0 = patch: x (B, M, N', D') with outer = B M, F = N', inner = 1, D = D'; mode 1 =
+ * channel: outer = B, F = M, inner = N', D = D'.  Per (g, c), with xn = LayerNorm_D(x; gamma, beta, eps):
+ *   v = xn[g, :, c] (F);  h = drop1(gelu(W1 v + b1)) (2F);  u = drop2(W2 h + b2) (F);  a = softmax_F(Wg u + bg);  out = x + u a
+ * gamma, beta (D); W1 (2F, F), b1 (2F), W2 (F, 2F), b2 (F): mlp.fc1 / fc2; Wg (F, F), bg (F): gating_block.attn_layer.
+ * Dropout (p_drop > 0): Philox key seed (+ *seed_step_dev if given); site: drop1, element ((g D + c) S1 + j), j < 2F, S1 = 2F rounded up
+ * to a multiple of 4; site + 1: drop2, element ((g D + c) S2 + o), o < F, S2 = F rounded up to a multiple of 4 (the padding elements are
+ * drawn by nobody).  backward must get the forward's p_drop / seed / site and redraws the bits.
+ * backward recomputes the forward from x (nothing else is saved), OVERWRITES dx (a buffer of its own: not dout) and the eight parameter
+ * gradients; a null gradient pointer skips that tensor.  The sums run in an order fixed by the shape (per-workgroup slabs in
+ * `workspace`, folded in index order; no floating-point atomics, no zero fill): the same inputs give the same bits.
+ * ..._supported: mode 0 / 1 (mode 0: inner = 1), 1 <= F <= 32, 1 <= D <= 65536, outer inner F D < 2^31; a workgroup's LDS (weights,
+ * statistics, the backward's staging buffer) stays within 64 KB, two workgroups per CU.  Otherwise 0 and the compute calls return
+ * IMMTSF_EUNSUPPORTED.  ..._workspace_bytes: the backward's workspace (host arithmetic only; 0 for unsupported dimensions).
+ * Gate rows: out = res + u softmax_d(g) per row of d >= 1 (a wave per row, any d); backward: du = dout a, dg = a (dout u - sum a dout u);
+ * the residual's gradient is dout itself. */
+int immtsf_ttm_mixer_supported(int32_t mode, int64_t outer, int32_t inner, int32_t F, int32_t D);
+size_t immtsf_ttm_mixer_workspace_bytes(int32_t mode, int64_t outer, int32_t inner, int32_t F, int32_t D);
+int immtsf_ttm_mixer_forward(int32_t mode, int64_t outer, int32_t inner, int32_t F, int32_t D, const float* x, const float* gamma,
+                             const float* beta, const float* W1, const float* b1, const float* W2, const float* b2, const float* Wg,
+                             const float* bg, float eps, float* out, float p_drop, uint64_t seed, uint64_t site, const uint64_t* seed_step_dev,
+                             immtsf_stream_t stream);
+int immtsf_ttm_mixer_backward(int32_t mode, int64_t outer, int32_t inner, int32_t F, int32_t D, const float* x, const float* gamma,
+                              const float* beta, const float* W1, const float* b1, const float* W2, const float* b2, const float* Wg,
+                              const float* bg, float eps, const float* dout, float* dx, float* dgamma, float* dbeta, float* dW1, float* db1,
+                              float* dW2, float* db2, float* dWg, float* dbg, float p_drop, uint64_t seed, uint64_t site,
+                              const uint64_t* seed_step_dev, void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
+int immtsf_ttm_gate_forward(int64_t rows, int32_t d, const float* res, const float* u, const float* g, float* out, immtsf_stream_t stream);
+int immtsf_ttm_gate_backward(int64_t rows, int32_t d, const float* u, const float* g, const float* dout, float* du, float* dg,
+                             immtsf_stream_t stream);
+
 /* ---- device-side batch builder: the reference's collate functions over a dataset that is
  * resident in HBM.  Replaces lib/parse_datasets.py:252-295 (variable_time_collate_fn), :298-366 +
  * lib/utils.py:359-413 (patch_variable_time_collate_fn / split_and_patch_batch) and :764-824 (multimodal wrapper).
