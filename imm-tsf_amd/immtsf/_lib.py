@@ -179,6 +179,15 @@ _PROTOS = {
                                   [c_f32p] * 10 + [C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_ttm_gate_forward": (C.c_int, [C.c_int64, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "immtsf_ttm_gate_backward": (C.c_int, [C.c_int64, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "immtsf_prob_attention_supported": (C.c_int, [C.c_int32] * 4),
+    "immtsf_prob_attention_forward": (C.c_int, [C.c_int32] * 8 + [C.c_float, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p,
+                                                c_stream]),
+    "immtsf_prob_attention_backward": (C.c_int, [C.c_int32] * 7 + [C.c_float] + [c_f32p] * 5 + [c_i32p] + [c_f32p] * 4 + [c_stream]),
+    "immtsf_conv_distil_supported": (C.c_int, [C.c_int32]),
+    "immtsf_conv_distil_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "immtsf_conv_distil_forward": (C.c_int, [C.c_int32] * 4 + [c_f32p, c_f32p, c_f32p, C.c_float, C.c_float, c_f32p, c_f32p, C.c_void_p, c_f32p,
+                                             c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_conv_distil_backward": (C.c_int, [C.c_int32] * 4 + [c_f32p] * 10 + [C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_eval_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "immtsf_eval_metrics_accum": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                             c_stream]),

@@ -129,3 +129,8 @@ timemixer_fused = os.environ.get("IMMTSF_TIMEMIXER_FUSED", "1") != "0"
 # launch per direction (csrc/ttm.hip), block by block wherever immtsf_ttm_mixer_supported allows; IMMTSF_TTM_FUSED=0: the composed path
 # (torch element-wise ops and permutes around immtsf.ops.linear / layer_norm calls) -- the cross-check.  The kernels are fp32 in either mode
 ttm_fused = os.environ.get("IMMTSF_TTM_FUSED", "1") != "0"
+# Informer's layers: ProbAttention as two HIP launches per direction (csrc/prob_attn.hip) wherever immtsf_prob_attention_supported allows,
+# and ConvLayer's BatchNorm + ELU + MaxPool on rows (csrc/conv_distil.hip) wherever immtsf_conv_distil_supported allows;
+# IMMTSF_INFORMER_FUSED=0: the composed path (torch gather / sort / scatter, nn.BatchNorm1d, nn.MaxPool1d) with the same tie rule -- the
+# cross-check.  The kernels are fp32 in either precision mode
+informer_fused = os.environ.get("IMMTSF_INFORMER_FUSED", "1") != "0"

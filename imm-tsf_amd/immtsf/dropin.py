@@ -8,7 +8,7 @@ does not mirror (`lib.utils`, `lib.parse_datasets`, `models.Informer`, ...), so:
     sys.path to the package's __path__: mirrored modules resolve here, everything else resolves to the reference;
   * `reexport_missing` (called at the end of a mirrored module) loads the shadowed reference module of the same name, if
     one exists, and copies the public names this build does not define (`layers.Embed.DataEmbedding_wo_pos`,
-    `layers.Transformer_EncDec.Decoder`, ...), so the reference's other models keep importing what they need.
+    `layers.Transformer_EncDec.TimerLayer`, ...), so the reference's other models keep importing what they need.
 
 Both are no-ops when no reference tree is on the path (the tests, the GPU box).
 """

@@ -2845,3 +2845,151 @@ def ttm_gate(res, u, g):
     if not (res.shape == u.shape == g.shape) or u.dim() < 1 or u.shape[-1] < 1:
         raise _lib.ImmtsfError(f"ttm_gate: shapes {tuple(res.shape)}, {tuple(u.shape)}, {tuple(g.shape)}")
     return TTMGateFn.apply(res.float(), u.float(), g.float())
+
+
+# ---- Informer's layers (csrc/prob_attn.hip, csrc/conv_distil.hip) ----------------------------------------------------------------------
+def prob_attention_supported(L_Q, L_K, D, u):
+    """the limits of the ProbAttention kernels (immtsf_prob_attention_supported): lengths <= 1024 in both roles, head width <= 512,
+    1 <= u <= L_Q"""
+    return bool(_lib.load().immtsf_prob_attention_supported(int(L_Q), int(L_K), int(D), int(u)))
+
+
+class ProbAttentionFn(torch.autograd.Function):
+    """immtsf_prob_attention_forward / _backward: two launches each.  q (B, L_Q, H, D), k / v (B, L_K, H, D), index_sample (L_Q, U)
+    int32 -> (B, H, L_Q, D); P (B, H, u, L_K) and the selected indices (B, H, u), ascending, are saved (ctx.sel is also left on the
+    Function's output as `.prob_sel` for the tests)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, index_sample, n_top, scale, causal):
+        lib = _lib.load()
+        q, k, v, index_sample = _c(q), _c(k), _c(v), _c(index_sample)
+        _need_gpu(q, k, v, index_sample)
+        B, LQ, H, D = q.shape
+        LK, U = k.shape[1], index_sample.shape[1]
+        dev = q.device
+        M = torch.empty(B, H, LQ, dtype=torch.float32, device=dev)
+        out = torch.empty(B, H, LQ, D, dtype=torch.float32, device=dev)
+        P = torch.empty(B, H, n_top, LK, dtype=torch.float32, device=dev)
+        sel = torch.empty(B, H, n_top, dtype=torch.int32, device=dev)
+        check(lib.immtsf_prob_attention_forward(B, H, LQ, LK, D, U, n_top, 1 if causal else 0, scale, ptr(q), ptr(k), ptr(v), ptr(index_sample),
+                                                ptr(M), ptr(out), ptr(P), ptr(sel), stream_ptr()), "prob_attention_forward")
+        ctx.save_for_backward(q, k, v, P, sel)
+        ctx.cfg = (B, H, LQ, LK, D, n_top, 1 if causal else 0, scale)
+        ctx.mark_non_differentiable(sel, M)
+        return out, sel, M
+
+    @staticmethod
+    def backward(ctx, dout, _dsel, _dM):
+        lib = _lib.load()
+        q, k, v, P, sel = ctx.saved_tensors
+        B, H, LQ, LK, D, u, causal, scale = ctx.cfg
+        dout = dout.contiguous()
+        dq, dk, dv, dS = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v), torch.empty_like(P)
+        check(lib.immtsf_prob_attention_backward(B, H, LQ, LK, D, u, causal, scale, ptr(q), ptr(k), ptr(v), ptr(dout), ptr(P), ptr(sel), ptr(dS),
+                                                 ptr(dq), ptr(dk), ptr(dv), stream_ptr()), "prob_attention_backward")
+        return dq, dk, dv, None, None, None, None
+
+
+def prob_attention_composed(q, k, v, index_sample, n_top, scale, causal, want_sel=False):
+    """the same function from torch ops (the cross-check, and the path outside the kernels' limits): the un-squeezed measure, ties in it
+    to the lower query index (a stable descending sort), the selected set ascending.  No gradient flows through the measure."""
+    _need_gpu(q, k, v, index_sample)
+    B, LQ, H, D = q.shape
+    LK = k.shape[1]
+    Q, K, V = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)      # (B, H, L, D)
+    idx = index_sample.long().clamp(0, LK - 1)
+    with torch.no_grad():
+        Ks = K[:, :, idx, :]                                                # (B, H, L_Q, U, D)
+        QK = torch.einsum("bhld,bhlud->bhlu", Q, Ks)
+        M = QK.max(-1).values - QK.sum(-1) / LK
+        M = torch.where(torch.isnan(M), torch.full_like(M, float("-inf")), M)
+        top = torch.sort(M, dim=-1, descending=True, stable=True).indices[..., :n_top]
+        top = torch.sort(top, dim=-1).values                                # (B, H, u) ascending
+    gather = top.unsqueeze(-1).expand(B, H, n_top, D)
+    scores = torch.matmul(torch.gather(Q, 2, gather), K.transpose(-2, -1)) * scale
+    if causal:
+        assert LQ == LK
+        keys = torch.arange(LK, device=q.device)
+        scores = scores.masked_fill(keys[None, None, None, :] > top.unsqueeze(-1), float("-inf"))
+        ctxt = V.cumsum(dim=-2)
+    else:
+        ctxt = V.mean(dim=-2, keepdim=True).expand(B, H, LQ, D)
+    upd = torch.matmul(torch.softmax(scores, dim=-1), V)
+    out = torch.scatter(ctxt.contiguous(), 2, gather, upd)
+    return (out, top.int()) if want_sel else out
+
+
+def prob_attention(q, k, v, index_sample, n_top, scale, causal, want_sel=False):
+    """Informer's ProbAttention core on q (B, L_Q, H, D), k / v (B, L_K, H, D) with an explicit (L_Q, U_part) integer sample of key indices:
+    -> (B, H, L_Q, D) contiguous (want_sel: also the selected query indices (B, H, n_top), ascending).  The kernels wherever
+    prob_attention_supported allows and config.informer_fused is on, else prob_attention_composed.  fp32 in either precision mode."""
+    if q.dim() != 4 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2:] != q.shape[2:] or index_sample.dim() != 2:
+        raise _lib.ImmtsfError(f"prob_attention: shapes {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}, {tuple(index_sample.shape)}")
+    q, k, v, index_sample = q.float(), k.float(), v.float(), index_sample.to(torch.int32)
+    _need_gpu(q, k, v, index_sample)
+    B, LQ, H, D = q.shape
+    LK, U = k.shape[1], index_sample.shape[1]
+    n_top = int(n_top)
+    if index_sample.shape[0] != LQ or not 1 <= U or not 1 <= n_top <= LQ or (causal and LQ != LK):
+        raise _lib.ImmtsfError(f"prob_attention: sample {tuple(index_sample.shape)}, n_top {n_top}, causal {causal} for L_Q {LQ}, L_K {LK}")
+    if config.informer_fused and U <= LK and prob_attention_supported(LQ, LK, D, n_top):
+        out, sel, _ = ProbAttentionFn.apply(q, k, v, index_sample, n_top, float(scale), bool(causal))
+        return (out, sel) if want_sel else out
+    return prob_attention_composed(q, k, v, index_sample, n_top, float(scale), bool(causal), want_sel)
+
+
+def conv_distil_supported(d):
+    """the widths the ConvLayer row kernels take (immtsf_conv_distil_supported; as residual_layernorm_supported): d % 4 == 0, d <= 1024"""
+    return d % 4 == 0 and 4 <= d <= 1024
+
+
+class ConvDistilFn(torch.autograd.Function):
+    """BatchNorm1d + ELU + MaxPool1d(3, 2, 1) on the rows y (B, L + 2, d) of ConvLayer's product (immtsf_conv_distil_forward / _backward):
+    two launches per direction, one for an evaluation forward.  The running buffers are updated in place by the kernel."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, running_mean, running_var, batches, eps, momentum, training):
+        lib = _lib.load()
+        y = _c(y)
+        _need_gpu(y, gamma, beta, running_mean, running_var)
+        B, T, d = y.shape
+        L = T - 2
+        mean, rstd = torch.empty(d, dtype=torch.float32, device=y.device), torch.empty(d, dtype=torch.float32, device=y.device)
+        out = torch.empty(B, (L + 1) // 2 + 1, d, dtype=torch.float32, device=y.device)
+        ws = _bytes(lib.immtsf_conv_distil_workspace_bytes(B, L, d), y.device)
+        check(lib.immtsf_conv_distil_forward(B, L, d, 1 if training else 0, ptr(y), ptr(gamma), ptr(beta), eps, momentum, ptr(running_mean),
+                                             ptr(running_var), ptr(batches), ptr(mean), ptr(rstd), ptr(out), ptr(ws), ws.numel(), stream_ptr()),
+              "conv_distil_forward")
+        ctx.save_for_backward(y, gamma, beta, mean, rstd)
+        ctx.cfg = (B, L, d, 1 if training else 0)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        y, gamma, beta, mean, rstd = ctx.saved_tensors
+        B, L, d, training = ctx.cfg
+        dout = dout.contiguous()
+        dn, dy = torch.empty_like(y), torch.empty_like(y)
+        (dgamma, dbeta), rets = _grad_buffers((gamma, beta))
+        ws = _bytes(lib.immtsf_conv_distil_workspace_bytes(B, L, d), y.device)
+        check(lib.immtsf_conv_distil_backward(B, L, d, training, ptr(y), ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), ptr(dout), ptr(dn), ptr(dy),
+                                              ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream_ptr()), "conv_distil_backward")
+        return dy, rets[0], rets[1], None, None, None, None, None, None
+
+
+def conv_distil(x, conv, norm, training, precision=None):
+    """Informer's ConvLayer on x (B, L, d), L >= 2: conv = nn.Conv1d(d, d, 3, padding=2, padding_mode="circular"), norm = nn.BatchNorm1d(d)
+    with affine parameters, running statistics and a float momentum -> (B, (L + 1) // 2 + 1, d).  The three taps are ONE product of the
+    GEMM family over the gathered image [x[t-2], x[t-1], x[t]] (indices mod L) of L + 2 rows; everything behind it is ConvDistilFn."""
+    _need_gpu(x)
+    B, L, d = x.shape
+    if L < 2 or not conv_distil_supported(d) or tuple(conv.weight.shape) != (d, d, 3):
+        raise _lib.ImmtsfError(f"conv_distil: x {tuple(x.shape)}, weight {tuple(conv.weight.shape)} is outside the kernel")
+    x = x.float()
+    xw = torch.cat([x[:, L - 2:], x, x[:, :2]], dim=1)                                      # xw[m] = x[(m - 2) mod L], L + 4 rows
+    img = torch.cat([xw[:, 0:L + 2], xw[:, 1:L + 3], xw[:, 2:L + 4]], dim=-1)               # (B, L + 2, 3 d): tap k at columns k d ..
+    W3 = conv.weight.permute(0, 2, 1).reshape(d, 3 * d)
+    y = linear(img, W3, conv.bias, precision)
+    return ConvDistilFn.apply(y, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.num_batches_tracked, float(norm.eps),
+                              float(norm.momentum), bool(training))

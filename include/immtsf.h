@@ -674,6 +674,37 @@ int immtsf_ttm_gate_forward(int64_t rows, int32_t d, const float* res, const flo
 int immtsf_ttm_gate_backward(int64_t rows, int32_t d, const float* u, const float* g, const float* dout, float* du, float* dg,
                              immtsf_stream_t stream);
 
+/* ---- Informer's layers (added within ABI 7: new functions only; csrc/prob_attn.hip, csrc/conv_distil.hip).  All fp32.
+ * ProbAttention (reference layers/SelfAttention_Family.py:80-178): q (B, L_Q, H, D), k / v (B, L_K, H, D) contiguous, index_sample
+ * (L_Q, U_part) int32 key indices shared by every batch and head (values outside [0, L_K) are clamped), u = n_top.  forward, two
+ * launches: M (B, H, L_Q) = max_j q_i.k_s(i,j) - sum_j q_i.k_s(i,j) / L_K; the u queries with the largest M per (b, h) -- ties to the
+ * lower index, NaN as -inf, the set stored ascending in sel (B, H, u) -- get softmax(scale q K^T) V (causal: key j > i masked) with
+ * their probabilities kept in P (B, H, u, L_K); every other row of out (B, H, L_Q, D) is mean(V), or with causal (L_Q == L_K) the running
+ * sum of V.  backward, two launches: OVERWRITES dq, dk, dv (the inputs' layouts; dq is exact zeros on unselected rows) from dO
+ * (B, H, L_Q, D), P and sel; dS (B, H, u, L_K) is scratch.  No gradient through M.  No atomics, fixed orders: same inputs, same bits.
+ * ..._supported: 1 <= L_Q, L_K <= 1024, 1 <= D <= 512, 1 <= u <= L_Q (a workgroup's LDS is 37 KB); otherwise IMMTSF_EUNSUPPORTED.
+ * ConvLayer behind its three-tap product (reference layers/Transformer_EncDec.py:6-24): y (B, L + 2, d) rows of the circular
+ * convolution -> BatchNorm1d (training: batch statistics, running_mean / running_var (unbiased) / num_batches updated IN PLACE by the
+ * kernel; else the running statistics) -> ELU -> max over {2s-1, 2s, 2s+1} -> out (B, (L + 1) / 2 + 1, d); mean, rstd (d) are kept for
+ * the backward, which routes to the first maximum, OVERWRITES dy (B, L + 2, d), dgamma, dbeta and uses dn (B, L + 2, d) as scratch.
+ * Two launches per direction (evaluation forward: one).  ..._supported: d % 4 == 0, 4 <= d <= 1024; L >= 2.
+ * ..._workspace_bytes: the per-share partial sums of either direction (host arithmetic only; 0 for unsupported dimensions). */
+int immtsf_prob_attention_supported(int32_t L_Q, int32_t L_K, int32_t D, int32_t u);
+int immtsf_prob_attention_forward(int32_t B, int32_t H, int32_t L_Q, int32_t L_K, int32_t D, int32_t U_part, int32_t u, int32_t causal,
+                                  float scale, const float* q, const float* k, const float* v, const int32_t* index_sample, float* M,
+                                  float* out, float* P, int32_t* sel, immtsf_stream_t stream);
+int immtsf_prob_attention_backward(int32_t B, int32_t H, int32_t L_Q, int32_t L_K, int32_t D, int32_t u, int32_t causal, float scale,
+                                   const float* q, const float* k, const float* v, const float* dO, const float* P, const int32_t* sel,
+                                   float* dS, float* dq, float* dk, float* dv, immtsf_stream_t stream);
+int immtsf_conv_distil_supported(int32_t d);
+size_t immtsf_conv_distil_workspace_bytes(int32_t B, int32_t L, int32_t d);
+int immtsf_conv_distil_forward(int32_t B, int32_t L, int32_t d, int32_t training, const float* y, const float* gamma, const float* beta,
+                               float eps, float momentum, float* running_mean, float* running_var, int64_t* num_batches, float* mean,
+                               float* rstd, float* out, void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
+int immtsf_conv_distil_backward(int32_t B, int32_t L, int32_t d, int32_t training, const float* y, const float* gamma, const float* beta,
+                                const float* mean, const float* rstd, const float* dout, float* dn, float* dy, float* dgamma, float* dbeta,
+                                void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
+
 /* ---- device-side batch builder: the reference's collate functions over a dataset that is
  * resident in HBM.  Replaces lib/parse_datasets.py:252-295 (variable_time_collate_fn), :298-366 +
  * lib/utils.py:359-413 (patch_variable_time_collate_fn / split_and_patch_batch) and :764-824 (multimodal wrapper).
