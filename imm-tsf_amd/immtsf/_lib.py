@@ -171,6 +171,12 @@ _PROTOS = {
                                            C.c_void_p, c_stream]),
     "immtsf_timemixer_backward": (C.c_int, [C.c_int32] * 11 + [c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_float, C.c_uint64,
                                             C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_cru_supported": (C.c_int, [C.c_int32] * 4),
+    "immtsf_cru_grad_layout": (C.c_int32, [C.c_int32] * 3 + [c_i32p, C.c_int32]),
+    "immtsf_cru_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "immtsf_cru_forward": (C.c_int, [C.c_int32] * 5 + [c_f32p, c_f32p, c_u8p, c_f32p] + [c_f32p] * 9 + [c_f32p] * 4 + [c_stream]),
+    "immtsf_cru_backward": (C.c_int, [C.c_int32] * 5 + [c_f32p, c_f32p, c_u8p, c_f32p] + [c_f32p] * 9 + [c_f32p] * 5 + [c_f32p] * 3 +
+                            [C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,

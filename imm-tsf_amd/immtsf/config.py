@@ -134,3 +134,7 @@ ttm_fused = os.environ.get("IMMTSF_TTM_FUSED", "1") != "0"
 # IMMTSF_INFORMER_FUSED=0: the composed path (torch gather / sort / scatter, nn.BatchNorm1d, nn.MaxPool1d) with the same tie rule -- the
 # cross-check.  The kernels are fp32 in either precision mode
 informer_fused = os.environ.get("IMMTSF_INFORMER_FUSED", "1") != "0"
+# CRU's Kalman recurrence as one HIP launch forward and two backward (csrc/cru.hip) wherever the cell is the continuous CRUCell with the
+# single Linear + softmax coefficient net and immtsf_cru_supported allows; IMMTSF_CRU_FUSED=0: the composed path (a Python loop over the
+# time points around torch.matrix_exp) -- the cross-check.  The kernels are fp32 in either precision mode
+cru_fused = os.environ.get("IMMTSF_CRU_FUSED", "1") != "0"

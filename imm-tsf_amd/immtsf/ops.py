@@ -2993,3 +2993,93 @@ def conv_distil(x, conv, norm, training, precision=None):
     y = linear(img, W3, conv.bias, precision)
     return ConvDistilFn.apply(y, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.num_batches_tracked, float(norm.eps),
                               float(norm.momentum), bool(training))
+
+
+# ------------------------------------------------------------------------------------------------ CRU backbone
+_cru_layouts = {}
+
+
+def cru_supported(lsd, num_basis, bandwidth, T):
+    """the limits of the fused CRU recurrence (immtsf_cru_supported): lsd even, 2 <= lsd <= 32, num_basis <= 256, bandwidth <= lsd / 2,
+    1 <= T <= 2^20"""
+    return bool(_lib.load().immtsf_cru_supported(int(lsd), int(num_basis), int(bandwidth), int(T)))
+
+
+def _cru_layout(lsd, K, bw):
+    """-> (the nine float offsets of [tm11 | tm12 | tm21 | tm22 | coef_w | coef_b | trans_var | icu | icl] in the flat gradient, its length)"""
+    got = _cru_layouts.get((lsd, K, bw))
+    if got is None:
+        offs = torch.zeros(9, dtype=torch.int32)
+        nv = int(_lib.load().immtsf_cru_grad_layout(lsd, K, bw, offs.data_ptr(), 9))
+        if nv < 0:
+            raise _lib.ImmtsfError(f"cru_scan: dimensions outside the fused kernel (lsd {lsd}, num_basis {K}, bandwidth {bw})")
+        got = _cru_layouts[(lsd, K, bw)] = (offs.tolist(), nv)
+    return got
+
+
+class CRUScanFn(torch.autograd.Function):
+    """The Kalman recurrence of a CRU layer (masked update, coefficient softmax, basis mix, matrix exponential, prior mean and covariance
+    diagonals over all T time points) as ONE launch; backward = TWO (immtsf_cru_forward / _backward, csrc/cru.hip).  The posterior
+    covariances are returned for their readers but carry no gradient (forecasting() never reads the variance decoder); the times and
+    the validity flags are data.  fp32 in either precision mode."""
+
+    @staticmethod
+    def forward(ctx, y, y_var, valid, t, bandwidth, *params):
+        lib = _lib.load()
+        y, y_var, valid, t = _c(y), _c(y_var), _c(valid), _c(t)
+        params = tuple(_c(q) for q in params)
+        _need_gpu(y, y_var, valid, t, *params)
+        B, T, lod = y.shape
+        lsd, K = 2 * lod, params[0].shape[0]
+        pm = torch.empty(B, T, lsd, dtype=torch.float32, device=y.device)
+        cov = torch.empty(3, B, T, lod, dtype=torch.float32, device=y.device)
+        if B > 0:
+            check(lib.immtsf_cru_forward(B, T, lsd, K, bandwidth, ptr(y), ptr(y_var), ptr(valid), ptr(t), *(ptr(q) for q in params), ptr(pm),
+                                         ptr(cov[0]), ptr(cov[1]), ptr(cov[2]), stream_ptr()), "cru_forward")
+        ctx.dims = (B, T, lsd, K, bandwidth)
+        ctx.shapes = [tuple(q.shape) for q in params]
+        ctx.save_for_backward(y, y_var, valid, t, pm, cov, *params)
+        cu, cl, cs = cov[0], cov[1], cov[2]
+        ctx.mark_non_differentiable(cu, cl, cs)
+        return pm, cu, cl, cs
+
+    @staticmethod
+    def backward(ctx, dpm, *_):
+        lib = _lib.load()
+        y, y_var, valid, t, pm, cov = ctx.saved_tensors[:6]
+        params = ctx.saved_tensors[6:]
+        B, T, lsd, K, bw = ctx.dims
+        offs, nv = _cru_layout(lsd, K, bw)
+        flat = torch.empty(nv, dtype=torch.float32, device=y.device)      # every entry is written: no zero fill
+        dy = torch.empty(2, B, T, lsd // 2, dtype=torch.float32, device=y.device)
+        ws = _bytes(lib.immtsf_cru_workspace_bytes(B, T, lsd, K, bw), y.device)
+        check(lib.immtsf_cru_backward(B, T, lsd, K, bw, ptr(y), ptr(y_var), ptr(valid), ptr(t), *(ptr(q) for q in params), ptr(pm), ptr(cov[0]),
+                                      ptr(cov[1]), ptr(cov[2]), ptr(dpm.contiguous()), ptr(dy[0]), ptr(dy[1]), ptr(flat), ptr(ws), ws.numel(),
+                                      stream_ptr()), "cru_backward")
+        rets = []
+        for o, shape, need in zip(offs, ctx.shapes, ctx.needs_input_grad[5:]):
+            numel = 1
+            for s in shape:
+                numel *= s
+            rets.append(flat[o:o + numel].view(shape) if need else None)
+        return (dy[0] if ctx.needs_input_grad[0] else None, dy[1] if ctx.needs_input_grad[1] else None, None, None, None) + tuple(rets)
+
+
+def cru_scan(y, y_var, valid, t, bandwidth, tm11, tm12, tm21, tm22, coef_w, coef_b, trans_var, icu, icl):
+    """y, y_var (B, T, lod) latent observations and variances, valid (B, T) bool / uint8, t (B, T) time stamps; tm** (K, E) the flat banded
+    bases, coef_w (K, 2 lod), coef_b (K), trans_var (2 lod values) / icu / icl (lod values) the ACTIVATED variances -> post_mean (B, T, 2 lod)
+    and the posterior covariance vectors cu, cl, cs (B, T, lod) of the continuous CRU cell.  Gradients reach y, y_var and the parameters."""
+    B, T, lod = y.shape
+    lsd, K = 2 * lod, tm11.shape[0]
+    if valid.dtype == torch.bool:
+        valid = valid.view(torch.uint8)
+    if B < 1 or not cru_supported(lsd, K, bandwidth, T) or B * T * lsd >= 1 << 31:
+        raise _lib.ImmtsfError(f"cru_scan: shapes outside the fused kernel (B {B}, T {T}, lsd {lsd}, num_basis {K}, bandwidth {bandwidth})")
+    E = _cru_layout(lsd, K, int(bandwidth))[0][1] // K
+    want = [(K, E)] * 4 + [(K, lsd), (K,), lsd, lod, lod]
+    params = (tm11, tm12, tm21, tm22, coef_w, coef_b, trans_var, icu, icl)
+    if tuple(y_var.shape) != (B, T, lod) or tuple(valid.shape) != (B, T) or tuple(t.shape) != (B, T) or valid.dtype != torch.uint8 or \
+            any(q.dtype != torch.float32 for q in (y, y_var, t) + params) or \
+            any((q.numel() != w) if isinstance(w, int) else (tuple(q.shape) != w) for q, w in zip(params, want)):
+        raise _lib.ImmtsfError("cru_scan: the tensors are not the fp32 tensors of these dimensions")
+    return CRUScanFn.apply(y, y_var, valid, t, int(bandwidth), *params)

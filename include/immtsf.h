@@ -640,6 +640,34 @@ int immtsf_timemixer_backward(int32_t B, int32_t L, int32_t C, int32_t S, int32_
                               const float* const* params, const float* dY, float* grads, float p_drop, uint64_t seed, uint64_t site,
                               const uint64_t* seed_step_dev, void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
 
+/* ---- CRU backbone (added within ABI 7: new functions only; csrc/cru.hip): the Kalman recurrence of reference lib/cru_components/CRULayer.py:42-109
+ * over the continuous CRUCell (CRUCell.py:277-312, :437-500) with a single Linear + softmax coefficient net, as ONE launch forward and TWO
+ * backward.  All fp32.  lsd = latent state dimension (even), lod = lsd / 2, K = num_basis, E = entries of a (lod x lod) band of
+ * `bandwidth` (row-major order of the band).  Inputs: y, y_var (B, T, lod) the encoder's latent observations and their variances; valid
+ * (B, T) bytes, non-zero = observed; t (B, T) time stamps (differences of any sign, zero included); tm11 / tm12 / tm21 / tm22 (K, E) the
+ * flat banded bases; coef_w (K, lsd), coef_b (K); trans_var (lsd) = the ACTIVATED transition noise; icu, icl (lod) = the ACTIVATED initial
+ * covariance (the initial mean and side covariance are zero).  Outputs: post_mean (B, T, lsd), post_cu / post_cl / post_cs (B, T, lod).
+ * The predict after the last step is not computed.  Per step the kernel forms exp(A dt) and int_0^dt exp(A s) Q exp(A^T s) ds by Taylor
+ * series of degree 8 at ||A dt||_1 / 2^s <= 1/2 and s squarings (s chosen per batch element and step from the norm, at most 16).
+ * backward: d_post_mean (B, T, lsd) is the only cotangent (the covariances' is taken as zero); OVERWRITES dy, dy_var (B, T, lod) and
+ * `grads`, one flat buffer laid out [tm11 | tm12 | tm21 | tm22 | coef_w | coef_b | trans_var | icu | icl] (..._grad_layout writes the nine
+ * float offsets and returns the length, -1 for unsupported dimensions).  Times and validity take no gradient.  The sums over B run in
+ * index order over per-element slabs in `workspace`: no atomics, the same inputs give the same bits.
+ * ..._supported: lsd even, 2 <= lsd <= 32, 1 <= num_basis <= 256, 0 <= bandwidth <= lod, 1 <= T <= 2^20; the compute calls also need
+ * B T lsd < 2^31.  Otherwise 0 / IMMTSF_EUNSUPPORTED.  ..._workspace_bytes: the backward's workspace (host arithmetic; 0 for bad dimensions). */
+int immtsf_cru_supported(int32_t lsd, int32_t num_basis, int32_t bandwidth, int32_t T);
+int32_t immtsf_cru_grad_layout(int32_t lsd, int32_t num_basis, int32_t bandwidth, int32_t* offsets, int32_t n_offsets);
+size_t immtsf_cru_workspace_bytes(int32_t B, int32_t T, int32_t lsd, int32_t num_basis, int32_t bandwidth);
+int immtsf_cru_forward(int32_t B, int32_t T, int32_t lsd, int32_t num_basis, int32_t bandwidth, const float* y, const float* y_var,
+                       const uint8_t* valid, const float* t, const float* tm11, const float* tm12, const float* tm21, const float* tm22,
+                       const float* coef_w, const float* coef_b, const float* trans_var, const float* icu, const float* icl, float* post_mean,
+                       float* post_cu, float* post_cl, float* post_cs, immtsf_stream_t stream);
+int immtsf_cru_backward(int32_t B, int32_t T, int32_t lsd, int32_t num_basis, int32_t bandwidth, const float* y, const float* y_var,
+                        const uint8_t* valid, const float* t, const float* tm11, const float* tm12, const float* tm21, const float* tm22,
+                        const float* coef_w, const float* coef_b, const float* trans_var, const float* icu, const float* icl,
+                        const float* post_mean, const float* post_cu, const float* post_cl, const float* post_cs, const float* d_post_mean,
+                        float* dy, float* dy_var, float* grads, void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.
