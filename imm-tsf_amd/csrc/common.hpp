@@ -191,5 +191,10 @@ enum : uint64_t {
     SITE_XADD_ATTN = 4,  // fusions/MMF_XAttn_Add.py:42-47
     SITE_XADD_OUT = 5,   // fusions/MMF_XAttn_Add.py:95
     SITE_GR_OUT = 6,     // fusions/MMF_GR_Add.py:51
-    SITE_LAYER_BASE = 16 // layers/* dropout sites: SITE_LAYER_BASE + caller-chosen id
+    SITE_LAYER_BASE = 16, // layers/* dropout sites: SITE_LAYER_BASE + caller-chosen id
+    // TimeLLM's frozen GPT-2 body (csrc/gpt2.hip), three sites per layer l behind the embedding dropout
+    SITE_GPT2_EMBD = 1 << 16,          // transformers GPT2Model.drop; index (b*S+s)*d+e
+    SITE_GPT2_ATTN = (1 << 16) + 1,    // + 3*l: GPT2Attention.attn_dropout; index ((b*H+h)*S+i)*1024+j
+    SITE_GPT2_RESID1 = (1 << 16) + 2,  // + 3*l: GPT2Attention.resid_dropout; index (b*S+s)*d+e
+    SITE_GPT2_RESID2 = (1 << 16) + 3   // + 3*l: GPT2MLP.dropout; index (b*S+s)*d+e
 };

@@ -177,6 +177,19 @@ _PROTOS = {
     "immtsf_cru_forward": (C.c_int, [C.c_int32] * 5 + [c_f32p, c_f32p, c_u8p, c_f32p] + [c_f32p] * 9 + [c_f32p] * 4 + [c_stream]),
     "immtsf_cru_backward": (C.c_int, [C.c_int32] * 5 + [c_f32p, c_f32p, c_u8p, c_f32p] + [c_f32p] * 9 + [c_f32p] * 5 + [c_f32p] * 3 +
                             [C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_gpt2_supported": (C.c_int, [C.c_int32] * 4),
+    "immtsf_gpt2_gemm": (C.c_int, [C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_int32, c_f32p, C.c_void_p, C.c_int32, c_f32p, C.c_int32, c_f32p,
+                                   C.c_int32, C.c_int32, C.c_int32, c_stream]),
+    "immtsf_gpt2_embed": (C.c_int, [c_f32p, c_f32p, c_f32p] + [C.c_int32] * 4 + [C.c_float, C.c_uint64, C.c_uint64, c_f32p, c_stream]),
+    "immtsf_gpt2_layernorm": (C.c_int, [c_f32p] + [C.c_int32] * 4 + [c_f32p, c_f32p, C.c_float, c_f32p, C.c_void_p, c_f32p, c_f32p, c_stream]),
+    "immtsf_gpt2_layernorm_backward": (C.c_int, [c_f32p] * 6 + [C.c_int64, C.c_int32, c_f32p, c_stream]),
+    "immtsf_gpt2_residual": (C.c_int, [c_f32p] + [C.c_int32] * 7 + [c_f32p, C.c_float, C.c_uint64, C.c_uint64, c_f32p, c_stream]),
+    "immtsf_gpt2_gelu": (C.c_int, [c_f32p, C.c_uint64, c_f32p, C.c_void_p, c_stream]),
+    "immtsf_gpt2_gelu_backward": (C.c_int, [c_f32p, c_f32p, C.c_uint64, c_f32p, c_stream]),
+    "immtsf_gpt2_attention_forward": (C.c_int, [c_f32p, C.c_int32, c_f32p, c_f32p] + [C.c_int32] * 5 + [C.c_float, C.c_float, C.c_uint64,
+                                                C.c_uint64, c_f32p, C.c_void_p, c_f32p, c_stream]),
+    "immtsf_gpt2_attention_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, c_f32p, C.c_int32, c_f32p, c_f32p, c_f32p] + [C.c_int32] * 4 +
+                                       [C.c_float, C.c_float, C.c_uint64, C.c_uint64, c_f32p, c_f32p, c_f32p, C.c_int32, c_stream]),
     "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,

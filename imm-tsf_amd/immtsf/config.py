@@ -138,3 +138,7 @@ informer_fused = os.environ.get("IMMTSF_INFORMER_FUSED", "1") != "0"
 # single Linear + softmax coefficient net and immtsf_cru_supported allows; IMMTSF_CRU_FUSED=0: the composed path (a Python loop over the
 # time points around torch.matrix_exp) -- the cross-check.  The kernels are fp32 in either precision mode
 cru_fused = os.environ.get("IMMTSF_CRU_FUSED", "1") != "0"
+# TimeLLM's frozen GPT-2 body on csrc/gpt2.hip + the GEMM family (immtsf.ops.gpt2_body: causal attention with a prefix, the last block and
+# the whole backward over the reprogrammed patch rows only, bf16 weight images in bf16 mode) wherever gpt2_body_supported allows;
+# IMMTSF_TIMELLM_FUSED=0: transformers' GPT2Model on stock PyTorch in fp32 -- the cross-check.  Follows config.precision
+timellm_fused = os.environ.get("IMMTSF_TIMELLM_FUSED", "1") != "0"

@@ -3083,3 +3083,211 @@ def cru_scan(y, y_var, valid, t, bandwidth, tm11, tm12, tm21, tm22, coef_w, coef
             any((q.numel() != w) if isinstance(w, int) else (tuple(q.shape) != w) for q, w in zip(params, want)):
         raise _lib.ImmtsfError("cru_scan: the tensors are not the fp32 tensors of these dimensions")
     return CRUScanFn.apply(y, y_var, valid, t, int(bandwidth), *params)
+
+
+# ------------------------------------------------------------------------------------------------ TimeLLM's frozen GPT-2 body
+GPT2_SITE_EMBD = 65536           # include/immtsf.h IMMTSF_SITE_GPT2_*
+
+
+def gpt2_sites(layer):
+    """(attention, first residual, second residual) dropout sites of block `layer`; the embedding dropout is GPT2_SITE_EMBD"""
+    return 65537 + 3 * layer, 65538 + 3 * layer, 65539 + 3 * layer
+
+
+def _gpt2_inner(cfg):
+    return cfg.n_inner if cfg.n_inner is not None else 4 * cfg.n_embd
+
+
+def gpt2_body_supported(llm_model, S_p, S_t):
+    """the limits of gpt2_body: a transformers GPT2Model with head_dim 64, gelu_new, scaled attention weights, neither the inverse-layer
+    scale nor the reordered up-cast attention, no cross attention, fp32 parameters, S = S_p + S_t <= n_positions and <= 1024"""
+    from transformers import GPT2Model
+    if not isinstance(llm_model, GPT2Model) or S_p < 0 or S_t < 1:
+        return False
+    cfg = llm_model.config
+    d, H = int(cfg.n_embd), int(cfg.n_head)
+    if (cfg.activation_function != "gelu_new" or not cfg.scale_attn_weights or cfg.scale_attn_by_inverse_layer_idx or
+            cfg.reorder_and_upcast_attn or getattr(cfg, "add_cross_attention", False) or len(llm_model.h) < 1):
+        return False
+    if d % 8 or _gpt2_inner(cfg) % 8 or any(p.dtype != torch.float32 for p in llm_model.parameters()):
+        return False
+    return bool(_lib.load().immtsf_gpt2_supported(d, H, int(S_p + S_t), int(cfg.n_positions)))
+
+
+def _gpt2_w16(model, W):
+    """bf16 image of a frozen Conv1D weight, same (in, out) layout, cached on the model and keyed by the parameter's storage address and
+    version: load_state_dict(), .to() or any in-place write makes a new one"""
+    cache = model.__dict__.setdefault("_immtsf_gpt2_w16", {})
+    key = (W.data_ptr(), W._version, tuple(W.shape))
+    hit = cache.get(id(W))
+    if hit is None or hit[0] != key:
+        h = torch.empty(W.shape, dtype=torch.bfloat16, device=W.device)
+        check(_lib.load().immtsf_f32_to_bf16(ptr(W.detach().contiguous()), ptr(h), W.numel(), stream_ptr()), "f32_to_bf16")
+        hit = cache[id(W)] = (key, h)
+    return hit[1]
+
+
+class GPT2BodyFn(torch.autograd.Function):
+    """transformers' GPT2Model(inputs_embeds=cat([prefix, tail], 1)).last_hidden_state[:, -S_t:] on csrc/gpt2.hip + the GEMM family.  The
+    body is frozen and only `tail` takes a gradient; attention is causal without a padding mask, so no prefix row depends on a tail row
+    and the backward runs over the B S_t tail rows alone (exactly).  The last block computes queries, projections and the MLP for the tail
+    rows only.  Saved per block: the c_attn output (K and V of all rows) and, for the tail rows, the block inputs, LayerNorm statistics,
+    q, attention output, log-sum-exp and the MLP pre-activation."""
+
+    @staticmethod
+    def forward(ctx, tail, prefix, model, p_drops, precision, seed, need_bwd):
+        lib = _lib.load()
+        st = stream_ptr()
+        cfg = model.config
+        B, S_t, d = tail.shape
+        S_p = 0 if prefix is None else prefix.shape[1]
+        S, H, inner, L = S_p + S_t, int(cfg.n_head), _gpt2_inner(cfg), len(model.h)
+        dev = tail.device
+        bf = precision == 1
+        p_e, p_a, p_r = p_drops
+        eps = float(cfg.layer_norm_epsilon)
+        scale = 1.0 / float(d // H) ** 0.5
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
+        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)      # noqa: E731
+        adr = lambda t, off=0: None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
+
+        def mm(a32, a16, W, bias, M, N, K, out, ldc, w_off=0, c_off=0):
+            """out[:, c_off:c_off+N] = a (M, K) W[:, w_off:w_off+N] + bias[w_off:...]; W is the Conv1D weight (in, out)"""
+            ldb = W.shape[1]
+            w16 = adr(_gpt2_w16(model, W), w_off) if bf else None
+            check(lib.immtsf_gpt2_gemm(1, precision, ptr(a32), ptr(a16), K, adr(W, w_off), w16, ldb, adr(out, c_off), ldc, adr(bias, w_off),
+                                       M, N, K, st), "gpt2_gemm")
+
+        def ln(x, rows_per_b, s_from, norm, stats):
+            n = B * (rows_per_b - s_from)
+            y32, y16 = (None, b16(n, d)) if bf else (f32(n, d), None)
+            mean, rstd = (f32(n), f32(n)) if stats else (None, None)
+            check(lib.immtsf_gpt2_layernorm(ptr(x), B, rows_per_b, s_from, d, ptr(norm.weight), ptr(norm.bias), eps, ptr(y32), ptr(y16),
+                                            ptr(mean), ptr(rstd), st), "gpt2_layernorm")
+            return y32, y16, mean, rstd
+
+        def tl(t, rows_per_b):        # the tail rows of a (B rows_per_b, ...) tensor, compact
+            if rows_per_b == S_t:
+                return t
+            return t.view(B, rows_per_b, -1)[:, rows_per_b - S_t:].contiguous().view(B * S_t, -1)
+
+        x = f32(B * S, d)
+        check(lib.immtsf_gpt2_embed(ptr(prefix), ptr(tail), ptr(model.wpe.weight), B, S_p, S_t, d, p_e, seed, GPT2_SITE_EMBD, ptr(x), st),
+              "gpt2_embed")
+        saved = []
+        for li, blk in enumerate(model.h):
+            qf = S_p if li == L - 1 else 0
+            Sq = S - qf
+            s_attn, s_r1, s_r2 = gpt2_sites(li)
+            ca, cp, fc, mp = blk.attn.c_attn, blk.attn.c_proj, blk.mlp.c_fc, blk.mlp.c_proj
+            h32, h16, mean1, rstd1 = ln(x, S, 0, blk.ln_1, need_bwd)
+            qkv = f32(B * S, 3 * d)
+            if qf == 0:
+                mm(h32, h16, ca.weight, ca.bias, B * S, 3 * d, d, qkv, 3 * d)
+                q, ldq = qkv, 3 * d
+            else:           # the last block: K and V of all rows, queries of the tail rows
+                mm(h32, h16, ca.weight, ca.bias, B * S, 2 * d, d, qkv, 3 * d, w_off=d, c_off=d)
+                t32, t16, _, _ = ln(x, S, qf, blk.ln_1, False)
+                q, ldq = f32(B * Sq, d), d
+                mm(t32, t16, ca.weight, ca.bias, B * Sq, d, d, q, d)
+            ao32 = f32(B * Sq, d) if (need_bwd or not bf) else None
+            ao16 = b16(B * Sq, d) if bf else None
+            lse = f32(B, H, Sq) if need_bwd else None
+            check(lib.immtsf_gpt2_attention_forward(ptr(q), ldq, adr(qkv, d), adr(qkv, 2 * d), 3 * d, B, S, H, qf, scale, p_a, seed, s_attn,
+                                                    ptr(ao32), ptr(ao16), ptr(lse), st), "gpt2_attention_forward")
+            pr = f32(B * Sq, d)
+            mm(ao32, ao16, cp.weight, cp.bias, B * Sq, d, d, pr, d)
+            x1 = f32(B * Sq, d)
+            check(lib.immtsf_gpt2_residual(ptr(x), B, S, qf, Sq, S, qf, d, ptr(pr), p_r, seed, s_r1, ptr(x1), st), "gpt2_residual")
+            g32, g16, mean2, rstd2 = ln(x1, Sq, 0, blk.ln_2, need_bwd)
+            pre = f32(B * Sq, inner)
+            mm(g32, g16, fc.weight, fc.bias, B * Sq, inner, d, pre, inner)
+            a32, a16 = (None, b16(B * Sq, inner)) if bf else (f32(B * Sq, inner), None)
+            check(lib.immtsf_gpt2_gelu(ptr(pre), pre.numel(), ptr(a32), ptr(a16), st), "gpt2_gelu")
+            mo = f32(B * Sq, d)
+            mm(a32, a16, mp.weight, mp.bias, B * Sq, d, inner, mo, d)
+            x2 = f32(B * Sq, d)
+            check(lib.immtsf_gpt2_residual(ptr(x1), B, Sq, 0, Sq, S, qf, d, ptr(mo), p_r, seed, s_r2, ptr(x2), st), "gpt2_residual")
+            if need_bwd:
+                q_t = q if qf else qkv.view(B, S, 3 * d)[:, S_p:, :d].contiguous().view(B * S_t, d)
+                lse_t = lse if Sq == S_t else lse[:, :, S_p:].contiguous()
+                saved.append((tl(x, S), tl(mean1.view(-1, 1), S).view(-1), tl(rstd1.view(-1, 1), S).view(-1), q_t, qkv, tl(ao32, Sq), lse_t,
+                              tl(x1, Sq), tl(mean2.view(-1, 1), Sq).view(-1), tl(rstd2.view(-1, 1), Sq).view(-1), tl(pre, Sq)))
+            x = x2
+        out = f32(B, S_t, d)
+        mean_f, rstd_f = (f32(B * S_t), f32(B * S_t)) if need_bwd else (None, None)
+        check(lib.immtsf_gpt2_layernorm(ptr(x), B, S_t, 0, d, ptr(model.ln_f.weight), ptr(model.ln_f.bias), eps, ptr(out), None, ptr(mean_f),
+                                        ptr(rstd_f), st), "gpt2_layernorm")
+        if need_bwd:
+            ctx.saved, ctx.final = saved, (x, mean_f, rstd_f)
+            ctx.model, ctx.dims, ctx.drops, ctx.seed, ctx.precision = model, (B, S_p, S_t, d, H, inner), p_drops, seed, precision
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        st = stream_ptr()
+        model = ctx.model
+        B, S_p, S_t, d, H, inner = ctx.dims
+        S, M = S_p + S_t, B * S_t
+        p_e, p_a, p_r = ctx.drops
+        seed, prec = ctx.seed, ctx.precision
+        dev = dout.device
+        scale = 1.0 / float(d // H) ** 0.5
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
+        adr = lambda t, off=0: C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
+
+        def mm_t(g, W, N, K):          # g (M, K) W^T: W is the Conv1D weight (in = N, out = K), read as it is stored
+            o = f32(M, N)
+            check(lib.immtsf_gpt2_gemm(0, prec, ptr(g), None, K, ptr(W), None, K, ptr(o), N, None, M, N, K, st), "gpt2_gemm (backward)")
+            return o
+
+        def ln_bwd(g, x, mean, rstd, norm, resid):
+            o = f32(M, d)
+            check(lib.immtsf_gpt2_layernorm_backward(ptr(g), ptr(x), ptr(mean), ptr(rstd), ptr(norm.weight), ptr(resid), M, d, ptr(o), st),
+                  "gpt2_layernorm_backward")
+            return o
+
+        def undrop(g, p, site):        # the dropout's backward: the same mask, redrawn
+            if p <= 0.0:
+                return g
+            o = f32(M, d)
+            check(lib.immtsf_gpt2_residual(None, B, 0, 0, S_t, S, S_p, d, ptr(g), p, seed, site, ptr(o), st), "gpt2_residual (backward)")
+            return o
+
+        xf, mean_f, rstd_f = ctx.final
+        dx = ln_bwd(dout.contiguous().view(M, d), xf, mean_f, rstd_f, model.ln_f, None)
+        for li in reversed(range(len(model.h))):
+            blk = model.h[li]
+            x_t, mean1, rstd1, q_t, qkv, ao_t, lse_t, x1_t, mean2, rstd2, pre_t = ctx.saved[li]
+            s_attn, s_r1, s_r2 = gpt2_sites(li)
+            dact = mm_t(undrop(dx, p_r, s_r2), blk.mlp.c_proj.weight, inner, d)
+            dpre = f32(M, inner)
+            check(lib.immtsf_gpt2_gelu_backward(ptr(pre_t), ptr(dact), dpre.numel(), ptr(dpre), st), "gpt2_gelu_backward")
+            dx1 = ln_bwd(mm_t(dpre, blk.mlp.c_fc.weight, d, inner), x1_t, mean2, rstd2, blk.ln_2, dx)
+            dao = mm_t(undrop(dx1, p_r, s_r1), blk.attn.c_proj.weight, d, d)
+            dqkv = f32(M, 3 * d)
+            check(lib.immtsf_gpt2_attention_backward(ptr(q_t), d, adr(qkv, d), adr(qkv, 2 * d), 3 * d, ptr(dao), ptr(ao_t), ptr(lse_t), B, S, H,
+                                                     S_p, scale, p_a, seed, s_attn, ptr(dqkv), adr(dqkv, d), adr(dqkv, 2 * d), 3 * d, st),
+                  "gpt2_attention_backward")
+            dx = ln_bwd(mm_t(dqkv, blk.attn.c_attn.weight, d, 3 * d), x_t, mean1, rstd1, blk.ln_1, dx1)
+        dtail = undrop(dx, p_e, GPT2_SITE_EMBD)
+        return dtail.view(B, S_t, d), None, None, None, None, None, None
+
+
+def gpt2_body(llm_model, prefix_embeds, tail_embeds, training, precision=None, seed=None):
+    """hidden_tail (B, S_t, d) = ln_f output of the last S_t rows of the frozen GPT-2 body over [prefix_embeds | tail_embeds].  Only
+    tail_embeds takes a gradient (prefix_embeds may require one; it gets none).  training: the body's three dropouts (embd / attn / resid
+    pdrop of its config) are drawn from immtsf's generator -- ops.dropout_keep_mask(seed, site, ...) reproduces them (GPT2_SITE_EMBD,
+    gpt2_sites(layer)); seed: the Philox key, config.next_seed() by default.  Outside gpt2_body_supported this raises: callers check."""
+    tail = _c(tail_embeds.float())
+    prefix = None if prefix_embeds is None or prefix_embeds.shape[1] == 0 else _c(prefix_embeds.detach().float())
+    _need_gpu(tail, prefix)
+    if not gpt2_body_supported(llm_model, 0 if prefix is None else prefix.shape[1], tail.shape[1]):
+        raise _lib.ImmtsfError("gpt2_body: this body / sequence length is outside gpt2_body_supported")
+    cfg = llm_model.config
+    drops = (float(cfg.embd_pdrop), float(cfg.attn_pdrop), float(cfg.resid_pdrop)) if training else (0.0, 0.0, 0.0)
+    if seed is None:
+        seed = config.next_seed() if any(p > 0.0 for p in drops) else 0
+    need_bwd = torch.is_grad_enabled() and tail.requires_grad
+    return GPT2BodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), int(seed) & 0xFFFFFFFFFFFFFFFF, need_bwd)

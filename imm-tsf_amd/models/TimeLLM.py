@@ -8,7 +8,9 @@ against the reference run the same way (its loader patched to the same stand-ins
 tests/golden/model_timellm.npz, test_gpu_fusion.py::test_timellm_forecasting_vs_reference_golden); parity with PRETRAINED
 weights stays unpinned.  The sub-layers on the
 hot-path scope -- PatchEmbedding on values and on timestamps, ReprogrammingLayer projections, FlattenHead -- use the
-HIP GEMM."""
+HIP GEMM.  A GPT-2 body inside immtsf.ops.gpt2_body_supported runs on immtsf.ops.gpt2_body (csrc/gpt2.hip, DESIGN 4l: the frozen body
+with its backward over the patch rows only; config.timellm_fused / IMMTSF_TIMELLM_FUSED=0 turns it off, `fused_body_calls` counts);
+`self.llm_model` stays the transformers model, and every other body runs the stock call."""
 from math import sqrt
 
 import torch
@@ -16,7 +18,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from immtsf import config
-from immtsf.ops import linear, shared_kv_attention
+from immtsf.ops import gpt2_body, gpt2_body_supported, linear, shared_kv_attention
 from layers.Embed import PatchEmbedding
 from models._common import masked_instance_norm
 
@@ -109,6 +111,7 @@ class TimeLLM(nn.Module):
         self.reprogramming_layer = ReprogrammingLayer(configs.d_model, configs.n_heads, d_llm=self.d_llm)
         self.output_projection = FlattenHead(self.head_nf, self.pred_len, head_dropout=configs.dropout)
         self.zeros_pad = torch.zeros(configs.batch_size, max(self.input_len, self.pred_len), self.C, device=configs.device)
+        self.fused_body_calls = 0          # forecasting() calls whose frozen body ran on immtsf.ops.gpt2_body
 
     def _get_model_and_tokenizer(self, model_name, layers, offline):
         from transformers import BertConfig, BertModel, BertTokenizer, GPT2Config, GPT2Model, GPT2Tokenizer
@@ -181,9 +184,14 @@ class TimeLLM(nn.Module):
         src = linear(self.word_embeddings.permute(1, 0), self.mapping_layer.weight, self.mapping_layer.bias).permute(1, 0)
         rep = self.reprogramming_layer(ts_out + tp_out, src, src)
         rep = rep.view(B, N, self.patch_nums, self.d_llm).permute(0, 2, 1, 3).reshape(B, -1, self.d_llm)
-        hidden = self.llm_model(inputs_embeds=torch.cat([prompt_embeds, rep], dim=1)).last_hidden_state
         total = self.patch_nums * n_vars
-        dec = hidden[:, -total:, :self.d_ff].view(B, self.patch_nums, n_vars, self.d_ff)
+        if config.timellm_fused and rep.is_cuda and gpt2_body_supported(self.llm_model, prompt_embeds.size(1), total):
+            # the frozen body on HIP: backward over the patch rows only (m.train() puts the body in train mode in the reference too)
+            hidden_tail = gpt2_body(self.llm_model, prompt_embeds, rep, self.llm_model.training)
+            self.fused_body_calls += 1
+        else:
+            hidden_tail = self.llm_model(inputs_embeds=torch.cat([prompt_embeds, rep], dim=1)).last_hidden_state[:, -total:]
+        dec = hidden_tail[..., :self.d_ff].view(B, self.patch_nums, n_vars, self.d_ff)
         dec = dec.permute(0, 2, 3, 1).reshape(B * n_vars, self.d_ff, self.patch_nums)
         out = self.output_projection(dec).view(B, n_vars, self.pred_len).permute(0, 2, 1)
         if self.use_norm:

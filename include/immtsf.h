@@ -668,6 +668,53 @@ int immtsf_cru_backward(int32_t B, int32_t T, int32_t lsd, int32_t num_basis, in
                         const float* post_mean, const float* post_cu, const float* post_cl, const float* post_cs, const float* d_post_mean,
                         float* dy, float* dy_var, float* grads, void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
 
+/* ---- TimeLLM's frozen GPT-2 body (added within ABI 7: new functions only; csrc/gpt2.hip): what immtsf.ops.gpt2_body composes with the GEMM
+ * family into transformers' GPT2Model(inputs_embeds=cat([prefix, tail], 1)) whose backward runs over the tail rows only.  Rows are (b, s),
+ * s < S = S_p + S_t; head_dim is 64, d = 64 H; all arithmetic fp32 (the *16 outputs are bf16 images for the bf16-in-memory GEMMs).
+ * ..._supported: d == 64 H, 1 <= S <= n_positions, S <= 1024.
+ * ..._gemm: C (M, N; pitch ldc) = op(A) op(B) + bias on the GEMM family with split-K off (one summation order: the same inputs give the
+ *   same bits).  layout 1: A (M, K) B (K, N), a Conv1D forward on the (in, out) weight as stored; layout 0: A (M, K) B (N, K)^T, its data
+ *   gradient on the same weight.  precision 1 with both bf16 images (A16, B16: same pitches) runs the bf16-in-memory kernels (A, B may then
+ *   be NULL); otherwise the fp32 operands are read.
+ * ..._embed: out (B, S, d) = dropout([prefix | tail] + wpe[0:S]) without the concatenated copy (prefix may be NULL when S_p == 0).
+ * ..._layernorm: the rows (b, s_from + t), t < S_in - s_from, of x (B, S_in, d) -> compact y32 and / or y16 (B (S_in - s_from), d), and the
+ *   rows' mean / rstd when given.  ..._layernorm_backward: dx = resid + LayerNorm'(dy) over `rows` compact rows (resid may be NULL), no
+ *   parameter gradients (the body is frozen).
+ * ..._residual: out (B, Sn, d) = xin[b, s_off + t] + dropout(y[b, t]), xin (B, S_in, d) or NULL (then out = dropout(y): the backward of the
+ *   dropout); the mask is that of row (b, q_from + t) of a (B, S, d) tensor.
+ * ..._gelu: gelu_new (the tanh form) of n elements; ..._gelu_backward: dpre = dact * gelu_new'(pre).
+ * ..._attention_forward: causal softmax(scale q k^T) v without a padding mask.  k, v: rows b S + j with pitch ldkv, head h at columns
+ *   64 h (the c_attn output as it is); q: the queries of positions q_from .. S-1, row b (S - q_from) + t with pitch ldq; out32 / out16
+ *   (B (S - q_from), 64 H) in the layout c_proj reads; lse (B, H, S - q_from) = log-sum-exp of the scaled scores (may be NULL).  Dropout on
+ *   the probabilities, index ((b H + h) S + i) 1024 + j for query position i and key j.
+ * ..._attention_backward: for the queries q_from .. S-1 (q, dout, out, lse in the forward's layouts): dq against all keys, dk / dv of the
+ *   keys q_from .. S-1 from those queries (exact when no gradient is wanted for earlier rows: causality), rows b (S - q_from) + t with
+ *   pitch ldd.  Probabilities are recomputed from lse and the mask is redrawn; one writer per element, fixed summation order, no atomics. */
+#define IMMTSF_SITE_GPT2_EMBD 65536   /* index (b*S+s)*d+e */
+#define IMMTSF_SITE_GPT2_ATTN 65537   /* + 3*layer; index ((b*H+h)*S+i)*1024+j */
+#define IMMTSF_SITE_GPT2_RESID1 65538 /* + 3*layer; index (b*S+s)*d+e */
+#define IMMTSF_SITE_GPT2_RESID2 65539 /* + 3*layer; index (b*S+s)*d+e */
+int immtsf_gpt2_supported(int32_t d, int32_t H, int32_t S, int32_t n_positions);
+int immtsf_gpt2_gemm(int32_t layout, int32_t precision, const float* A, const void* A16, int32_t lda, const float* B, const void* B16,
+                     int32_t ldb, float* C, int32_t ldc, const float* bias, int32_t M, int32_t N, int32_t K, immtsf_stream_t stream);
+int immtsf_gpt2_embed(const float* prefix, const float* tail, const float* wpe, int32_t B, int32_t S_p, int32_t S_t, int32_t d, float p_drop,
+                      uint64_t seed, uint64_t site, float* out, immtsf_stream_t stream);
+int immtsf_gpt2_layernorm(const float* x, int32_t B, int32_t S_in, int32_t s_from, int32_t d, const float* gamma, const float* beta, float eps,
+                          float* y32, void* y16, float* mean, float* rstd, immtsf_stream_t stream);
+int immtsf_gpt2_layernorm_backward(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                                   const float* resid, int64_t rows, int32_t d, float* dx, immtsf_stream_t stream);
+int immtsf_gpt2_residual(const float* xin, int32_t B, int32_t S_in, int32_t s_off, int32_t Sn, int32_t S, int32_t q_from, int32_t d,
+                         const float* y, float p_drop, uint64_t seed, uint64_t site, float* out, immtsf_stream_t stream);
+int immtsf_gpt2_gelu(const float* pre, uint64_t n, float* out32, void* out16, immtsf_stream_t stream);
+int immtsf_gpt2_gelu_backward(const float* pre, const float* dact, uint64_t n, float* dpre, immtsf_stream_t stream);
+int immtsf_gpt2_attention_forward(const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, int32_t B, int32_t S, int32_t H,
+                                  int32_t q_from, float scale, float p_drop, uint64_t seed, uint64_t site, float* out32, void* out16,
+                                  float* lse, immtsf_stream_t stream);
+int immtsf_gpt2_attention_backward(const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, const float* dout,
+                                   const float* out, const float* lse, int32_t B, int32_t S, int32_t H, int32_t q_from, float scale,
+                                   float p_drop, uint64_t seed, uint64_t site, float* dq, float* dk, float* dv, int32_t ldd,
+                                   immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

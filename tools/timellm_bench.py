@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""TimeLLM's frozen GPT-2 body, fused (immtsf.ops.gpt2_body: csrc/gpt2.hip + the GEMM family, backward over the patch rows only) against
+IMMTSF_TIMELLM_FUSED=0 (transformers' GPT2Model on stock PyTorch, fp32, full autograd), at the shape of `bench.py --config cfg5`: B = 64
+windows, a random-init 6-layer GPT-2 (768 wide, 12 heads), input_len = pred_len = 32, C = 8, patches of 16 with stride 8 -- S_t = 32
+patch rows behind the prompt the model builds for the batch (its length is printed as S_p).  Two measurements per precision mode (fp32,
+bf16): the body alone (forward + backward to the patch rows) and the whole forecasting() + backward.  Eager only: the prompt is built on
+the host, so the step cannot be captured.  In ONE process, after warming both paths: `--passes` alternating passes of `--iters` steps
+each, host clock around a pass with a synchronise at its end.  Prints one JSON line per mode: milliseconds per step, best pass and all
+passes (their spread is the noise).
+
+usage: python tools/timellm_bench.py [--iters 5] [--passes 5] [--batch 64] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "imm-tsf_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+L, C, LAYERS = 32, 8, 6
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--passes", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from immtsf import config, ops
+    from models.TimeLLM import TimeLLM
+    dev = torch.device("cuda:0")
+    B = args.batch
+    torch.manual_seed(0)
+    m = TimeLLM(types.SimpleNamespace(
+        input_len=L, pred_len=L, use_norm=True, d_ff=32, ts_vocab_size=1000, input_token_len=16, stride=8, domain_des="synthetic", top_k=5,
+        C=C, llm_model_timellm="GPT2", llm_layers_timellm=LAYERS, dropout=0.1, d_model=16, n_heads=8, batch_size=B, device=str(dev),
+        immtsf_offline_llm=True)).to(dev).train()
+    m.word_embeddings = m.llm_model.get_input_embeddings().weight
+    g = torch.Generator().manual_seed(1)
+    mask = (torch.rand(B, L, C, generator=g) < 0.7).float().to(dev)
+    data = torch.randn(B, L, C, generator=g).to(dev) * mask
+    tp = (torch.sort(torch.rand(B, L, generator=g), 1).values * 0.5).to(dev)
+    tpp = torch.sort(torch.rand(B, L, generator=g), 1).values.to(dev)
+    up = torch.randn(B, L, C, generator=g).to(dev)
+    # the body's inputs as forecasting() forms them: the prompt's embeddings (frozen) and S_t reprogrammed patch rows
+    from models._common import masked_instance_norm
+    with torch.no_grad():
+        tokens = m.tokenizer(m._get_prompt(masked_instance_norm(data, mask)[0]), return_tensors="pt", padding=True, truncation=True,
+                             max_length=512).input_ids.to(dev)
+        prefix = m.llm_model.get_input_embeddings()(tokens)
+    S_p, S_t, d = prefix.shape[1], m.patch_nums * C, m.d_llm
+    tail = (0.02 * torch.randn(B, S_t, d, generator=g)).to(dev).requires_grad_(True)
+    up_b = torch.randn(B, S_t, d, generator=g).to(dev)
+
+    def body(fused):
+        tail.grad = None
+        if fused:
+            out = ops.gpt2_body(m.llm_model, prefix, tail, True)
+        else:
+            out = m.llm_model(inputs_embeds=torch.cat([prefix, tail], 1)).last_hidden_state[:, -S_t:]
+        (out * up_b).sum().backward()
+
+    def whole(fused):
+        config.timellm_fused = fused
+        m.zero_grad(set_to_none=True)
+        (m.forecasting(tpp, data, tp, mask) * up).sum().backward()
+
+    def timed(fn, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / n
+
+    lines = []
+    for prec in ("fp32", "bf16"):
+        config.precision = prec
+        line = {"tool": "timellm_bench", "precision": prec, "B": B, "layers": LAYERS, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
+                "passes": args.passes}
+        for what, fn in (("body", body), ("forecasting", whole)):
+            for fused in (True, False):
+                for _ in range(2):
+                    fn(fused)
+            t = {True: [], False: []}
+            for _ in range(args.passes):
+                for fused in (True, False):
+                    t[fused].append(timed(lambda: fn(fused), args.iters))
+            for fused, name in ((True, "fused"), (False, "stock")):
+                line[f"{what}_{name}_ms"] = round(min(t[fused]), 3)
+                line[f"{what}_{name}_ms_passes"] = [round(v, 3) for v in t[fused]]
+            line[f"{what}_speedup"] = round(min(t[False]) / min(t[True]), 2)
+        config.timellm_fused = True
+        print(json.dumps(line), flush=True)
+        lines.append(json.dumps(line))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
