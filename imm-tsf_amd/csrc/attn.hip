@@ -787,7 +787,7 @@ __device__ __forceinline__ void attn_short_bwd_body(const ShortDims& d, const fl
                 float acc = 0.f;
                 if (s < d.L) {
                     short_load(qkv + short_off(d, b, s, 2, h), ev, v);
-                    acc = short_dot(g, v) * dropout_scale(drop, site, row * d.L + s);
+                    acc = mul_rounded(short_dot(g, v), dropout_scale(drop, site, row * d.L + s));      // one value for dot and dp - dot
                 }
                 dp[s] = acc;
                 dot = fmaf(p[s], acc, dot);

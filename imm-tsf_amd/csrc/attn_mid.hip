@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void attn_mid_bwd_kernel(AmDims d, const float
             float dot = 0.f;
             for (int t = 0; t < S; ++t) dot = fmaf(Sc[l * AM_L + t], Ad[l * AM_L + t], dot);        // sum_t dA[t] x (P[t] x dropout[t])
             const float p = Pr[l * AM_L + s];
-            ds_mine[r] = d.scale * (Sc[l * AM_L + s] * Ad[l * AM_L + s] - p * dot);
+            ds_mine[r] = d.scale * (mul_rounded(Sc[l * AM_L + s], Ad[l * AM_L + s]) - p * dot);      // the product as `dot` summed it
         }
     }
     __syncthreads();

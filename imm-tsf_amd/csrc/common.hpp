@@ -26,6 +26,14 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// a * b rounded to float once, never fused into a following add or subtract.  For a softmax backward dS = P (dP - sum P dP) whose dP
+// is itself a product (dA x dropout scale): the sum takes the rounded product, so the difference must take it too -- a row that sees
+// one key (P = 1) then has dS exactly 0 instead of the product's rounding residue.
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 // ---- wave / block reductions ----------------------------------------------------------------------
 // Cross-lane steps without the LDS crossbar: __shfl_xor compiles to ds_bpermute_b32 (an LDS-pipeline round trip per step and
 // an address register); inside a row of 16 lanes the DPP modifiers of the VALU add / max do the exchange for free, and
