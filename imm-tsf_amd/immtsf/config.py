@@ -142,3 +142,8 @@ cru_fused = os.environ.get("IMMTSF_CRU_FUSED", "1") != "0"
 # the whole backward over the reprogrammed patch rows only, bf16 weight images in bf16 mode) wherever gpt2_body_supported allows;
 # IMMTSF_TIMELLM_FUSED=0: transformers' GPT2Model on stock PyTorch in fp32 -- the cross-check.  Follows config.precision
 timellm_fused = os.environ.get("IMMTSF_TIMELLM_FUSED", "1") != "0"
+# LatentODE's forecasting() as one HIP launch forward and two backward (csrc/latent_ode.hip) wherever the encoder is the ODE-RNN with
+# rec_layers = gen_layers = 1, one trajectory sample, and immtsf_latent_ode_supported allows; IMMTSF_LATENTODE_FUSED=0: the composed path
+# (the reference's loop over the observed points on torch ops, the step plan copied to the host once) -- the cross-check.  fp32 in
+# either precision mode
+latentode_fused = os.environ.get("IMMTSF_LATENTODE_FUSED", "1") != "0"

@@ -3291,3 +3291,77 @@ def gpt2_body(llm_model, prefix_embeds, tail_embeds, training, precision=None, s
         seed = config.next_seed() if any(p > 0.0 for p in drops) else 0
     need_bwd = torch.is_grad_enabled() and tail.requires_grad
     return GPT2BodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), int(seed) & 0xFFFFFFFFFFFFFFFF, need_bwd)
+
+
+# ------------------------------------------------------------------------------------------------ LatentODE backbone
+def _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents):
+    return _lib.LatentODEDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(units), int(gru_units), int(latents))
+
+
+def latent_ode_supported(B, L, Lp, C, rec_dims, units, gru_units, latents, call=False):
+    """the limits of the fused LatentODE kernels (immtsf_latent_ode_supported: rec_dims, latents <= 64, units, gru_units <= 128, C <= 64,
+    L, Lp <= 2^20, the weights and a tile's state within 160 KB of LDS), from the dims alone; call: also what a compute call needs
+    (B >= 1 and the saved state's index range, immtsf_latent_ode_workspace_bytes > 0)"""
+    import ctypes
+    d = _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents)
+    lib = _lib.load()
+    if not lib.immtsf_latent_ode_supported(ctypes.byref(d)):
+        return False
+    return bool(lib.immtsf_latent_ode_workspace_bytes(ctypes.byref(d)) > 0) if call else True
+
+
+class LatentODEFn(torch.autograd.Function):
+    """LatentODE's forecasting() (ODE-RNN encoder over the observed points, transform_z0, z0 = mu + eps |sigma|, the generative ODE over
+    the forecast times, the decoder) as ONE launch; backward = TWO (immtsf_latent_ode_forward / _backward, csrc/latent_ode.hip).  The
+    flat parameter buffer is the only input with a gradient.  fp32 in either precision mode."""
+
+    @staticmethod
+    def forward(ctx, data, mask, steps, step_len, tpp, flat, eps, widths):
+        import ctypes
+        lib = _lib.load()
+        data, mask, steps, step_len, tpp, flat, eps = (_c(t) for t in (data, mask, steps, step_len, tpp, flat, eps))
+        _need_gpu(data, mask, steps, step_len, tpp, flat, eps)
+        B, L, C = data.shape
+        Lp = tpp.shape[0]
+        R, U, G, Z = widths
+        d = _latent_ode_dims(B, L, Lp, C, R, U, G, Z)
+        out = torch.empty(B, Lp, C, dtype=torch.float32, device=data.device)
+        states = torch.empty(B, L + 1, 2 * R, dtype=torch.float32, device=data.device)
+        traj = torch.empty(B, Lp, Z, dtype=torch.float32, device=data.device)
+        check(lib.immtsf_latent_ode_forward(ctypes.byref(d), ptr(data), ptr(mask), ptr(steps), ptr(step_len), ptr(tpp), ptr(flat), ptr(eps),
+                                            ptr(out), ptr(states), ptr(traj), stream_ptr()), "latent_ode_forward")
+        ctx.dims = (B, L, Lp, C, R, U, G, Z)
+        ctx.save_for_backward(data, mask, steps, step_len, tpp, flat, eps, states, traj)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        import ctypes
+        lib = _lib.load()
+        data, mask, steps, step_len, tpp, flat, eps, states, traj = ctx.saved_tensors
+        d = _latent_ode_dims(*ctx.dims)
+        grads = torch.empty_like(flat)      # every entry is written: no zero fill
+        ws = _bytes(lib.immtsf_latent_ode_workspace_bytes(ctypes.byref(d)), data.device)
+        check(lib.immtsf_latent_ode_backward(ctypes.byref(d), ptr(data), ptr(mask), ptr(steps), ptr(step_len), ptr(tpp), ptr(flat), ptr(eps),
+                                             ptr(states), ptr(traj), ptr(dout.contiguous()), ptr(grads), ptr(ws), ws.numel(), stream_ptr()),
+              "latent_ode_backward")
+        return None, None, None, None, None, grads, None, None
+
+
+def latent_ode(data, mask, steps, step_len, tp_pred, flat_params, eps, widths):
+    """data, mask (B, L, C); steps (L) int32 / step_len (L): the step plan of the shared time axis (-1: Euler, n >= 1: n RK4 steps, 0:
+    none); tp_pred (Lp); flat_params: every parameter in state_dict order, flattened; eps (B, latents); widths = (rec_dims, units,
+    gru_units, latents) -> the forecast (B, Lp, C).  Gradients reach flat_params only."""
+    import ctypes
+    B, L, C = data.shape
+    Lp = tp_pred.shape[0]
+    R, U, G, Z = (int(w) for w in widths)
+    if not latent_ode_supported(B, L, Lp, C, R, U, G, Z, call=True):
+        raise _lib.ImmtsfError(f"latent_ode: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, C {C}, widths {(R, U, G, Z)})")
+    d = _latent_ode_dims(B, L, Lp, C, R, U, G, Z)
+    nv = int(_lib.load().immtsf_latent_ode_param_count(ctypes.byref(d)))
+    if tuple(mask.shape) != (B, L, C) or tuple(steps.shape) != (L,) or tuple(step_len.shape) != (L,) or tp_pred.dim() != 1 or \
+            tuple(eps.shape) != (B, Z) or flat_params.numel() != nv or steps.dtype != torch.int32 or \
+            any(q.dtype != torch.float32 for q in (data, mask, step_len, tp_pred, flat_params, eps)):
+        raise _lib.ImmtsfError("latent_ode: the tensors are not the fp32 tensors of these dimensions")
+    return LatentODEFn.apply(data, mask, steps, step_len, tp_pred, flat_params, eps, (R, U, G, Z))

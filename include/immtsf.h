@@ -56,9 +56,10 @@ typedef void* immtsf_stream_t;
 int immtsf_abi_version(void);
 /* sizeof of every struct of this ABI, in the order immtsf_fusion_cfg, immtsf_t2v_params, immtsf_recavg_params, immtsf_xadd_params,
  * immtsf_gr_params, immtsf_ttcn_params, immtsf_gcn_params, immtsf_decoder_params, immtsf_time2vec_params, immtsf_encoder_layer_cfg,
- * immtsf_encoder_layer_params, immtsf_ffn_block_cfg, immtsf_ffn_block_params, immtsf_store, immtsf_note_index, immtsf_lowrank_grad: lets a
- * binding check its own struct definitions against the library it loaded (tests/test_abi.py compares with ctypes.sizeof).  Writes
- * min(max, 16) entries to the HOST array `out`, returns the number of structs (16).  (ABI 5; 16 structs from ABI 6) */
+ * immtsf_encoder_layer_params, immtsf_ffn_block_cfg, immtsf_ffn_block_params, immtsf_store, immtsf_note_index, immtsf_lowrank_grad,
+ * immtsf_latent_ode_dims: lets a binding check its own struct definitions against the library it loaded (tests/test_abi.py compares with
+ * ctypes.sizeof).  Writes min(max, 17) entries to the HOST array `out`, returns the number of structs (17).  (ABI 5; 16 structs from
+ * ABI 6; the 17th added within ABI 7 with the LatentODE functions) */
 /* the history's normalisation of PatchTST / TimesNet (reference models/PatchTST.py:104-109, models/TimesNet.py:113-117: x - mean over time,
  * / sqrt(biased variance + 1e-5)) as one launch: x (B, L, C) -> xn (B, L, C), means (B, C), stdev (B, C).  Data only: no gradient.  (ABI 6) */
 int immtsf_instance_norm(const float* x, int32_t B, int32_t L, int32_t C, float* xn, float* means, float* stdev, immtsf_stream_t stream);
@@ -69,7 +70,7 @@ int immtsf_instance_norm(const float* x, int32_t B, int32_t L, int32_t C, float*
 int immtsf_notes_stage(const float* emb, int32_t d_m, const int32_t* src_rows, const int32_t* total, int32_t max_rows, void* X_h, int32_t ldx,
                        const float* tau, const int32_t* rowmap, int32_t dt, const float* lin_w, const float* lin_b, const float* per_w,
                        const float* per_b, immtsf_stream_t stream);
-#define IMMTSF_ABI_NSTRUCTS 16
+#define IMMTSF_ABI_NSTRUCTS 17
 int immtsf_abi_sizes(int32_t* out, int32_t max);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -714,6 +715,34 @@ int immtsf_gpt2_attention_backward(const float* q, int32_t ldq, const float* k, 
                                    const float* out, const float* lse, int32_t B, int32_t S, int32_t H, int32_t q_from, float scale,
                                    float p_drop, uint64_t seed, uint64_t site, float* dq, float* dk, float* dv, int32_t ldd,
                                    immtsf_stream_t stream);
+
+/* ---- LatentODE backbone (added within ABI 7: new functions and one new struct only; csrc/latent_ode.hip): forecasting() of reference
+ * models/LatentODE.py over lib/latent_ode_components (the ODE-RNN encoder run backwards in time, transform_z0, one draw of z0, the
+ * generative ODE over the forecast times, the Linear decoder; rec_layers = gen_layers = 1, one trajectory sample) as ONE launch forward and
+ * TWO backward.  All fp32.  R = rec_dims, U = units, G = gru_units, Z = latents.  Inputs: data, mask (B, L, C); the step plan of the shared
+ * time axis, one entry per observed point i: steps[i] = -1: one Euler step y += step_len[i] f(y); n >= 1: n steps of the 3/8-rule RK4 of
+ * length step_len[i] each (n above 256 is taken as 256); 0: no ODE step; the points are walked i = L-1 .. 0; tp_pred (Lp) the forecast
+ * times; params: every parameter in the order of the module's state_dict, flattened into one buffer (GRU update / reset / new-state nets,
+ * the encoder's gradient net, transform_z0, the generative gradient net, the decoder; ..._param_count gives its length, -1 for dimensions
+ * outside the limits); eps (B, Z) the standard-normal draw.  Outputs: out (B, Lp, C); states (B, L + 1, 2R) and traj (B, Lp, Z), what the
+ * backward reads.  backward: d_out (B, Lp, C) -> OVERWRITES grads (the layout of params).  Data, mask, times and eps take no gradient.  The
+ * sums over B run in index order over per-workgroup slabs in `workspace`: no atomics, the same inputs give the same bits.
+ * ..._supported answers from the dims alone (host arithmetic): 1 <= R, Z <= 64, 1 <= U, G <= 128, 1 <= C <= 64, 1 <= L, Lp <= 2^20, B >= 0 and
+ * the weights and a tile's state within 160 KB of LDS; the compute calls also need B max(L + 1, Lp) max(2R, Z, C) < 2^31.  Otherwise 0 /
+ * IMMTSF_EUNSUPPORTED.  ..._workspace_bytes: the backward's workspace (0 for dimensions the compute calls refuse). */
+typedef struct immtsf_latent_ode_dims {
+    int32_t B, L, Lp, C, rec_dims, units, gru_units, latents;
+} immtsf_latent_ode_dims;
+int immtsf_latent_ode_supported(const immtsf_latent_ode_dims* dims);
+int32_t immtsf_latent_ode_param_count(const immtsf_latent_ode_dims* dims);
+size_t immtsf_latent_ode_workspace_bytes(const immtsf_latent_ode_dims* dims);
+int immtsf_latent_ode_forward(const immtsf_latent_ode_dims* dims, const float* data, const float* mask, const int32_t* steps,
+                              const float* step_len, const float* tp_pred, const float* params, const float* eps, float* out,
+                              float* states, float* traj, immtsf_stream_t stream);
+int immtsf_latent_ode_backward(const immtsf_latent_ode_dims* dims, const float* data, const float* mask, const int32_t* steps,
+                               const float* step_len, const float* tp_pred, const float* params, const float* eps, const float* states,
+                               const float* traj, const float* d_out, float* grads, void* workspace, size_t workspace_bytes,
+                               immtsf_stream_t stream);
 
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
