@@ -1,8 +1,10 @@
 // Device-side batch builder: the dataset's windows live in HBM as window-major CSR arrays (the
 // "resident store"); a batch is a list of window ids.  These kernels emit exactly what the reference's collate
 // functions return -- zero-padded history / prediction tensors with normalised times
-// (lib/parse_datasets.py:252-295), tPatchGNN's per-(patch, variable) compacted patches (:298-366 with
-// lib/utils.py:359-413) and the multimodal part, tau + zero-padded note embeddings (:764-824) -- plus the packed
+// (lib/parse_datasets.py:252-295; CRU's raw-time form, :369-408, is the same kernel with time_max = 1),
+// tPatchGNN's per-(patch, variable) compacted patches (:298-366 with lib/utils.py:359-413), LatentODE's grid on
+// the batch's shared time axis (:411-471, immtsf_collate_union: a gather, every element written once) and the
+// multimodal part, tau + zero-padded note embeddings (:764-824) -- plus the packed
 // ragged note index (lengths / offsets / row map into the resident embedding matrix) that the fusion kernels use,
 // so the padded embeddings and the |V|-sum mask re-derivation can be skipped.  Pure gathers: HBM-bound, bit-exact.
 #include "../../include/immtsf.h"
@@ -80,6 +82,81 @@ __global__ __launch_bounds__(256) void collate_patches_kernel(immtsf_store s, co
             omsk[o] = 0.f;
         }
     }
+}
+
+// LatentODE's axis time (lib/parse_datasets.py:448-454): normalize_masked_tp, then + j * eps; torch rounds the division, the
+// product and the sum to fp32 one by one.  hipcc contracts a * b + c into an FMA by default, and its __fmul_rn / __fadd_rn
+// are the plain operators, so contraction is switched off for this function: one FMA changes the last bit.
+__device__ __forceinline__ float union_tp(float u, int j, float scale, float eps) {
+#pragma clang fp contract(off)
+    const float jitter = (float)j * eps;
+    const float t = norm_tp(u, scale);
+    return t + jitter;
+}
+
+// the LAST row of a window's non-decreasing time slice whose time equals u (upper bound - 1, tested for equality), or -1.
+// Last, because the reference's index_put on the CPU lets the later of two rows with one timestamp win.
+__device__ __forceinline__ int union_row(const float* __restrict__ tt, int len, float u) {
+    int lo = 0, hi = len;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (tt[mid] <= u) lo = mid + 1; else hi = mid;
+    }
+    return (lo > 0 && tt[lo - 1] == u) ? lo - 1 : -1;
+}
+
+// one window's slab (n axis points x C) of one half of the grid; dat / msk point at the slab.  16-byte stores where the slab
+// length and both bases allow it (zeros are the bulk of the bytes), scalar stores otherwise
+__device__ __forceinline__ void union_half(const immtsf_store& s, long r0, int len, const float* __restrict__ axis, int n,
+                                           float* __restrict__ dat, float* __restrict__ msk, int t0, int stride) {
+    const int C = s.C, total = n * C;            // T * C <= 2^30 (checked at the entry point)
+    const float* __restrict__ tt = s.tt + r0;
+    if ((total & 3) == 0 && ((reinterpret_cast<uintptr_t>(dat) | reinterpret_cast<uintptr_t>(msk)) & 15) == 0) {
+        for (int q = t0; q < total / 4; q += stride) {
+            float v[4], m[4];
+            int j = q * 4 / C, c = q * 4 - j * C;
+            int row = union_row(tt, len, axis[j]);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                v[k] = row >= 0 ? s.vals[(size_t)(r0 + row) * C + c] : 0.f;
+                m[k] = row >= 0 ? s.mask[(size_t)(r0 + row) * C + c] : 0.f;
+                if (++c == C && k < 3) {
+                    c = 0;
+                    ++j;
+                    row = union_row(tt, len, axis[j]);
+                }
+            }
+            reinterpret_cast<float4*>(dat)[q] = make_float4(v[0], v[1], v[2], v[3]);
+            reinterpret_cast<float4*>(msk)[q] = make_float4(m[0], m[1], m[2], m[3]);
+        }
+    } else {
+        for (int i = t0; i < total; i += stride) {
+            const int j = i / C, c = i - j * C;
+            const int row = union_row(tt, len, axis[j]);
+            dat[i] = row >= 0 ? s.vals[(size_t)(r0 + row) * C + c] : 0.f;
+            msk[i] = row >= 0 ? s.mask[(size_t)(r0 + row) * C + c] : 0.f;
+        }
+    }
+}
+
+// grid (B, chunks): cell (b, j) of the (B, T, C) grid holds the row of window b whose time equals axis[j], else zeros; axis points
+// below n_obs go to the observed pair, the rest to the predicted pair.  The blocks of b == 0 also write the T axis times.
+__global__ __launch_bounds__(256) void collate_union_kernel(immtsf_store s, const int32_t* __restrict__ wid,
+                                                             const float* __restrict__ axis, int T, int n_obs, float scale, float eps,
+                                                             float* __restrict__ otp, float* __restrict__ odat, float* __restrict__ omsk,
+                                                             float* __restrict__ ptp, float* __restrict__ pdat, float* __restrict__ pmsk) {
+    const int b = blockIdx.x, w = wid[b], C = s.C, n_pred = T - n_obs;
+    const long r0 = s.row_off[w];
+    const int len = (int)(s.row_off[w + 1] - r0);
+    const int stride = gridDim.y * 256, t0 = blockIdx.y * 256 + threadIdx.x;
+    if (b == 0) {
+        for (int j = t0; j < T; j += stride) {
+            const float t = union_tp(axis[j], j, scale, eps);
+            if (j < n_obs) otp[j] = t; else ptp[j - n_obs] = t;
+        }
+    }
+    if (n_obs > 0) union_half(s, r0, len, axis, n_obs, odat + (size_t)b * n_obs * C, omsk + (size_t)b * n_obs * C, t0, stride);
+    if (n_pred > 0) union_half(s, r0, len, axis + n_obs, n_pred, pdat + (size_t)b * n_pred * C, pmsk + (size_t)b * n_pred * C, t0, stride);
 }
 
 // one block: lengths[b] = notes of window b, offsets = exclusive scan (B+1 entries)
@@ -172,6 +249,28 @@ int immtsf_collate_patches(const immtsf_store* s, const int32_t* window_ids, int
     scale = scale + (scale == 0.f ? 1.f : 0.f) * 1e-8f;
     hipLaunchKernelGGL(collate_patches_kernel, dim3(B, npatch), dim3(256), 0, static_cast<hipStream_t>(stream), *s, window_ids,
                        npatch, patch_size, patch_stride, history, Lp, scale, obs_tp, obs_data, obs_mask);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
+int immtsf_collate_union(const immtsf_store* s, const int32_t* window_ids, int32_t B, const float* axis, int32_t T, int32_t n_obs,
+                         float time_max, float* obs_tp, float* obs_data, float* obs_mask, float* pred_tp, float* pred_data,
+                         float* pred_mask, immtsf_stream_t stream) {
+    if (!store_ok(s) || !window_ids || B < 0 || T < 0 || n_obs < 0 || n_obs > T || (T > 0 && !axis)) return IMMTSF_EINVAL;
+    if (n_obs > 0 && (!obs_tp || !obs_data || !obs_mask)) return IMMTSF_EINVAL;
+    if (T - n_obs > 0 && (!pred_tp || !pred_data || !pred_mask)) return IMMTSF_EINVAL;
+    if ((long)T * s->C > (1L << 30)) return IMMTSF_EINVAL;      // the kernel indexes one window's slab with int
+    if (B == 0 || T == 0) return IMMTSF_OK;
+    float scale = time_max - 0.0f;
+    scale = scale + (scale == 0.f ? 1.f : 0.f) * 1e-8f;
+    const float eps = 1.1920928955078125e-07f * time_max;      // torch.finfo(float32).eps * cap: the cap itself, not the guarded scale
+    const long work = (long)(n_obs > T - n_obs ? n_obs : T - n_obs) * s->C;
+    long gy = (work + 1023) / 1024;                            // about one 16-byte store per thread
+    const long ty = ((long)T + 255) / 256;                     // ... and the axis times are spread no thinner
+    if (gy < ty) gy = ty;
+    if (gy > 64) gy = 64;
+    hipLaunchKernelGGL(collate_union_kernel, dim3(B, (unsigned)gy), dim3(256), 0, static_cast<hipStream_t>(stream), *s, window_ids, axis,
+                       T, n_obs, scale, eps, obs_tp, obs_data, obs_mask, pred_tp, pred_data, pred_mask);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
 }

@@ -330,6 +330,7 @@ _PROTOS = {
     "immtsf_collate_series": (C.c_int, [_P(Store), c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_float] + [c_f32p] * 6 + [c_stream]),
     "immtsf_collate_patches": (C.c_int, [_P(Store), c_i32p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32,
                                          C.c_float, c_f32p, c_f32p, c_f32p, c_stream]),
+    "immtsf_collate_union": (C.c_int, [_P(Store), c_i32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_float] + [c_f32p] * 6 + [c_stream]),
     "immtsf_collate_notes": (C.c_int, [_P(Store), c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p, c_i32p, c_i32p, C.c_void_p,
                                        c_stream]),
     "immtsf_gemm": (C.c_int, [C.c_int32, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p,

@@ -3,12 +3,15 @@
 The reference keeps the dataset as a Python list of per-window tensors and builds every batch on the host with
 pad_sequence / Python loops (lib/parse_datasets.py:252-366, 764-824).  Here the whole dataset is laid out ONCE as
 window-major CSR arrays in HBM (a 288 GB device holds every dataset the reference ships many times over), the
-text-embedding matrices stay resident, and a batch is built by three gather kernels from a list of window ids.
-`collate()` returns the same dict the reference's collate returns (bit-exact), plus the packed ragged note index
+text-embedding matrices stay resident, and a batch is built by gather kernels from a list of window ids.
+`collate()` returns the same dict the reference's collate returns (bit-exact) -- the standard form, tPatchGNN's patch
+form, CRU's raw-time form and LatentODE's shared-axis form (:369-471) -- plus the packed ragged note index
 (`note_lengths`, `note_offsets`, `note_rowmap`) that makes the zero-padded embeddings optional.
 
 Host side (one-time, numpy): per-window metadata -- history/prediction lengths, note counts and the per-window
-maximum patch population -- so output shapes are known without a device sync.
+maximum patch population -- so output shapes are known without a device sync.  The ODE form's shapes depend on the
+batch's distinct times: its axis is formed per batch from the host copy of the times (one np.unique) and sent over
+with one non-blocking copy; the device is never read back.
 """
 from __future__ import annotations
 
@@ -201,15 +204,34 @@ class ResidentStore:
             self._patch_cache[key] = out
         return self._patch_cache[key]
 
-    def collate(self, window_ids, patch=None, padded_notes=True):
+    def _union_axis(self, ids):
+        """-> (axis, n_obs): the sorted distinct fp32 times over all rows of the batch's windows and how many lie below `history`
+        (what torch.unique / torch.lt give the reference, lib/parse_datasets.py:418-424).  Host only: one sort of the batch's rows."""
+        ro = self._row_off
+        axis = np.unique(np.concatenate([self._tt[ro[w]:ro[w + 1]] for w in ids])) if len(ids) else np.zeros(0, np.float32)
+        return axis, int(np.searchsorted(axis, np.float32(self.history), side="left"))
+
+    def collate(self, window_ids, patch=None, padded_notes=True, form="standard"):
         """-> dict of device tensors.  patch=None: the standard collate's keys; patch=(patch_size, npatch, patch_stride):
-        tPatchGNN's.  Always: tau, note_lengths, note_offsets, note_rowmap (+ notes_embeddings unless padded_notes=False)."""
+        tPatchGNN's.  form="cru": the standard keys with the stored chunk-relative times (not normalised); form="ode": LatentODE's
+        -- one shared time axis, observed_tp (n_obs,) / tp_to_predict (T - n_obs,) and (B, n_obs | T - n_obs, C) grids.
+        Always: tau, note_lengths, note_offsets, note_rowmap (+ notes_embeddings unless padded_notes=False)."""
+        if form not in ("standard", "cru", "ode"):
+            raise ValueError(f"unknown collate form {form!r}: 'standard', 'cru' or 'ode'")
+        if patch is not None and form != "standard":
+            raise ValueError(f"patch= builds tPatchGNN's form; it cannot be combined with form={form!r}")
         lib = _lib.load()
         ids, ids_dev = self._ids(window_ids)
         B, dev, f32 = len(ids), self.device, torch.float32
+        if form == "ode":
+            out = self._collate_union(lib, ids, ids_dev)
+            if B:
+                self._collate_notes(lib, out, ids, ids_dev, padded_notes)
+            else:
+                self._empty_notes(out, padded_notes)
+            return out
         Lmax = int(self.hist_len[ids].max()) if B else 0
         Lpmax = int(self.pred_len[ids].max()) if B else 0
-        Nmax = int(self.n_notes[ids].max()) if B else 0
         out = {"tp_to_predict": torch.empty(B, Lpmax, dtype=f32, device=dev),
                "data_to_predict": torch.empty(B, Lpmax, self.C, dtype=f32, device=dev),
                "mask_predicted_data": torch.empty(B, Lpmax, self.C, dtype=f32, device=dev)}
@@ -217,18 +239,18 @@ class ResidentStore:
         if B == 0:          # nothing to launch (empty tensors have no device pointer)
             shp = (0, 0, self.C) if patch is None else (0, patch[1], 0, self.C)
             out.update(observed_tp=torch.empty(shp[:-1], dtype=f32, device=dev), observed_data=torch.empty(shp, dtype=f32, device=dev),
-                       observed_mask=torch.empty(shp, dtype=f32, device=dev), tau=torch.empty(0, 0, dtype=f32, device=dev),
-                       note_lengths=torch.empty(0, dtype=torch.int32, device=dev),
-                       note_offsets=torch.zeros(1, dtype=torch.int32, device=dev),
-                       note_rowmap=torch.empty(0, dtype=torch.int32, device=dev))
-            if padded_notes and self.d_m:
-                out["notes_embeddings"] = torch.empty(0, 0, self.d_m, dtype=f32, device=dev)
+                       observed_mask=torch.empty(shp, dtype=f32, device=dev))
+            self._empty_notes(out, padded_notes)
             return out
         if patch is None:
             out.update(observed_tp=torch.empty(B, Lmax, dtype=f32, device=dev),
                        observed_data=torch.empty(B, Lmax, self.C, dtype=f32, device=dev),
                        observed_mask=torch.empty(B, Lmax, self.C, dtype=f32, device=dev))
-            check(lib.immtsf_collate_series(st, ptr(ids_dev), B, Lmax, Lpmax, float(self.time_max), ptr(out["observed_tp"]),
+            # CRU's collate (lib/parse_datasets.py:369-408) is the standard one without the time normalisation.  The kernel computes
+            # (t - 0) / scale with scale = time_max + (time_max == 0) * 1e-8; at time_max = 1 that is t / 1, which IEEE division
+            # returns as t bit for bit (and the padding stays 0), so the raw-time form needs no kernel of its own.
+            time_max = 1.0 if form == "cru" else float(self.time_max)
+            check(lib.immtsf_collate_series(st, ptr(ids_dev), B, Lmax, Lpmax, time_max, ptr(out["observed_tp"]),
                                             ptr(out["observed_data"]), ptr(out["observed_mask"]), ptr(out["tp_to_predict"]),
                                             ptr(out["data_to_predict"]), ptr(out["mask_predicted_data"]), stream_ptr()),
                   "collate_series")
@@ -243,6 +265,45 @@ class ResidentStore:
             check(lib.immtsf_collate_patches(st, ptr(ids_dev), B, npatch, float(ps), float(pstride), self.history, Lp,
                                              float(self.time_max), ptr(out["observed_tp"]), ptr(out["observed_data"]),
                                              ptr(out["observed_mask"]), stream_ptr()), "collate_patches")
+        self._collate_notes(lib, out, ids, ids_dev, padded_notes)
+        return out
+
+    def _collate_union(self, lib, ids, ids_dev):
+        """the six keys of form="ode" (variable_time_collate_fn_ODE, lib/parse_datasets.py:411-471): one launch"""
+        B, dev, f32 = len(ids), self.device, torch.float32
+        axis, n_obs = self._union_axis(ids)
+        T = len(axis)
+        out = {"observed_tp": torch.empty(n_obs, dtype=f32, device=dev),
+               "observed_data": torch.empty(B, n_obs, self.C, dtype=f32, device=dev),
+               "observed_mask": torch.empty(B, n_obs, self.C, dtype=f32, device=dev),
+               "tp_to_predict": torch.empty(T - n_obs, dtype=f32, device=dev),
+               "data_to_predict": torch.empty(B, T - n_obs, self.C, dtype=f32, device=dev),
+               "mask_predicted_data": torch.empty(B, T - n_obs, self.C, dtype=f32, device=dev)}
+        if B == 0 or T == 0:          # nothing to launch
+            return out
+        # the axis goes over from pinned memory without blocking; the caching host allocator keeps the block until the copy has run
+        staged = torch.empty(T, dtype=f32, pin_memory=True)
+        staged.numpy()[:] = axis
+        axis_dev = staged.to(dev, non_blocking=True)
+        check(lib.immtsf_collate_union(C.byref(self._struct), ptr(ids_dev), B, ptr(axis_dev), T, n_obs, float(self.time_max),
+                                       ptr(out["observed_tp"]), ptr(out["observed_data"]), ptr(out["observed_mask"]),
+                                       ptr(out["tp_to_predict"]), ptr(out["data_to_predict"]), ptr(out["mask_predicted_data"]),
+                                       stream_ptr()), "collate_union")
+        return out
+
+    def _empty_notes(self, out, padded_notes):
+        """the multimodal part of a batch of no windows"""
+        dev = self.device
+        out.update(tau=torch.empty(0, 0, dtype=torch.float32, device=dev), note_lengths=torch.empty(0, dtype=torch.int32, device=dev),
+                   note_offsets=torch.zeros(1, dtype=torch.int32, device=dev), note_rowmap=torch.empty(0, dtype=torch.int32, device=dev))
+        if padded_notes and self.d_m:
+            out["notes_embeddings"] = torch.empty(0, 0, self.d_m, dtype=torch.float32, device=dev)
+
+    def _collate_notes(self, lib, out, ids, ids_dev, padded_notes):
+        """the multimodal part, the same for every form: tau, the padded embeddings and the packed ragged note index"""
+        B, dev, f32 = len(ids), self.device, torch.float32
+        st = C.byref(self._struct)
+        Nmax = int(self.n_notes[ids].max()) if B else 0
         total = int(self.n_notes[ids].sum()) if B else 0
         out["tau"] = torch.empty(B, Nmax, dtype=f32, device=dev)
         out["note_lengths"] = torch.empty(B, dtype=torch.int32, device=dev)
@@ -256,4 +317,3 @@ class ResidentStore:
         if self.d_m:
             from .ops import PackedNotes
             out["notes_packed"] = PackedNotes(self.d["emb"], out["note_rowmap"], out["note_lengths"], Nmax)
-        return out

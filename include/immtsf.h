@@ -837,6 +837,13 @@ int immtsf_collate_series(const immtsf_store* s, const int32_t* window_ids, int3
 int immtsf_collate_patches(const immtsf_store* s, const int32_t* window_ids, int32_t B, int32_t npatch, float patch_size,
                            float patch_stride, float history, int32_t Lp, float time_max, float* obs_tp, float* obs_data,
                            float* obs_mask, immtsf_stream_t stream);
+/* LatentODE's form (lib/parse_datasets.py:411-471): `axis` [T] (device) holds the sorted distinct fp32 times of the batch's rows,
+ * the first n_obs of them below `history`.  obs_* (n_obs) / (B,n_obs,C) and pred_* (T-n_obs) / (B,T-n_obs,C): cell (b,j) is window
+ * b's row whose time equals axis[j] (the last one if several do), else zeros; time j is axis[j] / time_max + j * (fp32 eps *
+ * time_max), every operation rounded on its own.  One launch, every element written once; a zero-length half may be NULL */
+int immtsf_collate_union(const immtsf_store* s, const int32_t* window_ids, int32_t B, const float* axis, int32_t T, int32_t n_obs,
+                         float time_max, float* obs_tp, float* obs_data, float* obs_mask, float* pred_tp, float* pred_data,
+                         float* pred_mask, immtsf_stream_t stream);
 /* tau (B,Nmax), notes (B,Nmax,d_m) zero padded (either may be NULL), and the packed ragged index: lengths[B],
  * offsets[B+1] (int32, bit-exact with immtsf_ragged_index on the padded tensor), rowmap[sum] -> row in `emb` (or NULL) */
 int immtsf_collate_notes(const immtsf_store* s, const int32_t* window_ids, int32_t B, int32_t Nmax, float* tau, float* notes,
