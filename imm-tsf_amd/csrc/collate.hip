@@ -216,6 +216,113 @@ __global__ __launch_bounds__(256) void collate_notes_kernel(immtsf_store s, cons
     }
 }
 
+// sum over the block's 256 threads, in every thread (integers: the order of the additions does not matter)
+__device__ __forceinline__ int block_sum_int(int v, int* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// A whole standard / CRU batch as ONE launch, grid (B, chunks): what collate_series_kernel, note_index_kernel and collate_notes_kernel
+// write between them.  offsets[b] is the number of notes of the windows in front of b; every block sums those counts for its own b
+// (B is a few thousand at most: at most a few loads per thread; blocks that write no index entry skip the sum), so the prefix sum
+// needs no second launch, no atomics and no block reads what another one wrote.  The blocks of chunk 0 write lengths / offsets, the block of the last window also offsets[B].
+__global__ __launch_bounds__(256) void collate_batch_kernel(immtsf_store s, const int32_t* __restrict__ wid, int B, int Lmax, int Lpmax,
+                                                             int Nmax, float scale, float* __restrict__ otp, float* __restrict__ odat,
+                                                             float* __restrict__ omsk, float* __restrict__ ptp, float* __restrict__ pdat,
+                                                             float* __restrict__ pmsk, float* __restrict__ tau, float* __restrict__ notes,
+                                                             int32_t* __restrict__ lengths, int32_t* __restrict__ offsets,
+                                                             int32_t* __restrict__ rowmap) {
+    __shared__ int red[4];
+    const int b = blockIdx.x, w = wid[b], C = s.C, d_m = s.d_m;
+    const int stride = gridDim.y * 256, t0 = blockIdx.y * 256 + threadIdx.x;
+    // ---- the note index.  Only the blocks that write lengths / offsets (chunk 0) or a row-map entry (a thread with t0 < n) need the
+    // offset; the condition is the same for the whole block, so the barrier inside block_sum_int is met by all of its threads or none
+    const long n0 = s.note_off[w];
+    const int n = (int)(s.note_off[w + 1] - n0);
+    int off = 0;
+    if (blockIdx.y == 0 || (int)(blockIdx.y * 256) < n) {
+        int before = 0;
+        for (int j = threadIdx.x; j < b; j += 256) {
+            const int wj = wid[j];
+            before += (int)(s.note_off[wj + 1] - s.note_off[wj]);
+        }
+        off = block_sum_int(before, red);
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        lengths[b] = n;
+        offsets[b] = off;
+        if (b == B - 1) offsets[B] = off + n;
+    }
+    // ---- the six series tensors (collate_series_kernel)
+    const long r0 = s.row_off[w];
+    const int len = (int)(s.row_off[w + 1] - r0), hl = s.hist_len[w], pl = len - hl;
+    for (int i = t0; i < Lmax; i += stride) otp[(size_t)b * Lmax + i] = i < hl ? norm_tp(s.tt[r0 + i], scale) : 0.f;
+    for (int i = t0; i < Lmax * C; i += stride) {
+        const int l = i / C;
+        const bool live = l < hl;
+        odat[(size_t)b * Lmax * C + i] = live ? s.vals[(r0 + l) * C + (i - l * C)] : 0.f;
+        omsk[(size_t)b * Lmax * C + i] = live ? s.mask[(r0 + l) * C + (i - l * C)] : 0.f;
+    }
+    for (int i = t0; i < Lpmax; i += stride) ptp[(size_t)b * Lpmax + i] = i < pl ? norm_tp(s.tt[r0 + hl + i], scale) : 0.f;
+    for (int i = t0; i < Lpmax * C; i += stride) {
+        const int l = i / C;
+        const bool live = l < pl;
+        pdat[(size_t)b * Lpmax * C + i] = live ? s.vals[(r0 + hl + l) * C + (i - l * C)] : 0.f;
+        pmsk[(size_t)b * Lpmax * C + i] = live ? s.mask[(r0 + hl + l) * C + (i - l * C)] : 0.f;
+    }
+    // ---- tau, the packed row map and the padded embeddings (collate_notes_kernel)
+    for (int i = t0; i < Nmax; i += stride) {
+        tau[(size_t)b * Nmax + i] = i < n ? s.note_tau[n0 + i] : 0.f;
+        if (i < n) rowmap[off + i] = (int32_t)s.note_src[n0 + i];
+    }
+    if (notes) {
+        const int q = d_m / 4;
+        if ((d_m & 3) == 0 && ((reinterpret_cast<uintptr_t>(s.emb) | reinterpret_cast<uintptr_t>(notes)) & 15) == 0) {
+            for (long i = t0; i < (long)Nmax * q; i += stride) {
+                const int r = (int)(i / q), c = (int)(i - (long)r * q);
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (r < n) v = reinterpret_cast<const float4*>(s.emb + (size_t)s.note_src[n0 + r] * d_m)[c];
+                reinterpret_cast<float4*>(notes + ((size_t)b * Nmax + r) * d_m)[c] = v;
+            }
+        } else {
+            for (long i = t0; i < (long)Nmax * d_m; i += stride) {
+                const int r = (int)(i / d_m), c = (int)(i - (long)r * d_m);
+                notes[((size_t)b * Nmax + r) * d_m + c] = r < n ? s.emb[(size_t)s.note_src[n0 + r] * d_m + c] : 0.f;
+            }
+        }
+    }
+}
+
+// one wave per window: the largest number of observed history points any (patch, variable) pair of the window holds -- the slot count
+// collate_patches_kernel needs, found with the same comparisons (t >= st, t < ed, the last patch ending at `history`, mask != 0)
+__global__ __launch_bounds__(256) void patch_max_kernel(immtsf_store s, int W, int npatch, float patch_size, float patch_stride,
+                                                         float history, int32_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63, w = blockIdx.x * 4 + (threadIdx.x >> 6), C = s.C;
+    if (w >= W) return;                      // wave-uniform
+    const long r0 = s.row_off[w];
+    const int hl = s.hist_len[w];
+    int best = 0;
+    for (int i = 0; i < npatch; ++i) {
+        const float st = (float)i * patch_stride, ed = (i == npatch - 1) ? history : st + patch_size;
+        for (int d = 0; d < C; ++d) {
+            int count = 0;
+            for (int j0 = 0; j0 < hl; j0 += 64) {
+                const int j = j0 + lane;
+                bool hit = false;
+                if (j < hl) {
+                    const float t = s.tt[r0 + j];
+                    hit = (t >= st) && (t < ed) && (s.mask[(r0 + j) * C + d] != 0.f);
+                }
+                count += __popcll(__ballot(hit));
+            }
+            best = count > best ? count : best;
+        }
+    }
+    if (lane == 0) out[w] = best;
+}
+
 bool store_ok(const immtsf_store* s) {
     return s && s->tt && s->vals && s->mask && s->row_off && s->hist_len && s->C > 0;
 }
@@ -289,6 +396,44 @@ int immtsf_collate_notes(const immtsf_store* s, const int32_t* window_ids, int32
     if (gy > 64) gy = 64;
     hipLaunchKernelGGL(collate_notes_kernel, dim3(B, gy < 1 ? 1 : gy), dim3(256), 0, st, *s, window_ids, Nmax, offsets, tau, notes,
                        rowmap);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
+int immtsf_collate_batch(const immtsf_store* s, const int32_t* window_ids, int32_t B, int32_t Lmax, int32_t Lpmax, int32_t Nmax,
+                         float time_max, float* obs_tp, float* obs_data, float* obs_mask, float* pred_tp, float* pred_data,
+                         float* pred_mask, float* tau, float* notes, int32_t* lengths, int32_t* offsets, int32_t* rowmap,
+                         immtsf_stream_t stream) {
+    if (!store_ok(s) || !s->note_off || !s->note_tau || !s->note_src || !window_ids || B <= 0 || Lmax < 0 || Lpmax < 0 || Nmax < 0)
+        return IMMTSF_EINVAL;
+    if (!lengths || !offsets) return IMMTSF_EINVAL;
+    if (Lmax > 0 && (!obs_tp || !obs_data || !obs_mask)) return IMMTSF_EINVAL;
+    if (Lpmax > 0 && (!pred_tp || !pred_data || !pred_mask)) return IMMTSF_EINVAL;
+    if (Nmax > 0 && (!tau || !rowmap)) return IMMTSF_EINVAL;
+    if (notes && (!s->emb || s->d_m <= 0)) return IMMTSF_EINVAL;
+    if ((long)(Lmax > Lpmax ? Lmax : Lpmax) * s->C > (1L << 30)) return IMMTSF_EINVAL;      // the kernel indexes one window's slab with int
+    float scale = time_max - 0.0f;
+    scale = scale + (scale == 0.f ? 1.f : 0.f) * 1e-8f;
+    const int series = (Lmax > Lpmax ? Lmax : Lpmax) * s->C;
+    const long text = (notes && Nmax > 0) ? (long)Nmax * (s->d_m / 4 > 0 ? s->d_m / 4 : s->d_m) : Nmax;
+    long gy = (text + 255) / 256;
+    if (gy > 64) gy = 64;                                                  // the embedding rows: as immtsf_collate_notes spreads them
+    if (gy < cdiv(series, 256)) gy = cdiv(series, 256);                    // the series: as immtsf_collate_series
+    if (gy < 1) gy = 1;
+    if (gy > 65535) gy = 65535;                                            // every loop of the kernel strides by the grid
+    hipLaunchKernelGGL(collate_batch_kernel, dim3(B, (unsigned)gy), dim3(256), 0, static_cast<hipStream_t>(stream), *s, window_ids, B,
+                       Lmax, Lpmax, Nmax, scale, obs_tp, obs_data, obs_mask, pred_tp, pred_data, pred_mask, tau, notes, lengths, offsets,
+                       rowmap);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
+int immtsf_collate_patch_max(const immtsf_store* s, int32_t W, int32_t npatch, float patch_size, float patch_stride, float history,
+                             int32_t* out, immtsf_stream_t stream) {
+    if (!store_ok(s) || W < 0 || npatch <= 0 || (W > 0 && !out)) return IMMTSF_EINVAL;
+    if (W == 0) return IMMTSF_OK;
+    hipLaunchKernelGGL(patch_max_kernel, dim3(cdiv(W, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), *s, W, npatch, patch_size,
+                       patch_stride, history, out);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
 }

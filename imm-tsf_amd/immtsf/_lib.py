@@ -333,6 +333,9 @@ _PROTOS = {
     "immtsf_collate_union": (C.c_int, [_P(Store), c_i32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, C.c_float] + [c_f32p] * 6 + [c_stream]),
     "immtsf_collate_notes": (C.c_int, [_P(Store), c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p, c_i32p, c_i32p, C.c_void_p,
                                        c_stream]),
+    "immtsf_collate_batch": (C.c_int, [_P(Store), c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float] + [c_f32p] * 8 +
+                             [c_i32p, c_i32p, c_i32p, c_stream]),
+    "immtsf_collate_patch_max": (C.c_int, [_P(Store), C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, c_i32p, c_stream]),
     "immtsf_gemm": (C.c_int, [C.c_int32, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p,
                               C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, c_stream]),
     "immtsf_linear_backward": (C.c_int, [C.c_int32, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p,

@@ -147,3 +147,7 @@ timellm_fused = os.environ.get("IMMTSF_TIMELLM_FUSED", "1") != "0"
 # (the reference's loop over the observed points on torch ops, the step plan copied to the host once) -- the cross-check.  fp32 in
 # either precision mode
 latentode_fused = os.environ.get("IMMTSF_LATENTODE_FUSED", "1") != "0"
+# lib.parse_datasets.parse_datasets() returns immtsf.data.ResidentLoader objects over a ResidentStore (the dataset in HBM, every batch
+# built on the device, one id upload per epoch); IMMTSF_RESIDENT_LOADER=0: the reference module's own host loaders, when a
+# reference tree is on the path (NotImplementedError otherwise)
+resident_loader = os.environ.get("IMMTSF_RESIDENT_LOADER", "1") != "0"

@@ -10,10 +10,22 @@ does not mirror (`lib.utils`, `lib.parse_datasets`, `models.Informer`, ...), so:
     one exists, and copies the public names this build does not define (`layers.Embed.DataEmbedding_wo_pos`,
     `layers.Transformer_EncDec.TimerLayer`, ...), so the reference's other models keep importing what they need.
 
-Both are no-ops when no reference tree is on the path (the tests, the GPU box).
+  * `overlay_module` (called from a package's __init__) is for a module of the reference that stays the reference's -- its file, its
+    names -- while this build replaces some of its entry points: when `<package>.<leaf>` is imported, the reference's module further
+    along the package's __path__ is executed as usual and then handed to `install(module)` of the module here that carries the
+    replacements (`lib.parse_datasets`: the reference's module with `parse_datasets` / `get_input_and_pred_len` of
+    `lib.resident_datasets` installed).  With no such module on the path the name is an alias of the module here, so it imports
+    standalone too.  Why not a mirrored file lib/parse_datasets.py ending in reexport_missing, like the others:
+    tests/test_dropin_packages.py::test_reference_main_imports_resolve_with_this_tree_in_front pins `lib.parse_datasets.__file__` to the
+    tree behind this one, and a file of that name here would always be found first.
+
+The first two are no-ops when no reference tree is on the path (the tests, the GPU box).
 """
 from __future__ import annotations
 
+import importlib
+import importlib.abc
+import importlib.machinery
 import importlib.util
 import os
 import sys
@@ -55,3 +67,48 @@ def reexport_missing(module_globals: dict) -> None:
                 if not k.startswith("_") and k not in module_globals:
                     module_globals[k] = v
             return
+
+
+class _Alias(importlib.abc.Loader):
+    """`fullname` is the already importable module `target`, the same object under a second name"""
+
+    def __init__(self, target):
+        self.target = target
+
+    def create_module(self, spec):
+        return importlib.import_module(self.target)
+
+    def exec_module(self, module):
+        pass
+
+
+class _Overlay(importlib.abc.MetaPathFinder):
+    def __init__(self, fullname, target):
+        self.fullname, self.target = fullname, target
+
+    def find_spec(self, fullname, path=None, target=None):
+        if fullname != self.fullname:
+            return None
+        spec = importlib.machinery.PathFinder.find_spec(fullname, path)
+        if spec is None or spec.loader is None:         # nothing behind this tree: the module here under the reference's name
+            return importlib.machinery.ModuleSpec(fullname, _Alias(self.target), origin=importlib.util.find_spec(self.target).origin)
+        inner, target = spec.loader, self.target
+
+        class Loader(importlib.abc.Loader):
+            def create_module(self, spec):
+                return inner.create_module(spec)
+
+            def exec_module(self, module):
+                inner.exec_module(module)
+                importlib.import_module(target).install(module)
+
+            def __getattr__(self, name):        # get_code, get_source, get_filename, ...: the file loader's own
+                return getattr(inner, name)
+
+        spec.loader = Loader()
+        return spec
+
+
+def overlay_module(fullname: str, target: str) -> None:
+    if not any(isinstance(f, _Overlay) and f.fullname == fullname for f in sys.meta_path):
+        sys.meta_path.insert(0, _Overlay(fullname, target))

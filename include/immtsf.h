@@ -849,6 +849,19 @@ int immtsf_collate_union(const immtsf_store* s, const int32_t* window_ids, int32
 int immtsf_collate_notes(const immtsf_store* s, const int32_t* window_ids, int32_t B, int32_t Nmax, float* tau, float* notes,
                          int32_t* lengths, int32_t* offsets, int32_t* rowmap, immtsf_stream_t stream);
 
+/* A whole standard-form batch as ONE launch: everything immtsf_collate_series (obs_* and pred_*, all six required when their length is
+ * not 0) and immtsf_collate_notes (tau, notes or NULL, lengths, offsets, rowmap) write, bit for bit, for B >= 1 windows whose ids are
+ * read from device memory -- a slice of an epoch's id order will do.  offsets is the exclusive prefix sum of the B note counts, formed
+ * inside the launch (every workgroup sums the counts in front of its window; no atomics).  time_max = 1 gives CRU's raw times. */
+int immtsf_collate_batch(const immtsf_store* s, const int32_t* window_ids, int32_t B, int32_t Lmax, int32_t Lpmax, int32_t Nmax,
+                         float time_max, float* obs_tp, float* obs_data, float* obs_mask, float* pred_tp, float* pred_data,
+                         float* pred_mask, float* tau, float* notes, int32_t* lengths, int32_t* offsets, int32_t* rowmap,
+                         immtsf_stream_t stream);
+/* out[w], w < W: the largest number of observed history points one (patch, variable) pair of window w holds -- the Lp that
+ * immtsf_collate_patches needs for a batch is the maximum of out over its windows.  Same patch ranges and comparisons as there. */
+int immtsf_collate_patch_max(const immtsf_store* s, int32_t W, int32_t npatch, float patch_size, float patch_stride, float history,
+                             int32_t* out, immtsf_stream_t stream);
+
 /* ---- building blocks exported for tests and for the layers/ mirror ------------------------------------------- */
 /* C = act(alpha * op(A) op(B)^T + bias); layout 0 = NT (A:(M,K), B:(N,K)), 1 = NN (B:(K,N)), 2 = TN (A:(K,M), B:(K,N)) */
 int immtsf_gemm(int32_t layout, int32_t precision, const float* A, int32_t lda, const float* B, int32_t ldb, float* C,
