@@ -64,6 +64,11 @@ class LatentODEDims(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "L", "Lp", "C", "rec_dims", "units", "gru_units", "latents")]
 
 
+class NeuralFlowDims(C.Structure):
+    """immtsf_neural_flow_dims"""
+    _fields_ = [(n, C.c_int32) for n in ("B", "L", "Lp", "C", "rec_dims", "latents", "hidden_dim", "hidden_layers", "flow_layers")]
+
+
 class EncoderLayerCfg(C.Structure):
     _fields_ = [("Bs", C.c_int32), ("S", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("F", C.c_int32), ("precision", C.c_int32),
                 ("training", C.c_int32), ("p_attn", C.c_float), ("p_drop", C.c_float), ("eps", C.c_float), ("seed", C.c_uint64),
@@ -200,6 +205,11 @@ _PROTOS = {
     "immtsf_latent_ode_workspace_bytes": (C.c_size_t, [_P(LatentODEDims)]),
     "immtsf_latent_ode_forward": (C.c_int, [_P(LatentODEDims), c_f32p, c_f32p, c_i32p] + [c_f32p] * 7 + [c_stream]),
     "immtsf_latent_ode_backward": (C.c_int, [_P(LatentODEDims), c_f32p, c_f32p, c_i32p] + [c_f32p] * 8 + [C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_neural_flow_supported": (C.c_int, [_P(NeuralFlowDims)]),
+    "immtsf_neural_flow_param_count": (C.c_int32, [_P(NeuralFlowDims)]),
+    "immtsf_neural_flow_workspace_bytes": (C.c_size_t, [_P(NeuralFlowDims)]),
+    "immtsf_neural_flow_forward": (C.c_int, [_P(NeuralFlowDims)] + [c_f32p] * 10 + [c_stream]),
+    "immtsf_neural_flow_backward": (C.c_int, [_P(NeuralFlowDims)] + [c_f32p] * 11 + [C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,
@@ -421,7 +431,7 @@ _PROTOS = {
 # the structs of the ABI in immtsf_abi_sizes' order (tests/test_abi.py compares ctypes.sizeof with the library's sizeof)
 def abi_structs():
     return [FusionCfg, T2VParams, RecAvgParams, XAddParams, GRParams, TTCNParams, GCNParams, DecoderParams, Time2VecParams,
-            EncoderLayerCfg, EncoderLayerParams, FFNBlockCfg, FFNBlockParams, Store, NoteIndex, LowRankGrad, LatentODEDims]
+            EncoderLayerCfg, EncoderLayerParams, FFNBlockCfg, FFNBlockParams, Store, NoteIndex, LowRankGrad, LatentODEDims, NeuralFlowDims]
 
 
 _lib = None

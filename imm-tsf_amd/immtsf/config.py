@@ -147,6 +147,10 @@ timellm_fused = os.environ.get("IMMTSF_TIMELLM_FUSED", "1") != "0"
 # (the reference's loop over the observed points on torch ops, the step plan copied to the host once) -- the cross-check.  fp32 in
 # either precision mode
 latentode_fused = os.environ.get("IMMTSF_LATENTODE_FUSED", "1") != "0"
+# NeuralFlow's forecasting() as two HIP launches forward and three backward (csrc/neural_flow.hip) wherever the flow is the coupling flow
+# with the TimeLinear time net and immtsf_neural_flow_supported allows; IMMTSF_NEURALFLOW_FUSED=0: the composed path (the reference's
+# loop over the observed points on torch ops) -- the cross-check.  fp32 in either precision mode
+neuralflow_fused = os.environ.get("IMMTSF_NEURALFLOW_FUSED", "1") != "0"
 # lib.parse_datasets.parse_datasets() returns immtsf.data.ResidentLoader objects over a ResidentStore (the dataset in HBM, every batch
 # built on the device, one id upload per epoch); IMMTSF_RESIDENT_LOADER=0: the reference module's own host loaders, when a
 # reference tree is on the path (NotImplementedError otherwise)

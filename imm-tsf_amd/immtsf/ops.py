@@ -3365,3 +3365,80 @@ def latent_ode(data, mask, steps, step_len, tp_pred, flat_params, eps, widths):
             any(q.dtype != torch.float32 for q in (data, mask, step_len, tp_pred, flat_params, eps)):
         raise _lib.ImmtsfError("latent_ode: the tensors are not the fp32 tensors of these dimensions")
     return LatentODEFn.apply(data, mask, steps, step_len, tp_pred, flat_params, eps, (R, U, G, Z))
+
+
+# ------------------------------------------------------------------------------------------------ NeuralFlow backbone
+def _neural_flow_dims(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers):
+    return _lib.NeuralFlowDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(latents), int(hidden_dim), int(hidden_layers),
+                               int(flow_layers))
+
+
+def neural_flow_supported(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers, call=False):
+    """the limits of the fused NeuralFlow kernels (immtsf_neural_flow_supported: rec_dims, latents <= 64, hidden_dim <= 128, hidden_layers,
+    flow_layers <= 4, C <= 64, L, Lp <= 2^20, W_hh, the flow's nets and a tile's state within 160 KB of LDS), from the dims alone; call:
+    also what a compute call needs (B >= 1 and the saved state's index range, immtsf_neural_flow_workspace_bytes > 0)"""
+    import ctypes
+    d = _neural_flow_dims(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers)
+    lib = _lib.load()
+    if not lib.immtsf_neural_flow_supported(ctypes.byref(d)):
+        return False
+    return bool(lib.immtsf_neural_flow_workspace_bytes(ctypes.byref(d)) > 0) if call else True
+
+
+class NeuralFlowFn(torch.autograd.Function):
+    """NeuralFlow's forecasting() (the encoder's reversed walk of coupling-flow step + LSTM cell, transform_z0, z0 = mu + eps sigma, the
+    coupling flow at every forecast time, the decoder) as TWO launches; backward = THREE (immtsf_neural_flow_forward / _backward,
+    csrc/neural_flow.hip).  The flat parameter buffer is the only input with a gradient.  fp32 in either precision mode."""
+
+    @staticmethod
+    def forward(ctx, data, mask, tp, tpp, flat, eps, widths):
+        import ctypes
+        lib = _lib.load()
+        data, mask, tp, tpp, flat, eps = (_c(t) for t in (data, mask, tp, tpp, flat, eps))
+        _need_gpu(data, mask, tp, tpp, flat, eps)
+        B, L, C = data.shape
+        Lp = tpp.shape[1]
+        R, Z = widths[0], widths[1]
+        d = _neural_flow_dims(B, L, Lp, C, *widths)
+        out = torch.empty(B, Lp, C, dtype=torch.float32, device=data.device)
+        xg = torch.empty(B, L, 4 * R, dtype=torch.float32, device=data.device)
+        states = torch.empty(B, L + 1, 2 * R, dtype=torch.float32, device=data.device)
+        zs = torch.empty(B, 3, Z, dtype=torch.float32, device=data.device)
+        check(lib.immtsf_neural_flow_forward(ctypes.byref(d), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(out), ptr(xg),
+                                             ptr(states), ptr(zs), stream_ptr()), "neural_flow_forward")
+        ctx.dims = (B, L, Lp, C) + tuple(widths)
+        ctx.save_for_backward(data, mask, tp, tpp, flat, eps, xg, states, zs)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        import ctypes
+        lib = _lib.load()
+        data, mask, tp, tpp, flat, eps, xg, states, zs = ctx.saved_tensors
+        d = _neural_flow_dims(*ctx.dims)
+        grads = torch.empty_like(flat)      # every entry is written: no zero fill
+        ws = _bytes(lib.immtsf_neural_flow_workspace_bytes(ctypes.byref(d)), data.device)
+        check(lib.immtsf_neural_flow_backward(ctypes.byref(d), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(xg),
+                                              ptr(states), ptr(zs), ptr(dout.contiguous()), ptr(grads), ptr(ws), ws.numel(), stream_ptr()),
+              "neural_flow_backward")
+        return None, None, None, None, grads, None, None
+
+
+def neural_flow(data, mask, tp, tp_pred, flat_params, eps, widths):
+    """data, mask (B, L, C); tp (B, L), tp_pred (B, Lp): every window's own times; flat_params: every parameter in state_dict order,
+    flattened; eps (B, latents); widths = (rec_dims, latents, hidden_dim, hidden_layers, flow_layers) -> the forecast (B, Lp, C).
+    Gradients reach flat_params only."""
+    import ctypes
+    B, L, C = data.shape
+    widths = tuple(int(w) for w in widths)
+    if tp_pred.dim() != 2:
+        raise _lib.ImmtsfError("neural_flow: tp_pred is (B, Lp)")
+    Lp = tp_pred.shape[1]
+    if not neural_flow_supported(B, L, Lp, C, *widths, call=True):
+        raise _lib.ImmtsfError(f"neural_flow: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, C {C}, widths {widths})")
+    d = _neural_flow_dims(B, L, Lp, C, *widths)
+    nv = int(_lib.load().immtsf_neural_flow_param_count(ctypes.byref(d)))
+    if tuple(mask.shape) != (B, L, C) or tuple(tp.shape) != (B, L) or tuple(tp_pred.shape) != (B, Lp) or tuple(eps.shape) != (B, widths[1]) or \
+            flat_params.numel() != nv or any(q.dtype != torch.float32 for q in (data, mask, tp, tp_pred, flat_params, eps)):
+        raise _lib.ImmtsfError("neural_flow: the tensors are not the fp32 tensors of these dimensions")
+    return NeuralFlowFn.apply(data, mask, tp, tp_pred, flat_params, eps, widths)

@@ -57,9 +57,9 @@ int immtsf_abi_version(void);
 /* sizeof of every struct of this ABI, in the order immtsf_fusion_cfg, immtsf_t2v_params, immtsf_recavg_params, immtsf_xadd_params,
  * immtsf_gr_params, immtsf_ttcn_params, immtsf_gcn_params, immtsf_decoder_params, immtsf_time2vec_params, immtsf_encoder_layer_cfg,
  * immtsf_encoder_layer_params, immtsf_ffn_block_cfg, immtsf_ffn_block_params, immtsf_store, immtsf_note_index, immtsf_lowrank_grad,
- * immtsf_latent_ode_dims: lets a binding check its own struct definitions against the library it loaded (tests/test_abi.py compares with
- * ctypes.sizeof).  Writes min(max, 17) entries to the HOST array `out`, returns the number of structs (17).  (ABI 5; 16 structs from
- * ABI 6; the 17th added within ABI 7 with the LatentODE functions) */
+ * immtsf_latent_ode_dims, immtsf_neural_flow_dims: lets a binding check its own struct definitions against the library it loaded
+ * (tests/test_abi.py compares with ctypes.sizeof).  Writes min(max, 18) entries to the HOST array `out`, returns the number of structs
+ * (18).  (ABI 5; 16 structs from ABI 6; the 17th added within ABI 7 with the LatentODE functions, the 18th with the NeuralFlow ones) */
 /* the history's normalisation of PatchTST / TimesNet (reference models/PatchTST.py:104-109, models/TimesNet.py:113-117: x - mean over time,
  * / sqrt(biased variance + 1e-5)) as one launch: x (B, L, C) -> xn (B, L, C), means (B, C), stdev (B, C).  Data only: no gradient.  (ABI 6) */
 int immtsf_instance_norm(const float* x, int32_t B, int32_t L, int32_t C, float* xn, float* means, float* stdev, immtsf_stream_t stream);
@@ -70,7 +70,7 @@ int immtsf_instance_norm(const float* x, int32_t B, int32_t L, int32_t C, float*
 int immtsf_notes_stage(const float* emb, int32_t d_m, const int32_t* src_rows, const int32_t* total, int32_t max_rows, void* X_h, int32_t ldx,
                        const float* tau, const int32_t* rowmap, int32_t dt, const float* lin_w, const float* lin_b, const float* per_w,
                        const float* per_b, immtsf_stream_t stream);
-#define IMMTSF_ABI_NSTRUCTS 17
+#define IMMTSF_ABI_NSTRUCTS 18
 int immtsf_abi_sizes(int32_t* out, int32_t max);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -743,6 +743,36 @@ int immtsf_latent_ode_backward(const immtsf_latent_ode_dims* dims, const float* 
                                const float* step_len, const float* tp_pred, const float* params, const float* eps, const float* states,
                                const float* traj, const float* d_out, float* grads, void* workspace, size_t workspace_bytes,
                                immtsf_stream_t stream);
+
+/* ---- NeuralFlow backbone (added within ABI 7: new functions and one new struct only; csrc/neural_flow.hip): forecasting() of reference
+ * models/NeuralFlow.py over lib/neural_flow_components at model = 'flow', flow_model = 'coupling', time_net = 'TimeLinear' (the encoder's
+ * reversed walk over the observed points -- a coupling-flow step over t_i - prev_t, then an LSTM cell kept where any feature is observed --
+ * transform_z0, softplus, one draw of z0, the coupling flow at every forecast time, the Linear decoder) as TWO launches forward and THREE
+ * backward.  All fp32.  R = rec_dims, Z = latents.  Inputs: data, mask (B, L, C); tp (B, L) and tp_pred (B, Lp), every window's own
+ * times; params: every parameter in the order of the module's state_dict, flattened into one buffer (lstm.weight_ih, weight_hh, bias_ih,
+ * bias_hh; per encoder flow layer the latent net's Linears and time_net.scale; transform_z0; the decode flow likewise; the decoder;
+ * ..._param_count gives its length, -1 for dimensions outside the limits); eps (B, Z) the standard-normal draw.  Outputs: out (B, Lp, C);
+ * xg (B, L, 4R), states (B, L + 1, 2R) and zs (B, 3, Z) = (mu, sigma, z0), what the backward reads.  backward: d_out (B, Lp, C) ->
+ * OVERWRITES grads (the layout of params).  Data, mask, times and eps take no gradient.  The sums over windows and decode rows run in
+ * index order over per-workgroup slabs in `workspace`: no atomics, the same inputs give the same bits.  exp() in the coupling layer takes
+ * its argument as the reference writes it: no clamp.
+ * ..._supported answers from the dims alone (host arithmetic): 1 <= R, Z <= 64, 1 <= hidden_dim <= 128, 1 <= hidden_layers, flow_layers <= 4,
+ * 1 <= C <= 64, 1 <= L, Lp <= 2^20, B >= 0 and W_hh, the flow's nets and a tile's state within 160 KB of LDS; the compute calls also need
+ * B max(L + 1, Lp) max(4R, Z, C) < 2^31.  Otherwise 0 / IMMTSF_EUNSUPPORTED, and nothing is launched.  ..._workspace_bytes: the backward's
+ * workspace (0 for dimensions the compute calls refuse). */
+typedef struct immtsf_neural_flow_dims {
+    int32_t B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers;
+} immtsf_neural_flow_dims;
+int immtsf_neural_flow_supported(const immtsf_neural_flow_dims* dims);
+int32_t immtsf_neural_flow_param_count(const immtsf_neural_flow_dims* dims);
+size_t immtsf_neural_flow_workspace_bytes(const immtsf_neural_flow_dims* dims);
+int immtsf_neural_flow_forward(const immtsf_neural_flow_dims* dims, const float* data, const float* mask, const float* tp,
+                               const float* tp_pred, const float* params, const float* eps, float* out, float* xg, float* states,
+                               float* zs, immtsf_stream_t stream);
+int immtsf_neural_flow_backward(const immtsf_neural_flow_dims* dims, const float* data, const float* mask, const float* tp,
+                                const float* tp_pred, const float* params, const float* eps, const float* xg, const float* states,
+                                const float* zs, const float* d_out, float* grads, void* workspace, size_t workspace_bytes,
+                                immtsf_stream_t stream);
 
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
