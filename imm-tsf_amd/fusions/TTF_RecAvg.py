@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from fusions._common import NanFlag, f32, prep_t_hat, resolve_precision
-from fusions.load_llm import get_d_model, load_llm
+from fusions.load_llm import embed_notes, get_d_model, load_llm
 from immtsf import config
 from immtsf.ops import TTFRecAvgFn
 
@@ -40,14 +40,27 @@ class TTF_RecAvg(nn.Module):
         self.last_seed = 0
         self._nan = NanFlag()
 
+    def train(self, mode: bool = True):
+        """the frozen LLM of raw-text mode stays in eval mode: its embeddings are the ones compute_text_embeddings.py would precompute"""
+        super().train(mode)
+        if not self.use_text_embeddings:
+            self.llm_model.eval()
+        return self
+
     def _params(self):
         ip = self.input_proj
         return (self.log_recency_sigma, None if ip is None else ip.weight, None if ip is None else ip.bias,
                 self.layer_norm.weight, self.layer_norm.bias, self.proj.weight, self.proj.bias)
 
     def forward(self, notes_input, tau: torch.Tensor, t_hat: torch.Tensor):
+        M_lists = None
         if not self.use_text_embeddings:
-            raise NotImplementedError("raw-text mode is not part of the MI355X hot path")
+            # raw-text mode: notes_input is a list of B lists of strings; M_txt follows the list lengths.  (The kernel takes the dense
+            # tensor and, as on the precomputed path, leaves a zero row -- a note of no tokens -- out of the average.)
+            notes_input, note_mask = embed_notes(notes_input, self.tokenizer, self.llm_model, self.max_length)
+            M_lists = note_mask.any(dim=1, keepdim=True)
+            if notes_input.shape[1] < tau.shape[1]:
+                notes_input = torch.nn.functional.pad(notes_input, (0, 0, 0, tau.shape[1] - notes_input.shape[1]))
         V = f32(notes_input)
         B = V.shape[0]
         t_hat = prep_t_hat(t_hat, B)
@@ -59,7 +72,7 @@ class TTF_RecAvg(nn.Module):
                                      self.last_seed, flag, *self._params())
         if mode == "sync":
             self._nan.raise_if_set("Input embeddings V contain NaN values.")
-        return E_txt, M.view(torch.bool).view(B, 1)
+        return E_txt, (M.view(torch.bool).view(B, 1) if M_lists is None else M_lists)
 
     def check_nan(self):
         self._nan.raise_if_set("Input embeddings V contain NaN values.")

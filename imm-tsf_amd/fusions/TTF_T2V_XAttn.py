@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from fusions._common import NanFlag, f32, prep_t_hat, resolve_precision
-from fusions.load_llm import get_d_model, load_llm
+from fusions.load_llm import embed_notes_packed, get_d_model, load_llm
 from immtsf import config
 from immtsf.ops import PackedNotes, TTFT2VXAttnFn
 
@@ -63,6 +63,13 @@ class TTF_T2V_XAttn(nn.Module):
         self.last_seed = 0             # Philox key of the most recent training forward (mask export in tests)
         self._nan = NanFlag()
 
+    def train(self, mode: bool = True):
+        """the frozen LLM of raw-text mode stays in eval mode: its embeddings are the ones compute_text_embeddings.py would precompute"""
+        super().train(mode)
+        if not self.use_text_embeddings:
+            self.llm_model.eval()
+        return self
+
     def _params(self):
         ip = self.input_proj
         return (self.Q_param, None if ip is None else ip.weight, None if ip is None else ip.bias,
@@ -93,7 +100,13 @@ class TTF_T2V_XAttn(nn.Module):
         the caller promises that this projection is Z's ONLY consumer (immtsf.config.z_handover: in bf16 mode Z then exists as its bf16
         image alone -- the returned fp32 tensor is a placeholder -- and the gradient comes back in low-rank form)."""
         if not self.use_text_embeddings:
-            raise NotImplementedError("raw-text mode is not part of the MI355X hot path")
+            # raw-text mode: notes_input is a list of B lists of strings.  The frozen LLM's pooled rows go on in packed form (no padded
+            # (B, N_max, d_model) tensor), and the note mask is the list lengths' (a note of no tokens is still a note)
+            emb, lengths, _ = embed_notes_packed(notes_input, self.tokenizer, self.llm_model, self.max_length)
+            if emb.shape[0]:
+                notes_input = PackedNotes(emb, torch.arange(emb.shape[0], dtype=torch.int32, device=emb.device), lengths, tau.shape[1])
+            else:
+                notes_input = emb.new_zeros(tau.shape[0], tau.shape[1], self.d_model)
         packed = notes_input if isinstance(notes_input, PackedNotes) else None
         V = packed.emb if packed is not None else f32(notes_input)
         B = tau.shape[0]

@@ -210,6 +210,13 @@ _PROTOS = {
     "immtsf_neural_flow_workspace_bytes": (C.c_size_t, [_P(NeuralFlowDims)]),
     "immtsf_neural_flow_forward": (C.c_int, [_P(NeuralFlowDims)] + [c_f32p] * 10 + [c_stream]),
     "immtsf_neural_flow_backward": (C.c_int, [_P(NeuralFlowDims)] + [c_f32p] * 11 + [C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_note_embed_supported": (C.c_int, [C.c_int32] * 4),
+    "immtsf_note_embed_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "immtsf_note_embed_tokens": (C.c_int, [c_i32p, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_f32p,
+                                           c_stream]),
+    "immtsf_note_embed_attention": (C.c_int, [c_f32p, C.c_int32, c_i32p] + [C.c_int32] * 4 + [C.c_float, C.c_int32, c_f32p, C.c_void_p,
+                                              c_stream]),
+    "immtsf_note_embed_pool": (C.c_int, [c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p, C.c_float, c_f32p, c_stream]),
     "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,

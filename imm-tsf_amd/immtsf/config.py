@@ -142,6 +142,14 @@ cru_fused = os.environ.get("IMMTSF_CRU_FUSED", "1") != "0"
 # the whole backward over the reprogrammed patch rows only, bf16 weight images in bf16 mode) wherever gpt2_body_supported allows;
 # IMMTSF_TIMELLM_FUSED=0: transformers' GPT2Model on stock PyTorch in fp32 -- the cross-check.  Follows config.precision
 timellm_fused = os.environ.get("IMMTSF_TIMELLM_FUSED", "1") != "0"
+# Raw-text mode (fusions.load_llm.embed_notes, immtsf.text.embed_corpus): a frozen GPT2Model over the notes' REAL tokens only, packed
+# back to back (immtsf.ops.gpt2_embed_notes: csrc/note_embed.hip + the GEMM family + the row kernels of csrc/gpt2.hip), wherever
+# gpt2_embed_notes_supported allows and the tokenizer pads on the right; IMMTSF_NOTE_EMBED_FUSED=0: the reference's formulation (every
+# note padded to max_length, transformers' model on stock PyTorch, masked mean) -- the cross-check.  Follows config.precision
+note_embed_fused = os.environ.get("IMMTSF_NOTE_EMBED_FUSED", "1") != "0"
+# ... in fp32 mode only for calls of at least this many notes: a single note per call measured 0.88x of the padded call there (the
+# small-row fp32 GEMMs), several notes 2.4x.  bf16 mode takes the fused path at any count (2.6x / 7.0x)
+note_embed_fp32_min_notes = int(os.environ.get("IMMTSF_NOTE_EMBED_FP32_MIN_NOTES", "2"))
 # LatentODE's forecasting() as one HIP launch forward and two backward (csrc/latent_ode.hip) wherever the encoder is the ODE-RNN with
 # rec_layers = gen_layers = 1, one trajectory sample, and immtsf_latent_ode_supported allows; IMMTSF_LATENTODE_FUSED=0: the composed path
 # (the reference's loop over the observed points on torch ops, the step plan copied to the host once) -- the cross-check.  fp32 in

@@ -3293,6 +3293,107 @@ def gpt2_body(llm_model, prefix_embeds, tail_embeds, training, precision=None, s
     return GPT2BodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), int(seed) & 0xFFFFFFFFFFFFFFFF, need_bwd)
 
 
+# ------------------------------------------------------------------------------------------------ raw-text mode: notes through a frozen GPT-2
+def gpt2_embed_notes_supported(llm_model, max_len):
+    """the limits of gpt2_embed_notes: gpt2_body_supported's conditions on the model (a transformers GPT2Model with head_dim 64, gelu_new,
+    scaled attention weights, neither the inverse-layer scale nor the reordered up-cast attention, no cross attention, fp32 parameters,
+    d and the MLP width multiples of 8) and 1 <= max_len <= n_positions, <= 1024"""
+    from transformers import GPT2Model
+    if not isinstance(llm_model, GPT2Model) or max_len < 1:
+        return False
+    cfg = llm_model.config
+    d, H = int(cfg.n_embd), int(cfg.n_head)
+    if (cfg.activation_function != "gelu_new" or not cfg.scale_attn_weights or cfg.scale_attn_by_inverse_layer_idx or
+            cfg.reorder_and_upcast_attn or getattr(cfg, "add_cross_attention", False) or len(llm_model.h) < 1):
+        return False
+    if d % 8 or _gpt2_inner(cfg) % 8 or any(p.dtype != torch.float32 for p in llm_model.parameters()):
+        return False
+    return bool(_lib.load().immtsf_note_embed_supported(d, H, int(max_len), int(cfg.n_positions)))
+
+
+def gpt2_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
+    """pooled (N, d) fp32: the mean over each note's tokens of the frozen GPT2Model's last hidden state -- reference
+    fusions/load_llm.py embed_notes without the padding (csrc/note_embed.hip + the GEMM family + the row kernels of csrc/gpt2.hip over the
+    packed rows).  ids (sum L) int32: the notes' real tokens back to back; cu (N + 1) int32: prefix sums of the token counts; both on the
+    model's device.  A note of no tokens gives an exact zero row.  max_len: an upper bound of the token counts (read from cu when not
+    given: one device -> host copy).  The model's parameters are read in place (the bf16 weight images of bf16 mode are gpt2_body's
+    cache); runs under no_grad and saves nothing.  Outside gpt2_embed_notes_supported this raises: callers check."""
+    with torch.no_grad():
+        _need_gpu(ids, cu)
+        if ids.dtype != torch.int32 or cu.dtype != torch.int32 or ids.dim() != 1 or cu.dim() != 1 or cu.numel() < 1:
+            raise _lib.ImmtsfError("gpt2_embed_notes: ids (sum L) and cu (N + 1) are int32 vectors")
+        ids, cu = _c(ids), _c(cu)
+        N, T = cu.numel() - 1, ids.numel()
+        cfg = llm_model.config
+        d = int(cfg.n_embd)
+        dev = ids.device
+        if N == 0:
+            return torch.zeros(0, d, dtype=torch.float32, device=dev)
+        if max_len is None:
+            max_len = int((cu[1:] - cu[:-1]).max()) if T else 1
+        max_len = max(int(max_len), 1)
+        if not gpt2_embed_notes_supported(llm_model, max_len):
+            raise _lib.ImmtsfError("gpt2_embed_notes: this model / note length is outside gpt2_embed_notes_supported")
+        if T >= 2 ** 31 // (4 * max(d, _gpt2_inner(cfg))):
+            raise _lib.ImmtsfError("gpt2_embed_notes: too many tokens for one call (split the batch)")
+        lib = _lib.load()
+        st = stream_ptr()
+        precision = config.precision_code(precision)
+        bf = precision == 1
+        H, inner = int(cfg.n_head), _gpt2_inner(cfg)
+        eps = float(cfg.layer_norm_epsilon)
+        scale = 1.0 / float(d // H) ** 0.5
+        pooled = torch.empty(N, d, dtype=torch.float32, device=dev)
+        if T == 0:
+            return pooled.zero_()
+        # one workspace for the whole pass, carved as include/immtsf.h lists it
+        ws = _bytes(lib.immtsf_note_embed_workspace_bytes(T, d, inner, precision), dev)
+        off = [0]
+
+        def carve(cols, op=False):
+            dt = torch.bfloat16 if (op and bf) else torch.float32
+            nbytes = T * cols * (2 if dt == torch.bfloat16 else 4)
+            t = ws[off[0]:off[0] + nbytes].view(dt).view(T, cols)
+            off[0] += (nbytes + 255) & ~255
+            return t
+
+        x, x1, h, qkv, ao, pr, pre, act = (carve(d), carve(d), carve(d, True), carve(3 * d), carve(d, True), carve(d), carve(inner),
+                                           carve(inner, True))
+        assert off[0] <= ws.numel()
+        a32 = lambda t: None if bf else ptr(t)      # noqa: E731
+        a16 = lambda t: ptr(t) if bf else None      # noqa: E731
+
+        def mm(a, conv, N_out, K, out):
+            W = conv.weight
+            check(lib.immtsf_gpt2_gemm(1, precision, a32(a), a16(a), K, ptr(W), ptr(_gpt2_w16(llm_model, W)) if bf else None, W.shape[1],
+                                       ptr(out), N_out, ptr(conv.bias), T, N_out, K, st), "gpt2_gemm")
+
+        def ln(src, norm, dst):
+            check(lib.immtsf_gpt2_layernorm(ptr(src), 1, T, 0, d, ptr(norm.weight), ptr(norm.bias), eps, a32(dst), a16(dst), None, None, st),
+                  "gpt2_layernorm")
+
+        def add(base, y, dst):
+            check(lib.immtsf_gpt2_residual(ptr(base), 1, T, 0, T, T, 0, d, ptr(y), 0.0, 0, 0, ptr(dst), st), "gpt2_residual")
+
+        check(lib.immtsf_note_embed_tokens(ptr(ids), ptr(cu), N, T, ptr(llm_model.wte.weight), int(llm_model.wte.weight.shape[0]),
+                                           ptr(llm_model.wpe.weight), int(llm_model.wpe.weight.shape[0]), d, ptr(x), st), "note_embed_tokens")
+        for blk in llm_model.h:
+            ln(x, blk.ln_1, h)
+            mm(h, blk.attn.c_attn, 3 * d, d, qkv)
+            check(lib.immtsf_note_embed_attention(ptr(qkv), 3 * d, ptr(cu), N, T, H, max_len, scale, precision, a32(ao), a16(ao), st),
+                  "note_embed_attention")
+            mm(ao, blk.attn.c_proj, d, d, pr)
+            add(x, pr, x1)
+            ln(x1, blk.ln_2, h)
+            mm(h, blk.mlp.c_fc, inner, d, pre)
+            check(lib.immtsf_gpt2_gelu(ptr(pre), pre.numel(), a32(act), a16(act), st), "gpt2_gelu")
+            mm(act, blk.mlp.c_proj, d, inner, pr)
+            add(x1, pr, x)
+        check(lib.immtsf_note_embed_pool(ptr(x), ptr(cu), N, T, d, ptr(llm_model.ln_f.weight), ptr(llm_model.ln_f.bias), eps, ptr(pooled), st),
+              "note_embed_pool")
+        return pooled
+
+
 # ------------------------------------------------------------------------------------------------ LatentODE backbone
 def _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents):
     return _lib.LatentODEDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(units), int(gru_units), int(latents))

@@ -774,6 +774,32 @@ int immtsf_neural_flow_backward(const immtsf_neural_flow_dims* dims, const float
                                 const float* zs, const float* d_out, float* grads, void* workspace, size_t workspace_bytes,
                                 immtsf_stream_t stream);
 
+/* ---- Raw-text mode (added within ABI 7: new functions only; csrc/note_embed.hip): what immtsf.ops.gpt2_embed_notes composes with
+ * immtsf_gpt2_gemm and the row kernels of the GPT-2 body (run with B = 1 over the packed rows, p_drop = 0) into reference
+ * fusions/load_llm.py embed_notes for a frozen GPT2Model -- over the RAGGED tokens: ids (rows) int32, the notes back to back; cu (N + 1)
+ * int32 prefix sums of the notes' token counts, on the device (cu[0] = 0, cu[N] = rows).  A causal model with a right-padding tokenizer
+ * gives a real token the same hidden state with or without the padding, and the mean-pool reads real tokens only, so the result is
+ * the padded formulation's.  Forward only, no dropout, no atomics, fixed summation order (the same inputs give the same bits).
+ * ..._supported: d == 64 H, H <= 65535, 1 <= max_len <= n_positions, max_len <= 1024 (max_len: an upper bound of every note's length).
+ * ..._workspace_bytes: the activations of one pass, each buffer rounded up to 256 bytes, in this order: x, x1 (rows, d) fp32; h (rows, d)
+ *   fp32 | bf16; qkv (rows, 3 d) fp32; ao (rows, d) fp32 | bf16; proj (rows, d) fp32; pre (rows, inner) fp32; act (rows, inner) fp32 |
+ *   bf16 -- bf16 in precision 1 (the GEMM operand images).  Host arithmetic only.
+ * ..._tokens: out[r, :] = wte[ids[r], :] + wpe[r - cu[n], :] for row r of note n (ids and positions are clamped into their tables).
+ * ..._attention: causal attention inside each note: qkv (rows; pitch ld >= 3 d) is c_attn's output (q | k | v, head h at columns 64 h of
+ *   each), query p of note n sees keys 0 .. p of note n; out32 / out16 (rows, d): the layout c_proj reads (either may be null).  scale
+ *   multiplies q . k.  precision 0: fp32 on the VALU; 1: both products on bf16 MFMA with fp32 accumulation, fp32 online softmax.  Grid
+ *   (note, head, query tile of 64 in reverse order): the tiles with the most keys start first; a note longer than max_len is cut there.
+ * ..._pool: pooled[n, :] = sum over note n's rows, in position order, of LayerNorm(x[row]; gamma, beta, eps), divided by max(L, 1): a note
+ *   of no tokens gives an exact zero row.  A note whose range does not lie in [0, rows) or is longer than 1024 counts as empty. */
+int immtsf_note_embed_supported(int32_t d, int32_t H, int32_t max_len, int32_t n_positions);
+size_t immtsf_note_embed_workspace_bytes(int64_t rows, int32_t d, int32_t inner, int32_t precision);
+int immtsf_note_embed_tokens(const int32_t* ids, const int32_t* cu, int32_t N, int32_t rows, const float* wte, int32_t vocab, const float* wpe,
+                             int32_t n_positions, int32_t d, float* out, immtsf_stream_t stream);
+int immtsf_note_embed_attention(const float* qkv, int32_t ld, const int32_t* cu, int32_t N, int32_t rows, int32_t H, int32_t max_len,
+                                float scale, int32_t precision, float* out32, void* out16, immtsf_stream_t stream);
+int immtsf_note_embed_pool(const float* x, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const float* gamma, const float* beta,
+                           float eps, float* pooled, immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Raw-text mode's note embedding, fused (fusions.load_llm.embed_notes -> immtsf.ops.gpt2_embed_notes: the real tokens only, packed;
+csrc/note_embed.hip + the GEMM family) against IMMTSF_NOTE_EMBED_FUSED=0 (the reference's formulation: every note padded to max_length,
+transformers' GPT2Model on stock PyTorch, masked mean), on the same GPU.  Shape: GPT-2 small (12 layers, 768 wide, 12 heads, random
+weights, max_length 1024) behind a stand-in tokenizer (one token per byte, right-padded).  Two workloads, the note lengths printed:
+  batch : one embed_notes call over `--notes` notes of mixed length (most short, a few long, one of 1024 tokens)
+  single: the same notes one call each, as the reference's compute_text_embeddings.py makes them
+The stock path runs the batch in slices of `--stock-slice` notes (a padded batch of all of them does not fit a sensible budget); the
+row-count ratio sum(L) / (N * max_length) -- what the algorithm alone saves -- is printed beside the times.  In ONE process, after
+warming both paths: `--passes` alternating passes, host clock around a pass with a synchronise at its end.  One JSON line per
+precision mode: milliseconds per workload, best pass and all passes (their spread is the noise).
+
+usage: python tools/note_embed_bench.py [--notes 32] [--passes 3] [--single 8] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "imm-tsf_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+MAX_LENGTH = 1024
+
+
+class ByteTokenizer:
+    """stand-in: one token per byte (ids < 256), right-padded to max_length with the pad id, with the attention mask"""
+    padding_side = "right"
+
+    def __call__(self, texts, padding="max_length", truncation=True, max_length=MAX_LENGTH, return_tensors="pt"):
+        import torch
+        ids = torch.zeros(len(texts), max_length, dtype=torch.long)
+        attn = torch.zeros(len(texts), max_length, dtype=torch.long)
+        for r, t in enumerate(texts):
+            b = list(t.encode("utf-8"))[:max_length]
+            ids[r, :len(b)] = torch.tensor(b, dtype=torch.long)
+            attn[r, :len(b)] = 1
+        return type("Enc", (), {"input_ids": ids, "attention_mask": attn})()
+
+
+def note_lengths(n):
+    """most notes short (tens of tokens), some a few hundred, one at the cap"""
+    base = [24, 48, 40, 96, 64, 200, 32, 56, 80, 320, 28, 72, 44, 150, 36, 1024]
+    return [base[i % len(base)] for i in range(n)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--notes", type=int, default=32)
+    ap.add_argument("--single", type=int, default=8, help="notes of the one-call-per-note workload (the first ones of the mix)")
+    ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--stock-slice", type=int, default=8)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from transformers import GPT2Config, GPT2Model
+
+    from fusions import load_llm as L
+    from immtsf import config
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = GPT2Model(GPT2Config(vocab_size=256, bos_token_id=0, eos_token_id=0)).requires_grad_(False).to(dev).eval()
+    tok = ByteTokenizer()
+    lengths = note_lengths(args.notes)
+    notes = [chr(97 + i % 26) * n for i, n in enumerate(lengths)]
+    ratio = sum(lengths) / (len(lengths) * MAX_LENGTH)
+    print(f"note lengths (tokens): {lengths}", flush=True)
+    print(f"rows: real {sum(lengths)} of padded {len(lengths) * MAX_LENGTH} (ratio {ratio:.4f})", flush=True)
+
+    def batch(fused):
+        config.note_embed_fused = fused
+        with torch.no_grad():
+            if fused:
+                L.embed_notes([notes], tok, model, max_length=MAX_LENGTH)
+            else:
+                for i in range(0, len(notes), args.stock_slice):
+                    L.embed_notes([notes[i:i + args.stock_slice]], tok, model, max_length=MAX_LENGTH)
+
+    def single(fused):
+        config.note_embed_fused = fused
+        with torch.no_grad():
+            for note in notes[:args.single]:
+                L.embed_notes([[note]], tok, model, max_length=MAX_LENGTH)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    lines = []
+    for prec in ("fp32", "bf16"):
+        config.precision = prec
+        line = {"tool": "note_embed_bench", "precision": prec, "layers": 12, "d": 768, "max_length": MAX_LENGTH, "notes": len(notes),
+                "row_ratio": round(ratio, 4), "single_notes": args.single, "single_row_ratio":
+                round(sum(lengths[:args.single]) / (args.single * MAX_LENGTH), 4), "passes": args.passes}
+        for what, fn in (("batch", batch), ("single", single)):
+            for fused in (True, False):
+                fn(fused)
+            t = {True: [], False: []}
+            for _ in range(args.passes):
+                for fused in (True, False):
+                    t[fused].append(timed(lambda: fn(fused)))
+            for fused, name in ((True, "fused"), (False, "stock")):
+                line[f"{what}_{name}_ms"] = round(min(t[fused]), 3)
+                line[f"{what}_{name}_ms_passes"] = [round(v, 3) for v in t[fused]]
+            line[f"{what}_speedup"] = round(min(t[False]) / min(t[True]), 2)
+        config.note_embed_fused = True
+        print(json.dumps(line), flush=True)
+        lines.append(json.dumps(line))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
