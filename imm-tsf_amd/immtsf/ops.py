@@ -126,28 +126,65 @@ def _bytes(n, dev):
     return torch.empty(max(int(n), 1), dtype=torch.uint8, device=dev)
 
 
+# ---- idioms of the fused backbones (one launch reads every parameter through a pointer table, one flat buffer takes every gradient)
+_pointer_tables = {}      # owner: _pointer_table.  Never emptied: a captured graph keeps reading the table it was captured with
+_grad_layouts = {}        # owner: _grad_layout.  (library entry, dims) -> (offsets, length): a few ints per shape ever seen
+
+
+def _pointer_table(params, device):
+    """the device array of parameter pointers a fused backbone kernel reads, in the order of `params`: one host -> device copy per
+    distinct set of storages (so the first call with a new set has to be outside a stream capture, as every warm-up run is)"""
+    key = (device.type, device.index) + tuple(p.data_ptr() for p in params)
+    t = _pointer_tables.get(key)
+    if t is None:
+        t = _pointer_tables[key] = torch.tensor(key[2:], dtype=torch.int64, device=device)
+    return t
+
+
+def _grad_layout(lib_fn, dims, n_entries, what):
+    """-> (float offset of each of the `n_entries` table entries in the flat gradient that the library entry named `lib_fn` lays out for
+    `dims`, -1 = none; the flat gradient's length).  what: the error text for dimensions the library refuses."""
+    got = _grad_layouts.get((lib_fn, dims))
+    if got is None:
+        offs = torch.full((n_entries,), -1, dtype=torch.int32)
+        nv = int(getattr(_lib.load(), lib_fn)(*dims, offs.data_ptr(), n_entries))
+        if nv < 0:
+            raise _lib.ImmtsfError(what)
+        got = _grad_layouts[(lib_fn, dims)] = (offs.tolist(), nv)
+    return got
+
+
+def _flat_views(flat, offs, shapes, needs):
+    """the flat gradient cut into per-parameter views (None where autograd wants none, or the layout has none)"""
+    rets = []
+    for o, shape, need in zip(offs, shapes, needs):
+        numel = 1
+        for s in shape:
+            numel *= s
+        rets.append(flat[o:o + numel].view(shape) if need and o >= 0 else None)
+    return rets
+
+
+def _kernel_drop(p, site, device):
+    """(p, seed, site, counter pointer) of a dropout drawn inside a fused kernel: one config.next_seed() when p > 0, none otherwise"""
+    return (p, config.next_seed() if p > 0 else 0, site, config.dropout_counter_ptr(device) if p > 0 else None)
+
+
+def _dims_supported(supported_fn, workspace_fn, dims_struct, call):
+    """a dims-struct backbone's limits: the library's `supported` entry and, for a compute call, a positive workspace size"""
+    if not supported_fn(C.byref(dims_struct)):
+        return False
+    return bool(workspace_fn(C.byref(dims_struct)) > 0) if call else True
+
+
 # ---- bf16 images of activations that cross a block boundary (bf16 mode).  The producer registers (fp32 tensor, bf16
 # image); a consumer that is handed the SAME, unmodified fp32 data finds the image and skips its cast kernel.  The registry
 # holds the fp32 tensor's STORAGE (so the address cannot be recycled under a stale entry) but not the tensor: a gradient that a
 # backward returns must stay un-referenced, or autograd's AccumulateGrad clones it instead of taking it (a copy launch on the
 # serial section in front of the backbone's backward, and the clone then misses its image: a cast launch more).
+# All three registries below are owned by the fusion blocks (TTF* / MMF* Functions), which reach them through _reg_put / _reg_take alone.
 _shadows = []          # [(storage, data_ptr, shape, version, bf16 tensor)], newest last, at most _SHADOW_CAP entries
 _SHADOW_CAP = 6
-
-
-def _shadow_put(t, h):
-    _shadows.append((t.untyped_storage(), t.data_ptr(), tuple(t.shape), t._version, h))
-    if len(_shadows) > _SHADOW_CAP:
-        del _shadows[0]
-
-
-def _shadow_get(x):
-    if not x.is_contiguous():
-        return None
-    for _st, p, shape, ver, h in reversed(_shadows):
-        if p == x.data_ptr() and shape == tuple(x.shape) and x._version == ver:
-            return h
-    return None
 
 
 # ---- hand-over of the fused tail (config.z_handover).  Forward: the producer (TTFT2VXAttnFn) registers its output Z with the cfg of its
@@ -265,7 +302,7 @@ class TTFT2VXAttnFn(torch.autograd.Function):
                                                    ws.numel(), ptr(nan_flag), stream_ptr()), "ttf_t2v_xattn_forward")
         cfg.out_h = None
         if E_h is not None:
-            _shadow_put(E, E_h)
+            _reg_put(_shadows, E, E_h)
         if handover:
             _reg_put(_handover, E, (cfg, bool(cfg.form & _lib.FORM_HALF_OUT)))
         ctx.cfg, ctx.ws, ctx.src_rows = cfg, ws, src_rows
@@ -297,7 +334,7 @@ class TTFT2VXAttnFn(torch.autograd.Function):
         sc = _bytes(lib.immtsf_ttf_t2v_xattn_scratch_bytes(C.byref(ctx.cfg)), notes.device)
         ps, gs = _struct(T2VParams, params), _struct(T2VParams, grads)
         ctx.cfg.sched_flag = ctx.gate
-        dE_h = _shadow_get(dE) if _bf16_dataflow(ctx.cfg.precision, ctx.cfg.d) else None
+        dE_h = _reg_take(_shadows, dE) if _bf16_dataflow(ctx.cfg.precision, ctx.cfg.d) else None
         ctx.cfg.in_h = None if dE_h is None else dE_h.data_ptr()
         lowrank = _reg_take(_lowrank, dE, pop=True) if ctx.no_proj else None      # (dE is then an unwritten placeholder: dZ = coef basis)
         ctx.cfg.lr_grad = None if lowrank is None else C.addressof(lowrank[0])
@@ -488,7 +525,7 @@ class MMFXAttnKVFn(torch.autograd.Function):
         ws = _bytes(lib.immtsf_mmf_xattn_kv_workspace_bytes(C.byref(cfg)), E.device)
         KV = torch.empty(B, T, 2 * d, dtype=torch.float32, device=E.device)
         ps = _struct(XAddParams, params)
-        E_h = _shadow_get(E) if _bf16_dataflow(precision, d) else None
+        E_h = _reg_take(_shadows, E) if _bf16_dataflow(precision, d) else None
         cfg.in_h = None if E_h is None else E_h.data_ptr()
         ctx.E_h = E_h
         check(lib.immtsf_mmf_xattn_kv_forward(C.byref(cfg), C.byref(ps), ptr(E), ptr(KV), ptr(ws), ws.numel(), stream_ptr()),
@@ -512,7 +549,7 @@ class MMFXAttnKVFn(torch.autograd.Function):
         dKV = dKV.contiguous()
         cfg, dE_h = ctx.cfg, None
         if _bf16_dataflow(cfg.precision, cfg.d):
-            dKV_h = _shadow_get(dKV)
+            dKV_h = _reg_take(_shadows, dKV)
             cfg.in_h = None if dKV_h is None else dKV_h.data_ptr()
             cfg.aux_h = None if ctx.E_h is None else ctx.E_h.data_ptr()
             dE_h = torch.empty(dE.shape, dtype=torch.bfloat16, device=dE.device)
@@ -521,7 +558,7 @@ class MMFXAttnKVFn(torch.autograd.Function):
                                                ctx.ws.numel(), ptr(sc), sc.numel(), C.byref(gs), stream_ptr()),
               "mmf_xattn_kv_backward")
         if dE_h is not None:
-            _shadow_put(dE, dE_h)
+            _reg_put(_shadows, dE, dE_h)
         _fire(ctx.done_hook)
         return (dE, None, None, None) + tuple(rets[1:5])
 
@@ -583,7 +620,7 @@ class MMFXAttnQFn(torch.autograd.Function):
                                               1 if defer else 0, stream_ptr()), "mmf_xattn_q_backward")
         cfg.out_h = None
         if dKV_h is not None:
-            _shadow_put(dKV, dKV_h)
+            _reg_put(_shadows, dKV, dKV_h)
         if defer:
             keep = (Y, M_u8, params, grads)         # the closure keeps every buffer it touches alive
 
@@ -628,7 +665,7 @@ class MMFXRankPFn(torch.autograd.Function):
         P = torch.empty(B, T, pw, dtype=torch.float32, device=E.device)
         bHO = torch.empty(Cc, dtype=torch.float32, device=E.device)
         ps = _struct(XAddParams, params)
-        E_h = _shadow_get(E) if _bf16_dataflow(precision, d) else None
+        E_h = _reg_take(_shadows, E) if _bf16_dataflow(precision, d) else None
         cfg.in_h = None if E_h is None else E_h.data_ptr()
         ctx.E_h = E_h
         # the fused tail's hand-over (config.z_handover): did the producer promise to take a low-rank gradient for this Z?
@@ -682,7 +719,7 @@ class MMFXRankPFn(torch.autograd.Function):
         dbHO = torch.zeros(cfg.C, dtype=torch.float32, device=E.device) if dbHO is None else dbHO.contiguous()
         dE_h = None
         if _bf16_dataflow(cfg.precision, cfg.d):
-            dP_h = _shadow_get(dP)
+            dP_h = _reg_take(_shadows, dP)
             cfg.in_h = None if dP_h is None else dP_h.data_ptr()
             cfg.aux_h = None if ctx.E_h is None else ctx.E_h.data_ptr()
             if proj is None:        # ("_z" form: the producer's backward reads dZ as fp32 rows only)
@@ -736,7 +773,7 @@ class MMFXRankPFn(torch.autograd.Function):
             data_half()
             params_chain(stream_ptr())
         if dE_h is not None:
-            _shadow_put(dE, dE_h)
+            _reg_put(_shadows, dE, dE_h)
         if lowrank:
             basis, rank = C.c_void_p(), C.c_int32()
             check(lib.immtsf_mmf_xrank_lowrank_basis(C.byref(cfg), ptr(ctx.ws), ctx.ws.numel(), C.byref(basis), C.byref(rank)),
@@ -784,11 +821,11 @@ class MMFXRankQFn(torch.autograd.Function):
               "mmf_xrank_q_backward")
         cfg.out_h = None
         if dP_h is not None:
-            _shadow_put(dP, dP_h)
+            _reg_put(_shadows, dP, dP_h)
         return (dY, dP, dbHO, None, None, None, None, None, None, None, None) + tuple(rets)
 
 
-_xq_tickets = {}
+_xq_tickets = {}       # owner: _xq_ticket.  (device type, index) -> the ticket words of the two *_q_train kernels
 
 
 def _xq_ticket(device) -> torch.Tensor:
@@ -836,7 +873,7 @@ class MMFXRankQLossFn(torch.autograd.Function):
                                            ptr(cnt), 1.0, None, ptr(loss), ptr(dY), ptr(dP), ptr(dbHO), ptr(grads[0]), ptr(grads[1]),
                                            ptr(sc), sc.numel(), ptr(_xq_ticket(Y.device)), flag, stream_ptr()), "mmf_xrank_q_train")
         if dP_h is not None:
-            _shadow_put(dP, dP_h)
+            _reg_put(_shadows, dP, dP_h)
         ctx.grads = (dY, dP, dbHO) + tuple(rets)
         # LayerNorm's two gradients went straight to FlatTrainer's sinks (rets None): they were written with the unit seed, so a
         # backward with any other seed (loss scaling, loss * k) has to rescale them where they lie
@@ -918,7 +955,7 @@ class MMFGRPFn(torch.autograd.Function):
             raise _lib.ImmtsfError("MMF_GR_Add split form: shape outside its limits")
         ws = _bytes(lib.immtsf_mmf_gr_p_workspace_bytes(C.byref(cfg), hidden), E.device)
         P = torch.empty(B, T, pw, dtype=torch.float32, device=E.device)
-        E_h = _shadow_get(E) if _bf16_dataflow(precision, d) else None
+        E_h = _reg_take(_shadows, E) if _bf16_dataflow(precision, d) else None
         cfg.in_h = None if E_h is None else E_h.data_ptr()
         ps = _struct(GRParams, params)
         check(lib.immtsf_mmf_gr_p_forward(C.byref(cfg), hidden, C.byref(ps), ptr(E), ptr(P), ptr(ws), ws.numel(), stream_ptr()),
@@ -956,7 +993,7 @@ class MMFGRPFn(torch.autograd.Function):
                                            sc.numel(), C.byref(gs), stream_ptr()), "mmf_gr_p_backward")
         cfg.aux_h = cfg.out_h = None
         if dE_h is not None:
-            _shadow_put(dE, dE_h)
+            _reg_put(_shadows, dE, dE_h)
         _fire(getattr(params[0], "_immtsf_bwd_hook", None))      # (the block's gradients are final once THIS half's backward has run)
         return (dE, None, None, None) + tuple(rets)
 
@@ -2404,7 +2441,7 @@ class MaskedMSEFn(torch.autograd.Function):
 
 
 _MSE_SMALL_MAX = 1 << 17        # IMMTSF_MSE_SMALL_MAX
-_mse_scratch_cache = {}
+_mse_scratch_cache = {}         # owner: _mse_scratch.  (device type, index) -> the device's ticket + partial-loss buffer
 
 
 def _mse_scratch(device) -> torch.Tensor:
@@ -2416,7 +2453,9 @@ def _mse_scratch(device) -> torch.Tensor:
     if t is None:
         t = _mse_scratch_cache[key] = torch.zeros(65, dtype=torch.float32, device=device)
     return t
-_unit_grads = {}
+
+
+_unit_grads = {}                # owner: unit_grad / is_unit_grad.  (device type, index) -> the device's constant 1.0
 
 
 def unit_grad(device) -> torch.Tensor:
@@ -2474,7 +2513,7 @@ class EvalScratch:
         return b, self.ticket
 
 
-_eval_default = {}
+_eval_default = {}              # owner: _eval_scratch.  (device type, index) -> the EvalScratch of callers that pass none
 
 
 def _eval_scratch(device, nbytes, scratch=None):
@@ -2533,22 +2572,9 @@ def mmf_xrank_q_eval(Y, P, bHO, M_u8, truth, mask, acc, d, H, kappa, precision, 
 
 
 # ------------------------------------------------------------------------------------------------ DLinear backbone
-_dl_tables = {}      # never emptied: a captured graph keeps reading the table it was captured with
-
-
 def dlinear_supported(S, P, Cc, k, individual):
     """the limits of the fused DLinear path (immtsf_dlinear_supported): 1 <= S, P <= 128, odd k >= 1, any C >= 1"""
     return bool(_lib.load().immtsf_dlinear_supported(int(S), int(P), int(Cc), int(k), 1 if individual else 0))
-
-
-def _dlinear_table(params, device):
-    """the device array of parameter pointers immtsf_dlinear_forward reads, [Ws | Wt | Wtau | bs | bt | btau][channel]: one host -> device
-    copy per distinct set of storages (so the first call with a new set has to be outside a stream capture, as every warm-up run is)"""
-    key = (device.type, device.index) + tuple(p.data_ptr() for p in params)
-    t = _dl_tables.get(key)
-    if t is None:
-        t = _dl_tables[key] = torch.tensor(key[2:], dtype=torch.int64, device=device)
-    return t
 
 
 class DLinearFn(torch.autograd.Function):
@@ -2604,14 +2630,13 @@ def dlinear_forecast(data, mask, tp, Lp, S, P, k, seasonal, trend, time):
     if not dlinear_supported(S, P, Cc, k, individual) or not (0 <= L <= S and 0 <= Lp <= P) or B < 1 or \
             tuple(mask.shape) != (B, L, Cc) or tuple(tp.shape) != (B, L):
         raise _lib.ImmtsfError(f"dlinear_forecast: shapes outside the fused kernel (B {B}, L {L}, C {Cc}, S {S}, P {P}, Lp {Lp}, k {k})")
-    return DLinearFn.apply(data, mask, tp, (int(S), int(P), int(Lp), int(k), 1 if individual else 0), _dlinear_table(params, data.device),
+    # (the table immtsf_dlinear_forward reads: [Ws | Wt | Wtau | bs | bt | btau][channel])
+    return DLinearFn.apply(data, mask, tp, (int(S), int(P), int(Lp), int(k), 1 if individual else 0), _pointer_table(params, data.device),
                            *params)
 
 
 # ------------------------------------------------------------------------------------------------ TimeMixer backbone
 SITE_TIMEMIXER_EMBED = SITE_LAYER_BASE + 42      # the embedding's dropout inside csrc/timemixer.hip: element ((off_i B + b T_i + t) d + f)
-_tm_tables = {}      # never emptied: a captured graph keeps reading the table it was captured with
-_tm_layouts = {}
 
 
 def timemixer_supported(S, P, Cc, d_model, d_ff, e_layers, down_layers, moving_avg):
@@ -2636,15 +2661,9 @@ def timemixer_params(model):
 
 def _timemixer_layout(dims):
     """-> (float offset of every table entry in the flat gradient, -1 = none; the flat gradient's length)"""
-    got = _tm_layouts.get(dims)
-    if got is None:
-        S, P, Cc, d, dff, E, n, _ = dims
-        offs = torch.full((2 + E * (8 * n + 4) + 4,), -1, dtype=torch.int32)
-        nv = int(_lib.load().immtsf_timemixer_grad_layout(S, P, Cc, d, dff, E, n, offs.data_ptr(), offs.numel()))
-        if nv < 0:
-            raise _lib.ImmtsfError(f"timemixer: dimensions outside the fused kernel {dims}")
-        got = _tm_layouts[dims] = (offs.tolist(), nv)
-    return got
+    E, n = dims[5], dims[6]
+    return _grad_layout("immtsf_timemixer_grad_layout", dims[:7], 2 + E * (8 * n + 4) + 4,
+                        f"timemixer: dimensions outside the fused kernel {dims}")
 
 
 class TimeMixerFn(torch.autograd.Function):
@@ -2683,13 +2702,7 @@ class TimeMixerFn(torch.autograd.Function):
         check(lib.immtsf_timemixer_backward(B, L, Cc, S, P, Lp, d, dff, E, n, k, ptr(data), ptr(mask), ptr(tp), ptr(ctx.table),
                                             ptr(dY.contiguous()), ptr(flat), p, seed, site, cnt, ptr(ws), ws.numel(), stream_ptr()),
               "timemixer_backward")
-        rets = []
-        for o, shape, need in zip(offs, ctx.shapes, ctx.needs_input_grad[7:]):
-            numel = 1
-            for s in shape:
-                numel *= s
-            rets.append(flat[o:o + numel].view(shape) if need and o >= 0 else None)
-        return (None,) * 7 + tuple(rets)
+        return (None,) * 7 + tuple(_flat_views(flat, offs, ctx.shapes, ctx.needs_input_grad[7:]))
 
 
 def timemixer_forecast(model, data, mask, tp, Lp):
@@ -2719,12 +2732,9 @@ def timemixer_forecast(model, data, mask, tp, Lp):
     if any(not q.is_contiguous() or q.dtype != torch.float32 for q in params) or pe.dim() != 3 or pe.shape[1] < S or pe.shape[2] != d or \
             any(w is not None and tuple(q.shape) != w for q, w in zip(params, want)):
         raise _lib.ImmtsfError("timemixer_forecast: the module's parameters are not the contiguous fp32 tensors of these dimensions")
-    key = (data.device.type, data.device.index) + tuple(q.data_ptr() for q in params)
-    table = _tm_tables.get(key)
-    if table is None:      # one host -> device copy per distinct set of storages: outside a stream capture, as every warm-up run is
-        table = _tm_tables[key] = torch.tensor(key[2:], dtype=torch.int64, device=data.device)
+    table = _pointer_table(params, data.device)
     p = float(model.enc_embedding.dropout.p) if model.training else 0.0
-    drop = (p, config.next_seed() if p > 0 else 0, SITE_TIMEMIXER_EMBED, config.dropout_counter_ptr(data.device) if p > 0 else None)
+    drop = _kernel_drop(p, SITE_TIMEMIXER_EMBED, data.device)
     model._last_drop = drop      # (p, seed, site, counter pointer) of this module's latest fused call: what dropout_keep_mask reproduces
     return TimeMixerFn.apply(data, mask, tp, int(Lp), dims, drop, table, *params)
 
@@ -2835,7 +2845,7 @@ def ttm_mixer(block, x, mode, training):
     p = float(block.mlp.dropout1.p) if training else 0.0
     if p > 0 and float(block.mlp.dropout2.p) != p:
         raise _lib.ImmtsfError("ttm_mixer: the two dropouts of a block share one probability")
-    drop = (p, config.next_seed() if p > 0 else 0, SITE_TTM_MIXER, config.dropout_counter_ptr(x.device) if p > 0 else None)
+    drop = _kernel_drop(p, SITE_TTM_MIXER, x.device)
     block._last_drop = drop
     return TTMMixerFn.apply(x, mode, drop, float(block.norm.eps), *params)
 
@@ -2996,9 +3006,6 @@ def conv_distil(x, conv, norm, training, precision=None):
 
 
 # ------------------------------------------------------------------------------------------------ CRU backbone
-_cru_layouts = {}
-
-
 def cru_supported(lsd, num_basis, bandwidth, T):
     """the limits of the fused CRU recurrence (immtsf_cru_supported): lsd even, 2 <= lsd <= 32, num_basis <= 256, bandwidth <= lsd / 2,
     1 <= T <= 2^20"""
@@ -3007,14 +3014,8 @@ def cru_supported(lsd, num_basis, bandwidth, T):
 
 def _cru_layout(lsd, K, bw):
     """-> (the nine float offsets of [tm11 | tm12 | tm21 | tm22 | coef_w | coef_b | trans_var | icu | icl] in the flat gradient, its length)"""
-    got = _cru_layouts.get((lsd, K, bw))
-    if got is None:
-        offs = torch.zeros(9, dtype=torch.int32)
-        nv = int(_lib.load().immtsf_cru_grad_layout(lsd, K, bw, offs.data_ptr(), 9))
-        if nv < 0:
-            raise _lib.ImmtsfError(f"cru_scan: dimensions outside the fused kernel (lsd {lsd}, num_basis {K}, bandwidth {bw})")
-        got = _cru_layouts[(lsd, K, bw)] = (offs.tolist(), nv)
-    return got
+    return _grad_layout("immtsf_cru_grad_layout", (lsd, K, bw), 9,
+                        f"cru_scan: dimensions outside the fused kernel (lsd {lsd}, num_basis {K}, bandwidth {bw})")
 
 
 class CRUScanFn(torch.autograd.Function):
@@ -3056,12 +3057,7 @@ class CRUScanFn(torch.autograd.Function):
         check(lib.immtsf_cru_backward(B, T, lsd, K, bw, ptr(y), ptr(y_var), ptr(valid), ptr(t), *(ptr(q) for q in params), ptr(pm), ptr(cov[0]),
                                       ptr(cov[1]), ptr(cov[2]), ptr(dpm.contiguous()), ptr(dy[0]), ptr(dy[1]), ptr(flat), ptr(ws), ws.numel(),
                                       stream_ptr()), "cru_backward")
-        rets = []
-        for o, shape, need in zip(offs, ctx.shapes, ctx.needs_input_grad[5:]):
-            numel = 1
-            for s in shape:
-                numel *= s
-            rets.append(flat[o:o + numel].view(shape) if need else None)
+        rets = _flat_views(flat, offs, ctx.shapes, ctx.needs_input_grad[5:])
         return (dy[0] if ctx.needs_input_grad[0] else None, dy[1] if ctx.needs_input_grad[1] else None, None, None, None) + tuple(rets)
 
 
@@ -3403,12 +3399,9 @@ def latent_ode_supported(B, L, Lp, C, rec_dims, units, gru_units, latents, call=
     """the limits of the fused LatentODE kernels (immtsf_latent_ode_supported: rec_dims, latents <= 64, units, gru_units <= 128, C <= 64,
     L, Lp <= 2^20, the weights and a tile's state within 160 KB of LDS), from the dims alone; call: also what a compute call needs
     (B >= 1 and the saved state's index range, immtsf_latent_ode_workspace_bytes > 0)"""
-    import ctypes
-    d = _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents)
     lib = _lib.load()
-    if not lib.immtsf_latent_ode_supported(ctypes.byref(d)):
-        return False
-    return bool(lib.immtsf_latent_ode_workspace_bytes(ctypes.byref(d)) > 0) if call else True
+    return _dims_supported(lib.immtsf_latent_ode_supported, lib.immtsf_latent_ode_workspace_bytes,
+                           _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents), call)
 
 
 class LatentODEFn(torch.autograd.Function):
@@ -3418,32 +3411,30 @@ class LatentODEFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, data, mask, steps, step_len, tpp, flat, eps, widths):
-        import ctypes
         lib = _lib.load()
         data, mask, steps, step_len, tpp, flat, eps = (_c(t) for t in (data, mask, steps, step_len, tpp, flat, eps))
         _need_gpu(data, mask, steps, step_len, tpp, flat, eps)
-        B, L, C = data.shape
+        B, L, Cc = data.shape
         Lp = tpp.shape[0]
         R, U, G, Z = widths
-        d = _latent_ode_dims(B, L, Lp, C, R, U, G, Z)
-        out = torch.empty(B, Lp, C, dtype=torch.float32, device=data.device)
+        d = _latent_ode_dims(B, L, Lp, Cc, R, U, G, Z)
+        out = torch.empty(B, Lp, Cc, dtype=torch.float32, device=data.device)
         states = torch.empty(B, L + 1, 2 * R, dtype=torch.float32, device=data.device)
         traj = torch.empty(B, Lp, Z, dtype=torch.float32, device=data.device)
-        check(lib.immtsf_latent_ode_forward(ctypes.byref(d), ptr(data), ptr(mask), ptr(steps), ptr(step_len), ptr(tpp), ptr(flat), ptr(eps),
+        check(lib.immtsf_latent_ode_forward(C.byref(d), ptr(data), ptr(mask), ptr(steps), ptr(step_len), ptr(tpp), ptr(flat), ptr(eps),
                                             ptr(out), ptr(states), ptr(traj), stream_ptr()), "latent_ode_forward")
-        ctx.dims = (B, L, Lp, C, R, U, G, Z)
+        ctx.dims = (B, L, Lp, Cc, R, U, G, Z)
         ctx.save_for_backward(data, mask, steps, step_len, tpp, flat, eps, states, traj)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes
         lib = _lib.load()
         data, mask, steps, step_len, tpp, flat, eps, states, traj = ctx.saved_tensors
         d = _latent_ode_dims(*ctx.dims)
         grads = torch.empty_like(flat)      # every entry is written: no zero fill
-        ws = _bytes(lib.immtsf_latent_ode_workspace_bytes(ctypes.byref(d)), data.device)
-        check(lib.immtsf_latent_ode_backward(ctypes.byref(d), ptr(data), ptr(mask), ptr(steps), ptr(step_len), ptr(tpp), ptr(flat), ptr(eps),
+        ws = _bytes(lib.immtsf_latent_ode_workspace_bytes(C.byref(d)), data.device)
+        check(lib.immtsf_latent_ode_backward(C.byref(d), ptr(data), ptr(mask), ptr(steps), ptr(step_len), ptr(tpp), ptr(flat), ptr(eps),
                                              ptr(states), ptr(traj), ptr(dout.contiguous()), ptr(grads), ptr(ws), ws.numel(), stream_ptr()),
               "latent_ode_backward")
         return None, None, None, None, None, grads, None, None
@@ -3453,15 +3444,14 @@ def latent_ode(data, mask, steps, step_len, tp_pred, flat_params, eps, widths):
     """data, mask (B, L, C); steps (L) int32 / step_len (L): the step plan of the shared time axis (-1: Euler, n >= 1: n RK4 steps, 0:
     none); tp_pred (Lp); flat_params: every parameter in state_dict order, flattened; eps (B, latents); widths = (rec_dims, units,
     gru_units, latents) -> the forecast (B, Lp, C).  Gradients reach flat_params only."""
-    import ctypes
-    B, L, C = data.shape
+    B, L, Cc = data.shape
     Lp = tp_pred.shape[0]
     R, U, G, Z = (int(w) for w in widths)
-    if not latent_ode_supported(B, L, Lp, C, R, U, G, Z, call=True):
-        raise _lib.ImmtsfError(f"latent_ode: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, C {C}, widths {(R, U, G, Z)})")
-    d = _latent_ode_dims(B, L, Lp, C, R, U, G, Z)
-    nv = int(_lib.load().immtsf_latent_ode_param_count(ctypes.byref(d)))
-    if tuple(mask.shape) != (B, L, C) or tuple(steps.shape) != (L,) or tuple(step_len.shape) != (L,) or tp_pred.dim() != 1 or \
+    if not latent_ode_supported(B, L, Lp, Cc, R, U, G, Z, call=True):
+        raise _lib.ImmtsfError(f"latent_ode: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, C {Cc}, widths {(R, U, G, Z)})")
+    d = _latent_ode_dims(B, L, Lp, Cc, R, U, G, Z)
+    nv = int(_lib.load().immtsf_latent_ode_param_count(C.byref(d)))
+    if tuple(mask.shape) != (B, L, Cc) or tuple(steps.shape) != (L,) or tuple(step_len.shape) != (L,) or tp_pred.dim() != 1 or \
             tuple(eps.shape) != (B, Z) or flat_params.numel() != nv or steps.dtype != torch.int32 or \
             any(q.dtype != torch.float32 for q in (data, mask, step_len, tp_pred, flat_params, eps)):
         raise _lib.ImmtsfError("latent_ode: the tensors are not the fp32 tensors of these dimensions")
@@ -3478,12 +3468,9 @@ def neural_flow_supported(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_lay
     """the limits of the fused NeuralFlow kernels (immtsf_neural_flow_supported: rec_dims, latents <= 64, hidden_dim <= 128, hidden_layers,
     flow_layers <= 4, C <= 64, L, Lp <= 2^20, W_hh, the flow's nets and a tile's state within 160 KB of LDS), from the dims alone; call:
     also what a compute call needs (B >= 1 and the saved state's index range, immtsf_neural_flow_workspace_bytes > 0)"""
-    import ctypes
-    d = _neural_flow_dims(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers)
     lib = _lib.load()
-    if not lib.immtsf_neural_flow_supported(ctypes.byref(d)):
-        return False
-    return bool(lib.immtsf_neural_flow_workspace_bytes(ctypes.byref(d)) > 0) if call else True
+    return _dims_supported(lib.immtsf_neural_flow_supported, lib.immtsf_neural_flow_workspace_bytes,
+                           _neural_flow_dims(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers), call)
 
 
 class NeuralFlowFn(torch.autograd.Function):
@@ -3493,33 +3480,31 @@ class NeuralFlowFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, data, mask, tp, tpp, flat, eps, widths):
-        import ctypes
         lib = _lib.load()
         data, mask, tp, tpp, flat, eps = (_c(t) for t in (data, mask, tp, tpp, flat, eps))
         _need_gpu(data, mask, tp, tpp, flat, eps)
-        B, L, C = data.shape
+        B, L, Cc = data.shape
         Lp = tpp.shape[1]
         R, Z = widths[0], widths[1]
-        d = _neural_flow_dims(B, L, Lp, C, *widths)
-        out = torch.empty(B, Lp, C, dtype=torch.float32, device=data.device)
+        d = _neural_flow_dims(B, L, Lp, Cc, *widths)
+        out = torch.empty(B, Lp, Cc, dtype=torch.float32, device=data.device)
         xg = torch.empty(B, L, 4 * R, dtype=torch.float32, device=data.device)
         states = torch.empty(B, L + 1, 2 * R, dtype=torch.float32, device=data.device)
         zs = torch.empty(B, 3, Z, dtype=torch.float32, device=data.device)
-        check(lib.immtsf_neural_flow_forward(ctypes.byref(d), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(out), ptr(xg),
+        check(lib.immtsf_neural_flow_forward(C.byref(d), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(out), ptr(xg),
                                              ptr(states), ptr(zs), stream_ptr()), "neural_flow_forward")
-        ctx.dims = (B, L, Lp, C) + tuple(widths)
+        ctx.dims = (B, L, Lp, Cc) + tuple(widths)
         ctx.save_for_backward(data, mask, tp, tpp, flat, eps, xg, states, zs)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes
         lib = _lib.load()
         data, mask, tp, tpp, flat, eps, xg, states, zs = ctx.saved_tensors
         d = _neural_flow_dims(*ctx.dims)
         grads = torch.empty_like(flat)      # every entry is written: no zero fill
-        ws = _bytes(lib.immtsf_neural_flow_workspace_bytes(ctypes.byref(d)), data.device)
-        check(lib.immtsf_neural_flow_backward(ctypes.byref(d), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(xg),
+        ws = _bytes(lib.immtsf_neural_flow_workspace_bytes(C.byref(d)), data.device)
+        check(lib.immtsf_neural_flow_backward(C.byref(d), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(xg),
                                               ptr(states), ptr(zs), ptr(dout.contiguous()), ptr(grads), ptr(ws), ws.numel(), stream_ptr()),
               "neural_flow_backward")
         return None, None, None, None, grads, None, None
@@ -3529,17 +3514,16 @@ def neural_flow(data, mask, tp, tp_pred, flat_params, eps, widths):
     """data, mask (B, L, C); tp (B, L), tp_pred (B, Lp): every window's own times; flat_params: every parameter in state_dict order,
     flattened; eps (B, latents); widths = (rec_dims, latents, hidden_dim, hidden_layers, flow_layers) -> the forecast (B, Lp, C).
     Gradients reach flat_params only."""
-    import ctypes
-    B, L, C = data.shape
+    B, L, Cc = data.shape
     widths = tuple(int(w) for w in widths)
     if tp_pred.dim() != 2:
         raise _lib.ImmtsfError("neural_flow: tp_pred is (B, Lp)")
     Lp = tp_pred.shape[1]
-    if not neural_flow_supported(B, L, Lp, C, *widths, call=True):
-        raise _lib.ImmtsfError(f"neural_flow: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, C {C}, widths {widths})")
-    d = _neural_flow_dims(B, L, Lp, C, *widths)
-    nv = int(_lib.load().immtsf_neural_flow_param_count(ctypes.byref(d)))
-    if tuple(mask.shape) != (B, L, C) or tuple(tp.shape) != (B, L) or tuple(tp_pred.shape) != (B, Lp) or tuple(eps.shape) != (B, widths[1]) or \
+    if not neural_flow_supported(B, L, Lp, Cc, *widths, call=True):
+        raise _lib.ImmtsfError(f"neural_flow: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, C {Cc}, widths {widths})")
+    d = _neural_flow_dims(B, L, Lp, Cc, *widths)
+    nv = int(_lib.load().immtsf_neural_flow_param_count(C.byref(d)))
+    if tuple(mask.shape) != (B, L, Cc) or tuple(tp.shape) != (B, L) or tuple(tp_pred.shape) != (B, Lp) or tuple(eps.shape) != (B, widths[1]) or \
             flat_params.numel() != nv or any(q.dtype != torch.float32 for q in (data, mask, tp, tp_pred, flat_params, eps)):
         raise _lib.ImmtsfError("neural_flow: the tensors are not the fp32 tensors of these dimensions")
     return NeuralFlowFn.apply(data, mask, tp, tp_pred, flat_params, eps, widths)

@@ -87,6 +87,32 @@ def test_two_writers_of_one_undeclared_sink_raise_on_the_host():
     ops._claim_sinks([q], [q._immtsf_grad_sink], "b")
 
 
+def test_ops_keeps_every_recorded_name():
+    """tests/golden/ops_names.txt records the names immtsf.ops offers its callers (the drop-in modules, train.py, the tools and the tests
+    reach private ones too): the list of the commit before the repeated idioms were folded, less the seven that the folds merged
+    (_shadow_put / _shadow_get into _reg_put / _reg_take; _dlinear_table, _dl_tables, _tm_tables into _pointer_table; _tm_layouts,
+    _cru_layouts into _grad_layout) and the `annotations` artefact of the __future__ import.  A later split of the module into a package
+    has to keep every one importable from here, and every Function, class and front end THE object of the module that defines it
+    (immtsf.ops or a submodule of it; immtsf._lib for the structs, check, ptr, stream_ptr), not a copy that can go stale."""
+    import importlib
+    import types
+    from immtsf import ops
+    with open(os.path.join(ROOT, "tests", "golden", "ops_names.txt")) as f:
+        names = f.read().split()
+    assert len(names) == len(set(names)) == 177
+    missing = [n for n in names if not hasattr(ops, n)]
+    assert not missing, missing
+    owned = [n for n in names if isinstance(getattr(ops, n), (type, types.FunctionType))]
+    assert len(owned) >= 150, len(owned)
+    for n in owned:
+        obj = getattr(ops, n)
+        home = obj.__module__
+        assert home == "immtsf._lib" or home == "immtsf.ops" or home.startswith("immtsf.ops."), (n, home)
+        assert getattr(importlib.import_module(home), n) is obj, n
+    merged = ("_shadow_put", "_shadow_get", "_dlinear_table", "_dl_tables", "_tm_tables", "_tm_layouts", "_cru_layouts")
+    assert not [n for n in merged if hasattr(ops, n)]              # one definition each: no second copy grows back unnoticed
+
+
 def test_t2v_form_selection_is_a_host_decision():
     """immtsf_ttf_t2v_xattn_folded (no kernel, no GPU): which formulation of TTF_T2V_XAttn a cfg gets -- the folded form from 8192 padded
     note rows on inside its limits (N <= 64), its mix-first variant for longer windows in bf16 mode with one head (or form 3), the chain
