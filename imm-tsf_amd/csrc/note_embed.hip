@@ -10,6 +10,8 @@
 //     key range taken from cu).  bf16 mode: both products on bf16 MFMA with fp32 accumulation, fp32 online softmax.
 //   * ln_f + mean-pool: LayerNorm of each row of a note, summed in position order, / max(L, 1); a note of no tokens gives an exact 0 row
 // Forward only, no dropout, no atomics, one writer per output element, every sum in a fixed order: two runs give the same bits.
+// The two attention kernels are templates on a CAUSAL switch: the non-causal instances (every query of a note sees all its keys) serve
+// the frozen BERT of bert_embed.hip through immtsf_bert_embed_attention, defined at the end of this file.
 //
 // Launch of the attention kernels: grid (note, head, query tile of 64 REVERSED), one wave per workgroup.  Workgroups are handed out in
 // x, y, z order, so the last query tiles of the long notes -- the ones with the most keys -- start first and the short tiles fill in
@@ -63,7 +65,10 @@ __global__ void __launch_bounds__(256) note_tokens_kernel(const int32_t* __restr
 }
 
 // ---- ragged causal attention, fp32 on the VALU ---------------------------------------------------------------------------------------
-// a thread owns one query (q, the output row and the softmax state in registers); K / V tiles of KT keys go through LDS as broadcasts
+// a thread owns one query (q, the output row and the softmax state in registers); K / V tiles of KT keys go through LDS as broadcasts.
+// CAUSAL (GPT-2): query t sees keys 0 .. t.  Not CAUSAL (BERT): every query of a note sees keys 0 .. L - 1, so the bound of the last key
+// tile is L itself and not the query's position.
+template <bool CAUSAL>
 __global__ void __launch_bounds__(64) note_attn_valu_kernel(const float* __restrict__ qkv, int ld, const int32_t* __restrict__ cu, int rows,
                                                             int d, float scale, float* __restrict__ o32, bf16_t* __restrict__ o16) {
     __shared__ float4 Ks[KT * HD / 4];
@@ -89,7 +94,7 @@ __global__ void __launch_bounds__(64) note_attn_valu_kernel(const float* __restr
 #pragma unroll
     for (int e = 0; e < HD; ++e) acc[e] = 0.f;
     float m = -INFINITY, l = 0.f;
-    const int kend = min(t0 + QT, L);                       // keys 0 .. kend-1 are visible to some query of the wave
+    const int kend = CAUSAL ? min(t0 + QT, L) : L;          // keys 0 .. kend-1 are visible to some query of the wave
     for (int j0 = 0; j0 < kend; j0 += KT) {
         __syncthreads();
 #pragma unroll
@@ -116,10 +121,11 @@ __global__ void __launch_bounds__(64) note_attn_valu_kernel(const float* __restr
                     const float4 kk = Ks[(c4 + c) * (HD / 4) + e];
                     a += qr[4 * e] * kk.x + qr[4 * e + 1] * kk.y + qr[4 * e + 2] * kk.z + qr[4 * e + 3] * kk.w;
                 }
-                sc[c] = (j0 + c4 + c <= t) ? a : -INFINITY;
+                sc[c] = (j0 + c4 + c < (CAUSAL ? t + 1 : L)) ? a : -INFINITY;
                 cmax = fmaxf(cmax, sc[c]);
             }
-            // (the running maximum is finite from the first chunk on: key 0 is visible to every query)
+            // (the running maximum is finite from the first chunk on: key 0 is visible to every query; a chunk is entered only when its
+            // first key lies below kend, so without the causal bound every chunk has a visible key too)
             if (cmax > m) {
                 const float corr = __expf(m - cmax);
                 m = cmax;
@@ -168,6 +174,9 @@ __global__ void __launch_bounds__(64) note_attn_valu_kernel(const float* __restr
 // The output row of a query lies across the 4 lanes with its fr: 4 consecutive head columns per 16-column tile each (16-byte stores).
 __device__ __forceinline__ f32x4 ne_mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
+// Not CAUSAL: the key loop runs to L for every query tile, the last 32-key tile is masked by L, and a 16-query tile that starts past the
+// note's end is skipped (its queries are clamped copies and nothing of it is written).
+template <bool CAUSAL>
 __global__ void __launch_bounds__(64) note_attn_mfma_kernel(const float* __restrict__ qkv, int ld, const int32_t* __restrict__ cu, int rows,
                                                             int d, float scale, float* __restrict__ o32, bf16_t* __restrict__ o16) {
     __shared__ __attribute__((aligned(16))) bf16_t Ks[KT * KS_LD];
@@ -199,7 +208,7 @@ __global__ void __launch_bounds__(64) note_attn_mfma_kernel(const float* __restr
 #pragma unroll
         for (int et = 0; et < 4; ++et) O[mt][et] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    const int kend = min(t0 + QT, L);
+    const int kend = CAUSAL ? min(t0 + QT, L) : L;
     for (int j0 = 0; j0 < kend; j0 += KT) {
         __syncthreads();
 #pragma unroll
@@ -232,8 +241,9 @@ __global__ void __launch_bounds__(64) note_attn_mfma_kernel(const float* __restr
         for (int mt = 0; mt < 4; ++mt) {
             // a 16-query tile that ends below the key tile sees none of it; one that is not skipped has j0 <= its first query (j0 is a
             // multiple of 32, the tile base of 16), so each of its queries sees key j0 and the running maximum below is finite
-            if (j0 > t0 + 16 * mt + 15) continue;
-            const int qi = t0 + 16 * mt + fr;
+            // (without the causal bound: j0 < L, so key j0 is visible to every query)
+            if (CAUSAL ? j0 > t0 + 16 * mt + 15 : t0 + 16 * mt >= L) continue;
+            const int qi = CAUSAL ? t0 + 16 * mt + fr : L - 1;     // the last key this lane's query sees
             float s[2][4];
             float cmax = -INFINITY;
 #pragma unroll
@@ -320,6 +330,26 @@ __global__ void __launch_bounds__(256) note_pool_kernel(const float* __restrict_
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
+template <bool CAUSAL>
+int launch_attention(const float* qkv, int32_t ld, const int32_t* cu, int32_t N, int32_t rows, int32_t H, int32_t max_len, float scale,
+                            int32_t precision, float* out32, void* out16, immtsf_stream_t stream) {
+    if (!qkv || !cu || (!out32 && !out16) || N <= 0 || rows <= 0 || H <= 0 || max_len <= 0) return IMMTSF_EINVAL;
+    if (precision < 0 || precision > 1) return IMMTSF_EINVAL;
+    if (H > 65535 || max_len > MAXL || ld < 3 * H * HD || (ld & 3) || !al16(qkv) || (out32 && !al16(out32)) ||
+        (out16 && (reinterpret_cast<uintptr_t>(out16) & 7)))
+        return IMMTSF_EUNSUPPORTED;
+    const dim3 grid((unsigned)N, (unsigned)H, (unsigned)((max_len + QT - 1) / QT));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (precision == 1)
+        hipLaunchKernelGGL(note_attn_mfma_kernel<CAUSAL>, grid, dim3(64), 0, s, qkv, ld, cu, rows, H * HD, scale, out32,
+                           static_cast<bf16_t*>(out16));
+    else
+        hipLaunchKernelGGL(note_attn_valu_kernel<CAUSAL>, grid, dim3(64), 0, s, qkv, ld, cu, rows, H * HD, scale, out32,
+                           static_cast<bf16_t*>(out16));
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -350,19 +380,13 @@ int immtsf_note_embed_tokens(const int32_t* ids, const int32_t* cu, int32_t N, i
 
 int immtsf_note_embed_attention(const float* qkv, int32_t ld, const int32_t* cu, int32_t N, int32_t rows, int32_t H, int32_t max_len,
                                 float scale, int32_t precision, float* out32, void* out16, immtsf_stream_t stream) {
-    if (!qkv || !cu || (!out32 && !out16) || N <= 0 || rows <= 0 || H <= 0 || max_len <= 0) return IMMTSF_EINVAL;
-    if (precision < 0 || precision > 1) return IMMTSF_EINVAL;
-    if (H > 65535 || max_len > MAXL || ld < 3 * H * HD || (ld & 3) || !al16(qkv) || (out32 && !al16(out32)) ||
-        (out16 && (reinterpret_cast<uintptr_t>(out16) & 7)))
-        return IMMTSF_EUNSUPPORTED;
-    const dim3 grid((unsigned)N, (unsigned)H, (unsigned)((max_len + QT - 1) / QT));
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (precision == 1)
-        hipLaunchKernelGGL(note_attn_mfma_kernel, grid, dim3(64), 0, s, qkv, ld, cu, rows, H * HD, scale, out32, static_cast<bf16_t*>(out16));
-    else
-        hipLaunchKernelGGL(note_attn_valu_kernel, grid, dim3(64), 0, s, qkv, ld, cu, rows, H * HD, scale, out32, static_cast<bf16_t*>(out16));
-    IMMTSF_LAUNCH_CHECK();
-    return IMMTSF_OK;
+    return launch_attention<true>(qkv, ld, cu, N, rows, H, max_len, scale, precision, out32, out16, stream);
+}
+
+// the same launch without the causal bound (csrc/bert_embed.hip has the rest of the BERT body)
+int immtsf_bert_embed_attention(const float* qkv, int32_t ld, const int32_t* cu, int32_t N, int32_t rows, int32_t H, int32_t max_len,
+                                float scale, int32_t precision, float* out32, void* out16, immtsf_stream_t stream) {
+    return launch_attention<false>(qkv, ld, cu, N, rows, H, max_len, scale, precision, out32, out16, stream);
 }
 
 int immtsf_note_embed_pool(const float* x, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const float* gamma, const float* beta,

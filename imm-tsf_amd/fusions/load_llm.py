@@ -4,11 +4,13 @@ get_d_model / get_context_window_size mirror the alias table of the reference's 
 reference asks the HF hub, which needs network access; the fusion constructors only need the integers).
 
 load_llm / embed_notes (reference :79-201) keep the reference's signatures and results.  embed_notes pads every note to max_length
-tokens, runs the padded batch through the frozen LLM and averages each note's real-token rows.  For a GPT2Model on the GPU behind a
-right-padding tokenizer the same function is computed over the real tokens alone (immtsf.ops.gpt2_embed_notes: a causal model never
-lets a pad token into a real token's hidden state, and the average never reads a pad row), so only the real ids are uploaded and the
-padded-out notes of a window get their zero rows without being run.  Every other case -- BERT, Llama, a left-padding tokenizer, the
-CPU, immtsf.config.note_embed_fused off, a model left in training mode with dropout -- runs the padded formulation on torch ops.
+tokens, runs the padded batch through the frozen LLM and averages each note's real-token rows.  For a GPT2Model or a BertModel on the
+GPU behind a right-padding tokenizer the same function is computed over the real tokens alone (immtsf.ops.gpt2_embed_notes: a causal
+model never lets a pad token into a real token's hidden state; immtsf.ops.bert_embed_notes: a padded key has an exact zero weight in a
+real query's softmax; the average never reads a pad row), so only the real ids are uploaded.  The padded-out notes of a window are
+the empty string: where that has no tokens (GPT-2) their rows are zeros without being run, where it has some (BERT's [CLS] [SEP]) the
+one note is run once in the same call and copied to every such row.  Every other case -- Llama, a left-padding tokenizer, the CPU,
+immtsf.config.note_embed_fused off, a model left in training mode with dropout -- runs the padded formulation on torch ops.
 path_calls counts which way each call went.
 """
 import torch
@@ -92,16 +94,34 @@ def _token_counts(attn):
     return counts, bool(torch.equal(prefix, attn.bool()))
 
 
+def _family(llm_model):
+    """what the fused path needs to know of a model family: (the packed-token op, its limits, the fewest notes of an fp32 call that take
+    it, the config's dropout rates), or None for a model without one"""
+    from transformers import BertModel, GPT2Model
+
+    from immtsf import ops
+    if isinstance(llm_model, GPT2Model):
+        return (ops.gpt2_embed_notes, ops.gpt2_embed_notes_supported, config.note_embed_fp32_min_notes,
+                ("embd_pdrop", "attn_pdrop", "resid_pdrop"))
+    if type(llm_model) is BertModel:
+        return (ops.bert_embed_notes, ops.bert_embed_notes_supported, config.bert_embed_fp32_min_notes,
+                ("hidden_dropout_prob", "attention_probs_dropout_prob"))
+    return None
+
+
 def _fused_ok(llm_model, device, max_length, n_notes):
     if not config.note_embed_fused or device.type != "cuda":
         return False
-    if config.precision_code(None) == 0 and n_notes < config.note_embed_fp32_min_notes:
-        return False             # (measured slower than the padded call there: DESIGN 4o)
-    from immtsf import ops
-    if not ops.gpt2_embed_notes_supported(llm_model, max_length):
+    family = _family(llm_model)
+    if family is None:
+        return False
+    _, supported, fp32_min_notes, drops = family
+    if config.precision_code(None) == 0 and n_notes < fp32_min_notes:
+        return False             # (measured slower than the padded call there: DESIGN 4o, 4p)
+    if not supported(llm_model, max_length):
         return False
     cfg = llm_model.config       # (a body left in training mode draws dropout masks in the padded formulation: that is not this kernel)
-    return not (llm_model.training and max(cfg.embd_pdrop, cfg.attn_pdrop, cfg.resid_pdrop) > 0.0)
+    return not (llm_model.training and max(float(getattr(cfg, k)) for k in drops) > 0.0)
 
 
 def _pool_padded(llm_model, ids, attn):
@@ -116,14 +136,13 @@ def _pool_rows(llm_model, ids, attn, rows, device):
     ids, attn = ids[rows], attn[rows]
     counts, is_prefix = _token_counts(attn)
     if is_prefix and rows.numel() and _fused_ok(llm_model, device, int(ids.shape[1]), int(rows.numel())):
-        from immtsf import ops
         real = ids[attn.bool()]                       # row-major: the notes' real tokens back to back
-        if real.numel() and (int(real.min()) < 0 or int(real.max()) >= llm_model.wte.weight.shape[0]):
+        if real.numel() and (int(real.min()) < 0 or int(real.max()) >= llm_model.get_input_embeddings().weight.shape[0]):
             raise IndexError("embed_notes: a token id lies outside the model's embedding table")
         cu = torch.zeros(rows.numel() + 1, dtype=torch.int32)
         cu[1:] = torch.cumsum(counts, 0)
         path_calls["fused"] += 1
-        return ops.gpt2_embed_notes(llm_model, real.to(torch.int32).to(device), cu.to(device), max_len=max(int(counts.max()), 1))
+        return _family(llm_model)[0](llm_model, real.to(torch.int32).to(device), cu.to(device), max_len=max(int(counts.max()), 1))
     path_calls["stock"] += 1
     return _pool_padded(llm_model, ids.to(device), attn.to(device))
 
@@ -146,11 +165,17 @@ def embed_notes(notes_text: list[list[str]], tokenizer, llm_model, max_length: i
     enc = _tokenize([n for w in notes_text for n in list(w) + [""] * (N_max - len(w))], tokenizer, max_length)
     ids, attn = enc.input_ids, enc.attention_mask
     every = torch.arange(B * N_max)
-    real = every[note_mask.reshape(-1)]
-    counts, is_prefix = _token_counts(attn[real])
-    if is_prefix and real.numel() and _fused_ok(llm_model, device, int(ids.shape[1]), int(real.numel())):
+    real, fill = every[note_mask.reshape(-1)], every[~note_mask.reshape(-1)]
+    # the padded-out notes are all the empty string: run one of them when it has tokens ([CLS] [SEP]); none when it has not (zero rows)
+    one_fill = fill[:1] if fill.numel() and int(attn[fill[0]].sum()) > 0 else fill[:0]
+    run = torch.cat([real, one_fill])
+    counts, is_prefix = _token_counts(attn[run])
+    if is_prefix and run.numel() and _fused_ok(llm_model, device, int(ids.shape[1]), int(run.numel())):
         out = torch.zeros(B * N_max, _hidden_size(llm_model), device=device)
-        out[real.to(device)] = _pool_rows(llm_model, ids, attn, real, device)
+        emb = _pool_rows(llm_model, ids, attn, run, device)
+        out[real.to(device)] = emb[:real.numel()]
+        if one_fill.numel():
+            out[fill.to(device)] = emb[-1]
     else:                  # every row, the padded-out notes included, as the reference runs them
         out = _pool_rows(llm_model, ids, attn, every, device)
     return out.view(B, N_max, -1), note_mask.to(device)

@@ -217,6 +217,16 @@ _PROTOS = {
     "immtsf_note_embed_attention": (C.c_int, [c_f32p, C.c_int32, c_i32p] + [C.c_int32] * 4 + [C.c_float, C.c_int32, c_f32p, C.c_void_p,
                                               c_stream]),
     "immtsf_note_embed_pool": (C.c_int, [c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p, C.c_float, c_f32p, c_stream]),
+    "immtsf_bert_embed_supported": (C.c_int, [C.c_int32] * 4),
+    "immtsf_bert_embed_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "immtsf_bert_embed_rows": (C.c_int, [c_i32p, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, c_f32p,
+                                         c_f32p, C.c_float, c_f32p, C.c_void_p, c_stream]),
+    "immtsf_bert_embed_attention": (C.c_int, [c_f32p, C.c_int32, c_i32p] + [C.c_int32] * 4 + [C.c_float, C.c_int32, c_f32p, C.c_void_p,
+                                              c_stream]),
+    "immtsf_bert_embed_add_layernorm": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, c_f32p, C.c_float, c_f32p, C.c_void_p,
+                                                  c_stream]),
+    "immtsf_bert_embed_gelu": (C.c_int, [c_f32p, C.c_uint64, c_f32p, C.c_void_p, c_stream]),
+    "immtsf_bert_embed_pool": (C.c_int, [c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_stream]),
     "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,

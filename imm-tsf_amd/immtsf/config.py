@@ -150,6 +150,11 @@ note_embed_fused = os.environ.get("IMMTSF_NOTE_EMBED_FUSED", "1") != "0"
 # ... in fp32 mode only for calls of at least this many notes: a single note per call measured 0.88x of the padded call there (the
 # small-row fp32 GEMMs), several notes 2.4x.  bf16 mode takes the fused path at any count (2.6x / 7.0x)
 note_embed_fp32_min_notes = int(os.environ.get("IMMTSF_NOTE_EMBED_FP32_MIN_NOTES", "2"))
+# The same switch covers a frozen BertModel (immtsf.ops.bert_embed_notes: csrc/bert_embed.hip, the non-causal ragged attention of
+# csrc/note_embed.hip, the GEMM family).  Its fp32 threshold is its own knob, measured on its own: a single note per call
+# 0.95x of the padded call (within the passes' spread of it: no win), 32 notes 1.8x.  bf16 mode takes the fused path at any count
+# (1.9x / 4.7x)
+bert_embed_fp32_min_notes = int(os.environ.get("IMMTSF_BERT_EMBED_FP32_MIN_NOTES", "2"))
 # LatentODE's forecasting() as one HIP launch forward and two backward (csrc/latent_ode.hip) wherever the encoder is the ODE-RNN with
 # rec_layers = gen_layers = 1, one trajectory sample, and immtsf_latent_ode_supported allows; IMMTSF_LATENTODE_FUSED=0: the composed path
 # (the reference's loop over the observed points on torch ops, the step plan copied to the host once) -- the cross-check.  fp32 in

@@ -3390,6 +3390,128 @@ def gpt2_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         return pooled
 
 
+# ------------------------------------------------------------------------------------------------ raw-text mode: notes through a frozen BERT
+def bert_embed_notes_supported(llm_model, max_len):
+    """the limits of bert_embed_notes: a transformers BertModel (the class itself; its pooler is ignored) with head_dim 64, hidden_act
+    "gelu" (the erf form), absolute position embeddings, neither a decoder nor cross attention, at least one layer left after
+    llm_layers_fusion has cut the stack, fp32 parameters, hidden_size and intermediate_size multiples of 8, and
+    1 <= max_len <= max_position_embeddings, <= 1024"""
+    from transformers import BertModel
+    if type(llm_model) is not BertModel or max_len < 1:
+        return False
+    cfg = llm_model.config
+    d, H = int(cfg.hidden_size), int(cfg.num_attention_heads)
+    if (cfg.hidden_act != "gelu" or getattr(cfg, "position_embedding_type", None) not in (None, "absolute") or
+            getattr(cfg, "is_decoder", False) or getattr(cfg, "add_cross_attention", False) or len(llm_model.encoder.layer) < 1):
+        return False
+    if d % 8 or int(cfg.intermediate_size) % 8 or any(p.dtype != torch.float32 for p in llm_model.parameters()):
+        return False
+    return bool(_lib.load().immtsf_bert_embed_supported(d, H, int(max_len), int(cfg.max_position_embeddings)))
+
+
+def _bert_qkv(model, att, bf):
+    """(W (3d, d), bias (3d), bf16 image of W or None) of one layer's query | key | value Linears, concatenated once and cached on the model,
+    keyed by the six parameters' storage address and version: load_state_dict(), .to() or any in-place write makes a new one"""
+    cache = model.__dict__.setdefault("_immtsf_bert_qkv", {})
+    params = (att.query.weight, att.key.weight, att.value.weight, att.query.bias, att.key.bias, att.value.bias)
+    key = tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in params)
+    hit = cache.get(id(att))
+    if hit is None or hit[0] != key:
+        hit = cache[id(att)] = [key, torch.cat([p.detach() for p in params[:3]], 0).contiguous(),
+                                torch.cat([p.detach() for p in params[3:]], 0).contiguous(), None]
+    if bf and hit[3] is None:
+        hit[3] = torch.empty(hit[1].shape, dtype=torch.bfloat16, device=hit[1].device)
+        check(_lib.load().immtsf_f32_to_bf16(ptr(hit[1]), ptr(hit[3]), hit[1].numel(), stream_ptr()), "f32_to_bf16")
+    return hit[1], hit[2], hit[3]
+
+
+def bert_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
+    """pooled (N, d) fp32: the mean over each note's tokens of the frozen BertModel's last hidden state -- reference fusions/load_llm.py
+    embed_notes without the padding (csrc/bert_embed.hip, the non-causal ragged attention of csrc/note_embed.hip and the GEMM family over
+    the packed rows; 8 launches a layer + 2).  ids (sum L) int32: the notes' real tokens back to back; cu (N + 1) int32: prefix sums of the
+    token counts; both on the model's device.  Token type 0 everywhere, as the reference calls the model.  A note of no tokens gives an
+    exact zero row.  max_len: an upper bound of the token counts (read from cu when not given: one device -> host copy).  The model's
+    parameters are read in place, but for the cached query | key | value concatenation and, in bf16 mode, the cached bf16 weight images;
+    runs under no_grad and saves nothing.  Outside bert_embed_notes_supported this raises: callers check."""
+    with torch.no_grad():
+        _need_gpu(ids, cu)
+        if ids.dtype != torch.int32 or cu.dtype != torch.int32 or ids.dim() != 1 or cu.dim() != 1 or cu.numel() < 1:
+            raise _lib.ImmtsfError("bert_embed_notes: ids (sum L) and cu (N + 1) are int32 vectors")
+        ids, cu = _c(ids), _c(cu)
+        N, T = cu.numel() - 1, ids.numel()
+        cfg = llm_model.config
+        d = int(getattr(cfg, "hidden_size", 0))
+        dev = ids.device
+        if max_len is None:
+            max_len = int((cu[1:] - cu[:-1]).max()) if T and N else 1
+        max_len = max(int(max_len), 1)
+        if not bert_embed_notes_supported(llm_model, max_len):
+            raise _lib.ImmtsfError("bert_embed_notes: this model / note length is outside bert_embed_notes_supported")
+        if N == 0:
+            return torch.zeros(0, d, dtype=torch.float32, device=dev)
+        inner = int(cfg.intermediate_size)
+        if T >= 2 ** 31 // (4 * max(3 * d, inner)):
+            raise _lib.ImmtsfError("bert_embed_notes: too many tokens for one call (split the batch)")
+        lib = _lib.load()
+        st = stream_ptr()
+        precision = config.precision_code(precision)
+        bf = precision == 1
+        H = int(cfg.num_attention_heads)
+        eps = float(cfg.layer_norm_eps)
+        scale = 1.0 / float(d // H) ** 0.5
+        pooled = torch.empty(N, d, dtype=torch.float32, device=dev)
+        if T == 0:
+            return pooled.zero_()
+        # one workspace for the whole pass, carved as include/immtsf.h lists it
+        ws = _bytes(lib.immtsf_bert_embed_workspace_bytes(T, d, inner, precision), dev)
+        off = [0]
+
+        def carve(cols, dt=torch.float32):
+            nbytes = T * cols * (2 if dt == torch.bfloat16 else 4)
+            t = ws[off[0]:off[0] + nbytes].view(dt).view(T, cols)
+            off[0] += (nbytes + 255) & ~255
+            return t
+
+        op = torch.bfloat16 if bf else torch.float32
+        x, x1 = carve(d), carve(d)
+        h = carve(d, torch.bfloat16) if bf else None
+        qkv, ao, pr, pre, act = carve(3 * d), carve(d, op), carve(d), carve(inner), carve(inner, op)
+        assert off[0] <= ws.numel()
+
+        def mm(a32, a16, W, W16, bias, out):
+            """out (T, N_out) = a (T, K) W^T + bias: W (N_out, K) is the nn.Linear weight as stored (layout 0)"""
+            N_out, K = W.shape
+            check(lib.immtsf_gpt2_gemm(0, precision, None if bf else ptr(a32), ptr(a16) if bf else None, K, ptr(W), ptr(W16) if bf else None, K,
+                                       ptr(out), N_out, ptr(bias), T, N_out, K, st), "gpt2_gemm")
+
+        def lin(a32, a16, dense, out):
+            mm(a32, a16, dense.weight, _gpt2_w16(llm_model, dense.weight) if bf else None, dense.bias, out)
+
+        def add_ln(y, base, norm, dst):
+            check(lib.immtsf_bert_embed_add_layernorm(ptr(y), ptr(base), T, d, ptr(norm.weight), ptr(norm.bias), eps, ptr(dst), ptr(h), st),
+                  "bert_embed_add_layernorm")
+
+        emb = llm_model.embeddings
+        word, pos = emb.word_embeddings.weight, emb.position_embeddings.weight
+        check(lib.immtsf_bert_embed_rows(ptr(ids), ptr(cu), N, T, ptr(word), int(word.shape[0]), ptr(pos), int(pos.shape[0]),
+                                         ptr(emb.token_type_embeddings.weight), d, ptr(emb.LayerNorm.weight), ptr(emb.LayerNorm.bias), eps,
+                                         ptr(x), ptr(h), st), "bert_embed_rows")
+        for layer in llm_model.encoder.layer:
+            att = layer.attention
+            Wqkv, bqkv, Wqkv16 = _bert_qkv(llm_model, att.self, bf)
+            mm(x, h, Wqkv, Wqkv16, bqkv, qkv)
+            check(lib.immtsf_bert_embed_attention(ptr(qkv), 3 * d, ptr(cu), N, T, H, max_len, scale, precision, None if bf else ptr(ao),
+                                                  ptr(ao) if bf else None, st), "bert_embed_attention")
+            lin(ao, ao, att.output.dense, pr)
+            add_ln(pr, x, att.output.LayerNorm, x1)
+            lin(x1, h, layer.intermediate.dense, pre)
+            check(lib.immtsf_bert_embed_gelu(ptr(pre), pre.numel(), None if bf else ptr(act), ptr(act) if bf else None, st), "bert_embed_gelu")
+            lin(act, act, layer.output.dense, pr)
+            add_ln(pr, x1, layer.output.LayerNorm, x)
+        check(lib.immtsf_bert_embed_pool(ptr(x), ptr(cu), N, T, d, ptr(pooled), st), "bert_embed_pool")
+        return pooled
+
+
 # ------------------------------------------------------------------------------------------------ LatentODE backbone
 def _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents):
     return _lib.LatentODEDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(units), int(gru_units), int(latents))

@@ -800,6 +800,39 @@ int immtsf_note_embed_attention(const float* qkv, int32_t ld, const int32_t* cu,
 int immtsf_note_embed_pool(const float* x, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const float* gamma, const float* beta,
                            float eps, float* pooled, immtsf_stream_t stream);
 
+/* ---- Raw-text mode, BERT (added within ABI 7: new functions only; csrc/bert_embed.hip, the attention in csrc/note_embed.hip): what
+ * immtsf.ops.bert_embed_notes composes with immtsf_gpt2_gemm layout 0 (an nn.Linear weight as stored) into reference fusions/load_llm.py
+ * embed_notes for a frozen BertModel -- over the RAGGED tokens, ids / cu as above.  BERT is not causal, but a padded key has an exact zero
+ * weight in every real query's softmax and the mean-pool reads real tokens only, so each note's real tokens alone give the padded
+ * formulation's result.  Post-LN body, 8 launches a layer: QKV (one product over the concatenated weights), attention, output
+ * projection, add + LayerNorm, intermediate, GELU, output, add + LayerNorm.  Forward only, no dropout, no atomics, fixed summation
+ * order (the same inputs give the same bits).  head_dim is 64, d = 64 H.
+ * ..._supported: d == 64 H, H <= 65535, 1 <= max_len <= max_positions, max_len <= 1024 (max_len: an upper bound of every note's length).
+ * ..._workspace_bytes: the activations of one pass, each buffer rounded up to 256 bytes, in this order: x, x1 (rows, d) fp32; h (rows, d)
+ *   bf16, in precision 1 only (the image of x / x1 the next product reads); qkv (rows, 3 d) fp32; ao (rows, d) fp32 | bf16; proj (rows, d)
+ *   fp32; pre (rows, inner) fp32; act (rows, inner) fp32 | bf16 -- bf16 in precision 1.  Host arithmetic only.
+ * ..._rows: out32[r, :] = LayerNorm(word[ids[r], :] + pos[r - cu[n], :] + type0[:]; gamma, beta, eps) for row r of note n, and its bf16
+ *   image in out16 when given.  type0: row 0 of the token-type table (the reference passes no token_type_ids).  An id outside [0, vocab)
+ *   or a position outside [0, max_positions) is not read: the row is written as zeros (callers check the ids first).
+ * ..._attention: immtsf_note_embed_attention without the causal bound: query p of note n sees keys 0 .. L_n - 1 of note n and nothing
+ *   else (the last 32-key tile is masked by L_n); same layouts, precisions, grid and limits.
+ * ..._add_layernorm: out32[r, :] = LayerNorm(y[r, :] + x[r, :]) over `rows` rows, and the bf16 image in out16 when given; out32 may be x.
+ * ..._gelu: x Phi(x), the erf form (hidden_act "gelu"), of n elements (n % 4 == 0) into out32 and / or out16.
+ * ..._pool: pooled[n, :] = sum over note n's rows of x, in position order, divided by max(L, 1) -- no final LayerNorm; a note of no
+ *   tokens gives an exact zero row.  A note whose range does not lie in [0, rows) or is longer than 1024 counts as empty.
+ * Arguments outside these limits give IMMTSF_EINVAL / IMMTSF_EUNSUPPORTED before anything is launched; nothing allocates or synchronises. */
+int immtsf_bert_embed_supported(int32_t d, int32_t H, int32_t max_len, int32_t max_positions);
+size_t immtsf_bert_embed_workspace_bytes(int64_t rows, int32_t d, int32_t inner, int32_t precision);
+int immtsf_bert_embed_rows(const int32_t* ids, const int32_t* cu, int32_t N, int32_t rows, const float* word, int32_t vocab, const float* pos,
+                           int32_t max_positions, const float* type0, int32_t d, const float* gamma, const float* beta, float eps,
+                           float* out32, void* out16, immtsf_stream_t stream);
+int immtsf_bert_embed_attention(const float* qkv, int32_t ld, const int32_t* cu, int32_t N, int32_t rows, int32_t H, int32_t max_len,
+                                float scale, int32_t precision, float* out32, void* out16, immtsf_stream_t stream);
+int immtsf_bert_embed_add_layernorm(const float* y, const float* x, int64_t rows, int32_t d, const float* gamma, const float* beta, float eps,
+                                    float* out32, void* out16, immtsf_stream_t stream);
+int immtsf_bert_embed_gelu(const float* pre, uint64_t n, float* out32, void* out16, immtsf_stream_t stream);
+int immtsf_bert_embed_pool(const float* x, const int32_t* cu, int32_t N, int32_t rows, int32_t d, float* pooled, immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

@@ -9,8 +9,11 @@ The stock path runs the batch in slices of `--stock-slice` notes (a padded batch
 row-count ratio sum(L) / (N * max_length) -- what the algorithm alone saves -- is printed beside the times.  In ONE process, after
 warming both paths: `--passes` alternating passes, host clock around a pass with a synchronise at its end.  One JSON line per
 precision mode: milliseconds per workload, best pass and all passes (their spread is the noise).
+--model bert: the same two workloads on a BERT-base body (768 wide, 12 heads, intermediate 3072, random weights) cut to 6 layers as
+load_llm cuts it at the default llm_layers_fusion, max_length 512, behind a WordPiece stand-in ([CLS], one token per character, [SEP],
+right-padded) -> immtsf.ops.bert_embed_notes; token counts from a few to 512.
 
-usage: python tools/note_embed_bench.py [--notes 32] [--passes 3] [--single 8] [--out FILE]
+usage: python tools/note_embed_bench.py [--model gpt2|bert] [--notes 32] [--passes 3] [--single 8] [--out FILE]
 """
 import argparse
 import json
@@ -27,8 +30,12 @@ MAX_LENGTH = 1024
 
 
 class ByteTokenizer:
-    """stand-in: one token per byte (ids < 256), right-padded to max_length with the pad id, with the attention mask"""
+    """stand-in: one token per byte (ids < 256), right-padded to max_length with the pad id, with the attention mask; frame = (first id,
+    last id): the WordPiece stand-in, every note between [CLS] and [SEP] (truncation keeps the [SEP])"""
     padding_side = "right"
+
+    def __init__(self, frame=None):
+        self.frame = frame
 
     def __call__(self, texts, padding="max_length", truncation=True, max_length=MAX_LENGTH, return_tensors="pt"):
         import torch
@@ -36,19 +43,22 @@ class ByteTokenizer:
         attn = torch.zeros(len(texts), max_length, dtype=torch.long)
         for r, t in enumerate(texts):
             b = list(t.encode("utf-8"))[:max_length]
+            if self.frame:
+                b = [self.frame[0]] + b[:max_length - 2] + [self.frame[1]]
             ids[r, :len(b)] = torch.tensor(b, dtype=torch.long)
             attn[r, :len(b)] = 1
         return type("Enc", (), {"input_ids": ids, "attention_mask": attn})()
 
 
-def note_lengths(n):
+def note_lengths(n, cap=MAX_LENGTH):
     """most notes short (tens of tokens), some a few hundred, one at the cap"""
-    base = [24, 48, 40, 96, 64, 200, 32, 56, 80, 320, 28, 72, 44, 150, 36, 1024]
+    base = [24, 48, 40, 96, 64, 200, 32, 56, 80, 320, 28, 72, 44, 150, 36 if cap == MAX_LENGTH else 6, cap]
     return [base[i % len(base)] for i in range(n)]
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", choices=("gpt2", "bert"), default="gpt2")
     ap.add_argument("--notes", type=int, default=32)
     ap.add_argument("--single", type=int, default=8, help="notes of the one-call-per-note workload (the first ones of the mix)")
     ap.add_argument("--passes", type=int, default=3)
@@ -56,34 +66,43 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
-    from transformers import GPT2Config, GPT2Model
+    from transformers import BertConfig, BertModel, GPT2Config, GPT2Model
 
     from fusions import load_llm as L
     from immtsf import config
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    model = GPT2Model(GPT2Config(vocab_size=256, bos_token_id=0, eos_token_id=0)).requires_grad_(False).to(dev).eval()
-    tok = ByteTokenizer()
-    lengths = note_lengths(args.notes)
-    notes = [chr(97 + i % 26) * n for i, n in enumerate(lengths)]
-    ratio = sum(lengths) / (len(lengths) * MAX_LENGTH)
+    if args.model == "bert":
+        max_length, layers = 512, 6
+        model = BertModel(BertConfig(vocab_size=258, num_hidden_layers=layers, pad_token_id=0), add_pooling_layer=False)
+        tok = ByteTokenizer(frame=(256, 257))
+        lengths = note_lengths(args.notes, max_length)
+        notes = [chr(97 + i % 26) * (n - 2) for i, n in enumerate(lengths)]
+    else:
+        max_length, layers = MAX_LENGTH, 12
+        model = GPT2Model(GPT2Config(vocab_size=256, bos_token_id=0, eos_token_id=0))
+        tok = ByteTokenizer()
+        lengths = note_lengths(args.notes)
+        notes = [chr(97 + i % 26) * n for i, n in enumerate(lengths)]
+    model = model.requires_grad_(False).to(dev).eval()
+    ratio = sum(lengths) / (len(lengths) * max_length)
     print(f"note lengths (tokens): {lengths}", flush=True)
-    print(f"rows: real {sum(lengths)} of padded {len(lengths) * MAX_LENGTH} (ratio {ratio:.4f})", flush=True)
+    print(f"rows: real {sum(lengths)} of padded {len(lengths) * max_length} (ratio {ratio:.4f})", flush=True)
 
     def batch(fused):
         config.note_embed_fused = fused
         with torch.no_grad():
             if fused:
-                L.embed_notes([notes], tok, model, max_length=MAX_LENGTH)
+                L.embed_notes([notes], tok, model, max_length=max_length)
             else:
                 for i in range(0, len(notes), args.stock_slice):
-                    L.embed_notes([notes[i:i + args.stock_slice]], tok, model, max_length=MAX_LENGTH)
+                    L.embed_notes([notes[i:i + args.stock_slice]], tok, model, max_length=max_length)
 
     def single(fused):
         config.note_embed_fused = fused
         with torch.no_grad():
             for note in notes[:args.single]:
-                L.embed_notes([[note]], tok, model, max_length=MAX_LENGTH)
+                L.embed_notes([[note]], tok, model, max_length=max_length)
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -95,9 +114,9 @@ def main():
     lines = []
     for prec in ("fp32", "bf16"):
         config.precision = prec
-        line = {"tool": "note_embed_bench", "precision": prec, "layers": 12, "d": 768, "max_length": MAX_LENGTH, "notes": len(notes),
-                "row_ratio": round(ratio, 4), "single_notes": args.single, "single_row_ratio":
-                round(sum(lengths[:args.single]) / (args.single * MAX_LENGTH), 4), "passes": args.passes}
+        line = {"tool": "note_embed_bench", "model": args.model, "precision": prec, "layers": layers, "d": 768, "max_length": max_length,
+                "notes": len(notes), "row_ratio": round(ratio, 4), "single_notes": args.single, "single_row_ratio":
+                round(sum(lengths[:args.single]) / (args.single * max_length), 4), "passes": args.passes}
         for what, fn in (("batch", batch), ("single", single)):
             for fused in (True, False):
                 fn(fused)
