@@ -3,6 +3,7 @@
 #include "attn.hpp"
 #include "gemm.hpp"
 #include "rowops.hpp"
+#include "seam_small.hpp"
 #include "tail.hpp"
 #include "block_util.hpp"
 #include <atomic>
@@ -189,6 +190,23 @@ int immtsf_attention_short_backward(const float* qkv, const float* dout, int32_t
     DropCfg d = mk_drop(p_drop, seed);
     d.seed_dev = seed_step_dev;
     return launch_attn_short_bwd(qkv, dout, B, L, H, E, scale, causal, d, site, dqkv, static_cast<hipStream_t>(stream));
+}
+
+/* ---- test / tool entries of the seam's small-row kernels (csrc/seam_small.hip, layernorm_bwd_lr_kernel) */
+int immtsf_seam_route(int32_t rows, int32_t d, int32_t PW) { return seam_p_fwd_shape_ok(rows, d, PW) ? 1 : 0; }
+
+int immtsf_seam_p_bf16(const void* A, const void* W, const float* bias, float* P, int32_t rows, int32_t d, int32_t PW, immtsf_stream_t stream) {
+    return launch_seam_p_fwd(A, W, bias, P, rows, d, PW, static_cast<hipStream_t>(stream));
+}
+
+int immtsf_layernorm_backward_lowrank(const float* G, int32_t ldg, int32_t PW, const float* basis, int32_t rows, int32_t d, const float* gamma,
+                                      const float* xhat, const void* xhat_h, const float* rstd, float* dx, void* dxh, float p_drop,
+                                      const void* keep, int32_t keep_T, const uint8_t* row_flag, int32_t flag_div, float* dgamma, float* dbeta,
+                                      float* dxsum, float* scratch, size_t scratch_bytes, int32_t form, immtsf_stream_t stream) {
+    if (scratch_bytes < (size_t)256 * 3 * d * sizeof(float) || (form != 0 && form != 1)) return IMMTSF_EINVAL;
+    if (p_drop > 0.f && !keep) return IMMTSF_EINVAL;      // (this entry takes the forward's exported keep words only)
+    return launch_layernorm_bwd_lr(G, ldg, PW, basis, rows, d, gamma, xhat, xhat_h, rstd, dx, dxh, mk_drop(p_drop, 0), 0, dgamma, dbeta, dxsum,
+                                   scratch, row_flag, flag_div, static_cast<hipStream_t>(stream), keep, keep_T, form);
 }
 
 int immtsf_layernorm_forward(const float* x, int32_t rows, int32_t d, const float* gamma, const float* beta, float eps,

@@ -1674,12 +1674,16 @@ int launch_instance_norm(const float* x, int B, int L, int C, float* xn, float* 
 
 // the low-rank form: dy = G Wb (G: rows x PW, pitch ldg; Wb: PW x d) is never written -- see layernorm_bwd_lr_kernel.  x_hat as the
 // bf16 image, dx fp32 and / or bf16; sums and row flags as launch_layernorm_bwd_sums with out_q.  IMMTSF_EUNSUPPORTED outside its limits.
+#ifndef LNLR_SMALL_R
+#define LNLR_SMALL_R 2
+#endif
 bool ln_lr_ok(int rows, int d, int PW) {
     return (d & 3) == 0 && d <= 1024 && d >= 256 && PW >= 1 && PW <= 64 && rows >= 512 && (size_t)(PW + 3) * d * sizeof(float) <= 150 * 1024;
 }
 int launch_layernorm_bwd_lr(const float* G, int ldg, int PW, const float* Wb, int rows, int d, const float* gamma, const float* xhat,
                             const void* xhat_h, const float* rstd, float* dx, void* dxh, DropCfg drop, uint64_t site, float* out_gw, float* out_gb,
-                            float* out_q, float* scratch, const unsigned char* row_flag, int flag_div, hipStream_t s, const void* keep, int keep_T) {
+                            float* out_q, float* scratch, const unsigned char* row_flag, int flag_div, hipStream_t s, const void* keep, int keep_T,
+                            int form) {
     if (!ln_lr_ok(rows, d, PW)) return IMMTSF_EUNSUPPORTED;
     if (keep && (keep_T <= 0 || keep_T > 32)) return IMMTSF_EINVAL;
     if (!G || !Wb || (!xhat && !xhat_h) || (!dx && !dxh) || !out_gw || !out_gb || !out_q || !scratch) return IMMTSF_EINVAL;
@@ -1688,8 +1692,12 @@ int launch_layernorm_bwd_lr(const float* G, int ldg, int PW, const float* Wb, in
     if ((al & 15) || ((reinterpret_cast<uintptr_t>(dxh) | reinterpret_cast<uintptr_t>(xhat_h)) & 7)) return IMMTSF_EUNSUPPORTED;
     const void* xa = xhat_h ? xhat_h : static_cast<const void*>(xhat);
     const size_t lds = (size_t)(PW + 3) * d * sizeof(float);
+    // rows per wave R: every read of the basis from LDS serves R rows and a workgroup's copy of it 8 R.  From 8192 rows on, as many as
+    // the registers hold (4, or 2 with four chunks per lane); below, LNLR_SMALL_R = 2: 2048 rows are then 16 rows each on 128 workgroups,
+    // half the basis copies of one row per wave (in the 64-window step 4 on 64 workgroups was slower: profiles/seam_small_rows_summary.md)
     const bool many = rows >= 8192;
-    const int per_wg = 8 * (many ? (d <= 768 ? 4 : 2) : 1);
+    const int R = form == 1 ? 1 : many ? (d <= 768 ? 4 : 2) : (d <= 768 ? LNLR_SMALL_R : 2);
+    const int per_wg = 8 * R;
     int nsl = cdiv(rows, per_wg);
     nsl = nsl > 256 ? 256 : nsl;          // (one workgroup per CU: the LDS copy of Wb)
     const int fd = flag_div > 0 ? flag_div : 1;
@@ -1702,8 +1710,8 @@ int launch_layernorm_bwd_lr(const float* G, int ldg, int PW, const float* Wb, in
                            static_cast<bf16_t*>(dxh), drop, site, scratch, row_flag, fd, static_cast<const unsigned long long*>(keep), keep_T); \
     } while (0)
 #define LNLR2(RR, DVV) do { if (xhat_h) LNLR(RR, DVV, true); else LNLR(RR, DVV, false); } while (0)
-    if (d <= 768) { if (many) LNLR2(4, 3); else LNLR2(1, 3); }
-    else { if (many) LNLR2(2, 4); else LNLR2(1, 4); }       // (four chunks per lane: two rows at a time fit the registers)
+    if (d <= 768) { if (R == 4) LNLR2(4, 3); else if (R == 2) LNLR2(2, 3); else LNLR2(1, 3); }
+    else { if (R == 2) LNLR2(2, 4); else LNLR2(1, 4); }       // (four chunks per lane: two rows at a time fit the registers)
 #undef LNLR2
 #undef LNLR
     IMMTSF_LAUNCH_CHECK();

@@ -28,6 +28,7 @@
 #include "block_util.hpp"
 #include "t2v_fold.hpp"
 #include "eval.hpp"
+#include "seam_small.hpp"
 #include <math.h>
 #include <algorithm>
 #include <vector>
@@ -1629,7 +1630,9 @@ int immtsf_mmf_xrank_p_forward_z(const immtsf_fusion_cfg* cfg, const immtsf_xadd
         CHECK(launch_f32_to_bf16(Z, w.E16, (size_t)BT * d, s));
         Zm.h = w.E16;
     }
-    {   // P = Z Wc^T + bc
+    if (hf && seam_p_fwd_ok(BT, d, x.PW, Zm.h, w.Wc16, P)) {     // a few thousand rows: the skinny form (seam_small.hip)
+        CHECK(launch_seam_p_fwd(Zm.h, w.Wc16, w.bc, P, BT, d, x.PW, s));
+    } else {   // P = Z Wc^T + bc
         GemmArgs g = gemm_args(BT, x.PW, d, d, d, x.PW);
         set_problem2(g, 0, Zm, mat(w.Wc, w.Wc16), mat(P), w.bc);
         CHECK(immtsf_launch_gemm(GEMM_NT, prec, g, s));

@@ -443,6 +443,11 @@ _PROTOS = {
     "immtsf_adam_range": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
                                     C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_float, c_f32p, C.c_int32, C.c_void_p, c_stream]),
     "immtsf_guard_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_stream]),
+    "immtsf_seam_route": (C.c_int, [C.c_int32] * 3),
+    "immtsf_seam_p_bf16": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_stream]),
+    "immtsf_layernorm_backward_lowrank": (C.c_int, [c_f32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_f32p, c_f32p, C.c_void_p, c_f32p,
+                                                    c_f32p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_f32p, c_f32p,
+                                                    c_f32p, c_f32p, C.c_size_t, C.c_int32, c_stream]),
 }
 
 # the structs of the ABI in immtsf_abi_sizes' order (tests/test_abi.py compares ctypes.sizeof with the library's sizeof)

@@ -1026,6 +1026,22 @@ int immtsf_attention_short_forward(const float* qkv, int32_t B, int32_t L, int32
 int immtsf_attention_short_backward(const float* qkv, const float* dout, int32_t B, int32_t L, int32_t H, int32_t E, float scale,
                                     int32_t causal, float p_drop, uint64_t seed, uint64_t site, const uint64_t* seed_step_dev,
                                     float* dqkv, immtsf_stream_t stream);
+/* Test / tool entries of the small-row forward product of the rank-PW seam between TTF_T2V_XAttn and MMF_XAttn_Add
+ * (csrc/seam_small.hip; the product path reaches it inside immtsf_mmf_xrank_p_forward_z).  immtsf_seam_route: 1 when a product of
+ * this shape takes the small-row kernel, 0 when it stays on the GEMM family.  immtsf_seam_p_bf16: P (rows, PW fp32) = A (rows, d
+ * bf16) W (PW, d bf16)^T + bias (PW, may be NULL); IMMTSF_EUNSUPPORTED where immtsf_seam_route says 0. */
+int immtsf_seam_route(int32_t rows, int32_t d, int32_t PW);
+int immtsf_seam_p_bf16(const void* A, const void* W, const float* bias, float* P, int32_t rows, int32_t d, int32_t PW, immtsf_stream_t stream);
+/* LayerNorm backward whose upstream gradient arrives in low-rank form dy = G basis (G: rows x PW, pitch ldg; basis: PW x d), with the
+ * column sums dgamma, dbeta and dxsum (sum of dx before the row flags).  x_hat as fp32 (xhat) or as its bf16 image (xhat_h); dx as fp32
+ * and / or bf16 (dxh); p_drop > 0: the output dropout's keep words as the forward exported them (keep, keep_T <= 32 rows per window);
+ * row_flag: rows of windows with a zero flag come out zero.  scratch >= 256 * 3 * d floats.  form 0: the product rule; 1: one row per
+ * wave (what every row count below 8192 ran before; the tests' point of comparison).  IMMTSF_EUNSUPPORTED outside d in [256, 1024],
+ * 4 | d, PW <= 64, rows >= 512. */
+int immtsf_layernorm_backward_lowrank(const float* G, int32_t ldg, int32_t PW, const float* basis, int32_t rows, int32_t d, const float* gamma,
+                                      const float* xhat, const void* xhat_h, const float* rstd, float* dx, void* dxh, float p_drop,
+                                      const void* keep, int32_t keep_T, const uint8_t* row_flag, int32_t flag_div, float* dgamma, float* dbeta,
+                                      float* dxsum, float* scratch, size_t scratch_bytes, int32_t form, immtsf_stream_t stream);
 /* LayerNorm(+dropout) rows: xhat,rstd may be NULL in forward when no backward follows */
 int immtsf_layernorm_forward(const float* x, int32_t rows, int32_t d, const float* gamma, const float* beta, float eps,
                              float* xhat, float* rstd, float* z, float p_drop, uint64_t seed, uint64_t site,
