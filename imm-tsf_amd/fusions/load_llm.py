@@ -4,12 +4,14 @@ get_d_model / get_context_window_size mirror the alias table of the reference's 
 reference asks the HF hub, which needs network access; the fusion constructors only need the integers).
 
 load_llm / embed_notes (reference :79-201) keep the reference's signatures and results.  embed_notes pads every note to max_length
-tokens, runs the padded batch through the frozen LLM and averages each note's real-token rows.  For a GPT2Model or a BertModel on the
-GPU behind a right-padding tokenizer the same function is computed over the real tokens alone (immtsf.ops.gpt2_embed_notes: a causal
-model never lets a pad token into a real token's hidden state; immtsf.ops.bert_embed_notes: a padded key has an exact zero weight in a
-real query's softmax; the average never reads a pad row), so only the real ids are uploaded.  The padded-out notes of a window are
-the empty string: where that has no tokens (GPT-2) their rows are zeros without being run, where it has some (BERT's [CLS] [SEP]) the
-one note is run once in the same call and copied to every such row.  Every other case -- Llama, a left-padding tokenizer, the CPU,
+tokens, runs the padded batch through the frozen LLM and averages each note's real-token rows.  For a GPT2Model, a BertModel or a
+LlamaModel (Llama-3.1, deepseek-llm) on the GPU behind a right-padding tokenizer the same function is computed over the real tokens alone
+(immtsf.ops.gpt2_embed_notes, llama_embed_notes: a causal model never lets a pad token into a real token's hidden state, and Llama's
+rotary positions are arange(seq) whatever the mask is; immtsf.ops.bert_embed_notes: a padded key has an exact zero weight in a real
+query's softmax; the average never reads a pad row), so only the real ids are uploaded.  The padded-out notes of a window are the empty
+string: where that has no tokens (GPT-2) their rows are zeros without being run, where it has some (BERT's [CLS] [SEP], Llama's BOS) the
+one note is run once in the same call and copied to every such row.  Every other case -- another model class, a Llama outside
+llama_embed_notes_supported (parameters stored in bf16, dynamic / yarn / longrope RoPE), a left-padding tokenizer, the CPU,
 immtsf.config.note_embed_fused off, a model left in training mode with dropout -- runs the padded formulation on torch ops.
 path_calls counts which way each call went.
 """
@@ -97,7 +99,7 @@ def _token_counts(attn):
 def _family(llm_model):
     """what the fused path needs to know of a model family: (the packed-token op, its limits, the fewest notes of an fp32 call that take
     it, the config's dropout rates), or None for a model without one"""
-    from transformers import BertModel, GPT2Model
+    from transformers import BertModel, GPT2Model, LlamaModel
 
     from immtsf import ops
     if isinstance(llm_model, GPT2Model):
@@ -106,6 +108,8 @@ def _family(llm_model):
     if type(llm_model) is BertModel:
         return (ops.bert_embed_notes, ops.bert_embed_notes_supported, config.bert_embed_fp32_min_notes,
                 ("hidden_dropout_prob", "attention_probs_dropout_prob"))
+    if type(llm_model) is LlamaModel:
+        return (ops.llama_embed_notes, ops.llama_embed_notes_supported, config.llama_embed_fp32_min_notes, ("attention_dropout",))
     return None
 
 
@@ -117,7 +121,7 @@ def _fused_ok(llm_model, device, max_length, n_notes):
         return False
     _, supported, fp32_min_notes, drops = family
     if config.precision_code(None) == 0 and n_notes < fp32_min_notes:
-        return False             # (measured slower than the padded call there: DESIGN 4o, 4p)
+        return False             # (measured slower than the padded call there: DESIGN 4o, 4p, 4q)
     if not supported(llm_model, max_length):
         return False
     cfg = llm_model.config       # (a body left in training mode draws dropout masks in the padded formulation: that is not this kernel)

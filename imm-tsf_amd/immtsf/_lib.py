@@ -227,6 +227,18 @@ _PROTOS = {
                                                   c_stream]),
     "immtsf_bert_embed_gelu": (C.c_int, [c_f32p, C.c_uint64, c_f32p, C.c_void_p, c_stream]),
     "immtsf_bert_embed_pool": (C.c_int, [c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_stream]),
+    "immtsf_llama_embed_supported": (C.c_int, [C.c_int32] * 6),
+    "immtsf_llama_embed_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 6),
+    "immtsf_llama_embed_tokens": (C.c_int, [c_i32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_f32p, c_stream]),
+    "immtsf_llama_embed_rmsnorm": (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_float, c_f32p, C.c_void_p, c_stream]),
+    "immtsf_llama_embed_add_rmsnorm": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_float, c_f32p, C.c_void_p, c_stream]),
+    "immtsf_llama_embed_rope_table": (C.c_int, [c_f32p, C.c_float, C.c_int32, c_f32p, c_f32p, c_stream]),
+    "immtsf_llama_embed_rope": (C.c_int, [c_f32p, C.c_int32, c_i32p] + [C.c_int32] * 5 + [c_f32p, c_f32p, c_stream]),
+    "immtsf_llama_embed_attention": (C.c_int, [c_f32p, C.c_int32, c_i32p] + [C.c_int32] * 5 + [C.c_float, C.c_int32, c_f32p, C.c_void_p,
+                                               c_stream]),
+    "immtsf_llama_embed_swiglu": (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_void_p, c_stream]),
+    "immtsf_llama_embed_pool": (C.c_int, [c_f32p, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_float, c_f32p, c_f32p,
+                                          c_stream]),
     "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,

@@ -155,6 +155,10 @@ note_embed_fp32_min_notes = int(os.environ.get("IMMTSF_NOTE_EMBED_FP32_MIN_NOTES
 # 0.95x of the padded call (within the passes' spread of it: no win), 32 notes 1.8x.  bf16 mode takes the fused path at any count
 # (1.9x / 4.7x)
 bert_embed_fp32_min_notes = int(os.environ.get("IMMTSF_BERT_EMBED_FP32_MIN_NOTES", "2"))
+# ... and a frozen LlamaModel (immtsf.ops.llama_embed_notes: csrc/llama_embed.hip, the GEMM family), again with its own fp32 threshold.
+# Measured at Llama-3.1-8B's widths a single note per call is 3.0x the padded call in fp32 and 32 notes 2.0x (bf16: 8.5x /
+# 20x), so nothing is gated off: the threshold is 1
+llama_embed_fp32_min_notes = int(os.environ.get("IMMTSF_LLAMA_EMBED_FP32_MIN_NOTES", "1"))
 # LatentODE's forecasting() as one HIP launch forward and two backward (csrc/latent_ode.hip) wherever the encoder is the ODE-RNN with
 # rec_layers = gen_layers = 1, one trajectory sample, and immtsf_latent_ode_supported allows; IMMTSF_LATENTODE_FUSED=0: the composed path
 # (the reference's loop over the observed points on torch ops, the step plan copied to the host once) -- the cross-check.  fp32 in

@@ -3512,6 +3512,143 @@ def bert_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         return pooled
 
 
+# ------------------------------------------------------------------------------------------------ raw-text mode: notes through a frozen Llama
+_LLAMA_ROPE_TYPES = ("default", "linear", "llama3")      # inv_freq is fixed at construction: the module's buffer is the whole of it
+
+
+def _llama_dims(cfg):
+    """(d, H, H_kv, head_dim, inner) of a LlamaConfig"""
+    d, H = int(cfg.hidden_size), int(cfg.num_attention_heads)
+    return d, H, int(getattr(cfg, "num_key_value_heads", None) or H), int(getattr(cfg, "head_dim", None) or d // H), int(cfg.intermediate_size)
+
+
+def llama_embed_notes_supported(llm_model, max_len):
+    """the limits of llama_embed_notes: a transformers LlamaModel (the class itself) with head_dim 128, H query heads over H_kv K/V heads
+    with H / H_kv in {1, 2, 4, 8}, hidden_act "silu", neither attention nor MLP bias, rope_type default / linear / llama3 (those whose
+    inv_freq does not depend on the call: dynamic, yarn and longrope keep the stock path), at least one layer, fp32 parameters,
+    hidden_size and intermediate_size multiples of 8, and 1 <= max_len <= max_position_embeddings, <= 1024"""
+    from transformers import LlamaModel
+    if type(llm_model) is not LlamaModel or max_len < 1:
+        return False
+    cfg = llm_model.config
+    d, H, H_kv, hd, inner = _llama_dims(cfg)
+    rope = getattr(llm_model, "rotary_emb", None)
+    if (hd != 128 or cfg.hidden_act != "silu" or getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False) or
+            len(llm_model.layers) < 1 or getattr(rope, "rope_type", None) not in _LLAMA_ROPE_TYPES or
+            tuple(getattr(rope, "inv_freq", torch.zeros(0)).shape) != (64,)):
+        return False
+    if any(p.dtype != torch.float32 for p in llm_model.parameters()):
+        return False
+    return bool(_lib.load().immtsf_llama_embed_supported(d, H, H_kv, inner, int(max_len), int(cfg.max_position_embeddings)))
+
+
+def _llama_cat(model, owner, slot, linears, bf):
+    """(W, bf16 image of W or None): the weights of `linears` concatenated along the output axis, once, cached on the model under
+    (owner, slot) and keyed by the parameters' storage address and version: load_state_dict(), .to() or any in-place write makes a new one"""
+    cache = model.__dict__.setdefault("_immtsf_llama_cat", {})
+    params = tuple(lin.weight for lin in linears)
+    key = tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in params)
+    hit = cache.get((id(owner), slot))
+    if hit is None or hit[0] != key:
+        hit = cache[(id(owner), slot)] = [key, torch.cat([p.detach() for p in params], 0).contiguous(), None]
+    if bf and hit[2] is None:
+        hit[2] = torch.empty(hit[1].shape, dtype=torch.bfloat16, device=hit[1].device)
+        check(_lib.load().immtsf_f32_to_bf16(ptr(hit[1]), ptr(hit[2]), hit[1].numel(), stream_ptr()), "f32_to_bf16")
+    return hit[1], hit[2]
+
+
+def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
+    """pooled (N, d) fp32: the mean over each note's tokens of the frozen LlamaModel's last hidden state -- reference fusions/load_llm.py
+    embed_notes without the padding (csrc/llama_embed.hip and the GEMM family over the packed rows; 9 launches a layer + 5).  ids (sum L)
+    int32: the notes' real tokens back to back; cu (N + 1) int32: prefix sums of the token counts; both on the model's device.  Positions
+    are 0 .. L - 1 inside each note, the cos / sin table is built per call from the model's own rotary_emb.inv_freq and
+    attention_scaling.  A note of no tokens gives an exact zero row.  max_len: an upper bound of the token counts (read from cu when not
+    given: one device -> host copy).  The model's parameters are read in place, but for the cached q | k | v and gate | up concatenations
+    and, in bf16 mode, the cached bf16 weight images; runs under no_grad and saves nothing.  Outside llama_embed_notes_supported this
+    raises: callers check."""
+    with torch.no_grad():
+        _need_gpu(ids, cu)
+        if ids.dtype != torch.int32 or cu.dtype != torch.int32 or ids.dim() != 1 or cu.dim() != 1 or cu.numel() < 1:
+            raise _lib.ImmtsfError("llama_embed_notes: ids (sum L) and cu (N + 1) are int32 vectors")
+        ids, cu = _c(ids), _c(cu)
+        N, T = cu.numel() - 1, ids.numel()
+        cfg = llm_model.config
+        dev = ids.device
+        if max_len is None:
+            max_len = int((cu[1:] - cu[:-1]).max()) if T and N else 1
+        max_len = max(int(max_len), 1)
+        if not llama_embed_notes_supported(llm_model, max_len):
+            raise _lib.ImmtsfError("llama_embed_notes: this model / note length is outside llama_embed_notes_supported")
+        d, H, H_kv, hd, inner = _llama_dims(cfg)
+        if N == 0:
+            return torch.zeros(0, d, dtype=torch.float32, device=dev)
+        dq, dqkv = H * hd, (H + 2 * H_kv) * hd
+        if T >= 2 ** 31 // (4 * max(d, dqkv, 2 * inner)):
+            raise _lib.ImmtsfError("llama_embed_notes: too many tokens for one call (split the batch)")
+        lib = _lib.load()
+        st = stream_ptr()
+        precision = config.precision_code(precision)
+        bf = precision == 1
+        eps = float(cfg.rms_norm_eps)
+        scale = 1.0 / float(hd) ** 0.5
+        pooled = torch.empty(N, d, dtype=torch.float32, device=dev)
+        if T == 0:
+            return pooled.zero_()
+        # one workspace for the whole pass, carved as include/immtsf.h lists it
+        ws = _bytes(lib.immtsf_llama_embed_workspace_bytes(T, d, H, H_kv, inner, max_len, precision), dev)
+        off = [0]
+
+        def carve(rows, cols, dt=torch.float32):
+            nbytes = rows * cols * (2 if dt == torch.bfloat16 else 4)
+            t = ws[off[0]:off[0] + nbytes].view(dt).view(rows, cols)
+            off[0] += (nbytes + 255) & ~255
+            return t
+
+        op = torch.bfloat16 if bf else torch.float32
+        x, h, qkv, ao, pr, gu, act = (carve(T, d), carve(T, d, op), carve(T, dqkv), carve(T, dq, op), carve(T, d), carve(T, 2 * inner),
+                                      carve(T, inner, op))
+        cos_t, sin_t, rstd = carve(max_len, 64), carve(max_len, 64), carve(T, 1)
+        assert off[0] <= ws.numel()
+        o32 = lambda t: None if bf else ptr(t)      # noqa: E731
+        o16 = lambda t: ptr(t) if bf else None      # noqa: E731
+
+        def mm(a, W, W16, out):
+            """out (T, N_out) = a (T, K) W^T: W (N_out, K) is the nn.Linear weight as stored (layout 0); Llama's Linears have no bias"""
+            N_out, K = W.shape
+            check(lib.immtsf_gpt2_gemm(0, precision, o32(a), o16(a), K, ptr(W), ptr(W16) if bf else None, K, ptr(out), N_out, None, T, N_out, K,
+                                       st), "gpt2_gemm")
+
+        def lin(a, dense, out):
+            mm(a, dense.weight, _gpt2_w16(llm_model, dense.weight) if bf else None, out)
+
+        rope = llm_model.rotary_emb
+        inv_freq = rope.inv_freq.detach().to(device=dev, dtype=torch.float32).contiguous()
+        check(lib.immtsf_llama_embed_rope_table(ptr(inv_freq), float(rope.attention_scaling), max_len, ptr(cos_t), ptr(sin_t), st),
+              "llama_embed_rope_table")
+        emb = llm_model.embed_tokens.weight
+        check(lib.immtsf_llama_embed_tokens(ptr(ids), T, ptr(emb), int(emb.shape[0]), d, ptr(x), st), "llama_embed_tokens")
+        for i, layer in enumerate(llm_model.layers):
+            att, mlp = layer.self_attn, layer.mlp
+            w_in = layer.input_layernorm.weight
+            if i == 0:
+                check(lib.immtsf_llama_embed_rmsnorm(ptr(x), T, d, ptr(w_in), eps, o32(h), o16(h), st), "llama_embed_rmsnorm")
+            else:      # the residual add of the layer before rides on this norm
+                check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(w_in), eps, o32(h), o16(h), st), "llama_embed_add_rmsnorm")
+            mm(h, *_llama_cat(llm_model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf), qkv)
+            check(lib.immtsf_llama_embed_rope(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, ptr(cos_t), ptr(sin_t), st), "llama_embed_rope")
+            check(lib.immtsf_llama_embed_attention(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, scale, precision, o32(ao), o16(ao), st),
+                  "llama_embed_attention")
+            lin(ao, att.o_proj, pr)
+            check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(layer.post_attention_layernorm.weight), eps, o32(h), o16(h), st),
+                  "llama_embed_add_rmsnorm")
+            mm(h, *_llama_cat(llm_model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf), gu)
+            check(lib.immtsf_llama_embed_swiglu(ptr(gu), T, inner, o32(act), o16(act), st), "llama_embed_swiglu")
+            lin(act, mlp.down_proj, pr)
+        check(lib.immtsf_llama_embed_pool(ptr(x), ptr(pr), ptr(cu), N, T, d, ptr(llm_model.norm.weight), eps, ptr(rstd), ptr(pooled), st),
+              "llama_embed_pool")
+        return pooled
+
+
 # ------------------------------------------------------------------------------------------------ LatentODE backbone
 def _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents):
     return _lib.LatentODEDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(units), int(gru_units), int(latents))

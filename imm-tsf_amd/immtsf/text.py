@@ -1,8 +1,8 @@
 """Corpus-level note embedding: what the reference's compute_text_embeddings.py loops over one note per call, as a few launches.
 
 embed_corpus tokenises every note once (the reference's tokenizer call), orders the notes by token count, cuts that order into groups
-of at most `tokens_per_batch` real tokens and sends each group through fusions.load_llm's pooling -- immtsf.ops.gpt2_embed_notes or
-bert_embed_notes over the packed tokens where the fused conditions hold, the padded formulation otherwise -- then puts the rows back
+of at most `tokens_per_batch` real tokens and sends each group through fusions.load_llm's pooling -- immtsf.ops.gpt2_embed_notes,
+bert_embed_notes or llama_embed_notes over the packed tokens where the fused conditions hold, the padded formulation otherwise -- then puts the rows back
 in input order on the CPU. (Grouping by length costs the fused path nothing and keeps the stock path's padded batches small.)
 """
 import torch

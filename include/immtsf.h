@@ -833,6 +833,55 @@ int immtsf_bert_embed_add_layernorm(const float* y, const float* x, int64_t rows
 int immtsf_bert_embed_gelu(const float* pre, uint64_t n, float* out32, void* out16, immtsf_stream_t stream);
 int immtsf_bert_embed_pool(const float* x, const int32_t* cu, int32_t N, int32_t rows, int32_t d, float* pooled, immtsf_stream_t stream);
 
+/* ---- Raw-text mode, Llama (added within ABI 7: new functions only; csrc/llama_embed.hip): what immtsf.ops.llama_embed_notes composes with
+ * immtsf_gpt2_gemm layout 0 (an nn.Linear weight as stored, bias null) into reference fusions/load_llm.py embed_notes for a frozen
+ * LlamaModel (Llama-3.1, deepseek-llm) -- over the RAGGED tokens, ids / cu as above.  The model is causal and its positions are
+ * arange(seq) whatever the mask is, so behind a right-padding tokenizer a real token has the same hidden state with or without the
+ * padding and the mean-pool reads real tokens only.  Pre-norm body, 9 launches a layer: RMSNorm (behind the residual add of the layer
+ * before), QKV (one product over q_proj | k_proj | v_proj), RoPE, attention, o_proj, add + RMSNorm, gate_proj | up_proj (one product),
+ * SwiGLU, down_proj.  Forward only, no dropout, no atomics, fixed summation order (the same inputs give the same bits).  head_dim is
+ * 128; H query heads over H_kv K/V heads, G = H / H_kv in {1, 2, 4, 8}.
+ * ..._supported: d, inner > 0 and multiples of 8, H % H_kv == 0 with G in {1, 2, 4, 8}, H_kv <= 65535, 1 <= max_len <= max_positions,
+ *   max_len <= 1024 (max_len: an upper bound of every note's length).
+ * ..._workspace_bytes: the buffers of one pass, each rounded up to 256 bytes, in this order: x (rows, d) fp32; h (rows, d) fp32 | bf16;
+ *   qkv (rows, (H + 2 H_kv) 128) fp32; ao (rows, 128 H) fp32 | bf16; proj (rows, d) fp32; gu (rows, 2 inner) fp32; act (rows, inner) fp32 |
+ *   bf16; cos, sin (max_len, 64) fp32; rstd (rows) fp32 -- bf16 in precision 1 (the GEMM operand images).  Host arithmetic only.
+ * ..._tokens: out[r, :] = embed[ids[r], :] (an id outside [0, vocab) is clamped into the table; callers check the ids first).  d % 4 == 0.
+ * ..._rmsnorm: out32 / out16[r, :] = x[r, :] rsqrt(mean(x[r, :]^2) + eps) w[:] over `rows` rows, fp32 statistics; either output may be
+ *   null, not both.  d % 4 == 0.
+ * ..._add_rmsnorm: x[r, :] <- x[r, :] + y[r, :] in place, then ..._rmsnorm of the sum.
+ * ..._rope_table: cos_out / sin_out[p, i] = cos / sin(float(p) inv_freq[i]) attention_scaling for p < max_len, i < 64: the angle is one
+ *   fp32 product, cos / sin the precise single-precision functions (transformers' LlamaRotaryEmbedding).  inv_freq (64) on the device.
+ * ..._rope: rotates, in place, the H query heads and the H_kv key heads of each row of qkv (rows; pitch ld >= (H + 2 H_kv) 128) by the
+ *   row's position p = r - cu[n] (clamped into [0, max_len)): (x[i], x[i + 64]) <- (x[i] c - x[i + 64] s, x[i + 64] c + x[i] s) with
+ *   c = cos_t[p, i], s = sin_t[p, i] -- rotate_half's pairing.  The value heads are not touched.
+ * ..._attention: causal attention inside each note: query p of note n and head h sees keys 0 .. p of note n and K/V head h / G; q at
+ *   columns 128 h, k at 128 (H + kvh), v at 128 (H + H_kv + kvh) of a row of qkv; out32 / out16 (rows, 128 H): the layout o_proj reads
+ *   (either may be null).  scale multiplies q . k.  precision 0: fp32 on the VALU; 1: both products on bf16 MFMA with fp32 accumulation,
+ *   fp32 online softmax.  Grid (note, K/V head, query tile of 32 in reverse order), G waves a workgroup sharing the K / V tiles; a note
+ *   longer than max_len is cut there.
+ * ..._swiglu: out[r, c] = silu(gu[r, c]) gu[r, inner + c] for gu (rows, 2 inner), into out32 and / or out16 (rows, inner).  inner % 4 == 0.
+ * ..._pool: x <- x + y in place when y is given (the last down_proj's residual add), rstd[r] = rsqrt(mean(x[r, :]^2) + eps), then
+ *   pooled[n, :] = w[:] sum over note n's rows, in position order, of x[row, :] rstd[row], divided by max(L, 1): a note of no tokens gives
+ *   an exact zero row.  A note whose range does not lie in [0, rows) or is longer than 1024 counts as empty.  Two launches.
+ * Arguments outside these limits give IMMTSF_EINVAL / IMMTSF_EUNSUPPORTED before anything is launched; nothing allocates or synchronises. */
+int immtsf_llama_embed_supported(int32_t d, int32_t H, int32_t H_kv, int32_t inner, int32_t max_len, int32_t max_positions);
+size_t immtsf_llama_embed_workspace_bytes(int64_t rows, int32_t d, int32_t H, int32_t H_kv, int32_t inner, int32_t max_len, int32_t precision);
+int immtsf_llama_embed_tokens(const int32_t* ids, int32_t rows, const float* embed, int32_t vocab, int32_t d, float* out, immtsf_stream_t stream);
+int immtsf_llama_embed_rmsnorm(const float* x, int64_t rows, int32_t d, const float* w, float eps, float* out32, void* out16,
+                               immtsf_stream_t stream);
+int immtsf_llama_embed_add_rmsnorm(float* x, const float* y, int64_t rows, int32_t d, const float* w, float eps, float* out32, void* out16,
+                                   immtsf_stream_t stream);
+int immtsf_llama_embed_rope_table(const float* inv_freq, float attention_scaling, int32_t max_len, float* cos_out, float* sin_out,
+                                  immtsf_stream_t stream);
+int immtsf_llama_embed_rope(float* qkv, int32_t ld, const int32_t* cu, int32_t N, int32_t rows, int32_t H, int32_t H_kv, int32_t max_len,
+                            const float* cos_t, const float* sin_t, immtsf_stream_t stream);
+int immtsf_llama_embed_attention(const float* qkv, int32_t ld, const int32_t* cu, int32_t N, int32_t rows, int32_t H, int32_t H_kv,
+                                 int32_t max_len, float scale, int32_t precision, float* out32, void* out16, immtsf_stream_t stream);
+int immtsf_llama_embed_swiglu(const float* gu, int64_t rows, int32_t inner, float* out32, void* out16, immtsf_stream_t stream);
+int immtsf_llama_embed_pool(float* x, const float* y, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const float* w, float eps,
+                            float* rstd, float* pooled, immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

@@ -12,8 +12,11 @@ precision mode: milliseconds per workload, best pass and all passes (their sprea
 --model bert: the same two workloads on a BERT-base body (768 wide, 12 heads, intermediate 3072, random weights) cut to 6 layers as
 load_llm cuts it at the default llm_layers_fusion, max_length 512, behind a WordPiece stand-in ([CLS], one token per character, [SEP],
 right-padded) -> immtsf.ops.bert_embed_notes; token counts from a few to 512.
+--model llama: the widths of Llama-3.1-8B (4096 wide, 32 heads over 8 K/V heads, head_dim 128, intermediate 14336, llama3 RoPE, random
+weights) cut to `--layers` layers (default 2: the whole body is 32 of them and every layer costs the same, so the times scale and the
+ratios stand), max_length 1024, the GPT-2 note mix behind a begin-of-text token -> immtsf.ops.llama_embed_notes.
 
-usage: python tools/note_embed_bench.py [--model gpt2|bert] [--notes 32] [--passes 3] [--single 8] [--out FILE]
+usage: python tools/note_embed_bench.py [--model gpt2|bert|llama] [--layers 2] [--notes 32] [--passes 3] [--single 8] [--out FILE]
 """
 import argparse
 import json
@@ -31,7 +34,8 @@ MAX_LENGTH = 1024
 
 class ByteTokenizer:
     """stand-in: one token per byte (ids < 256), right-padded to max_length with the pad id, with the attention mask; frame = (first id,
-    last id): the WordPiece stand-in, every note between [CLS] and [SEP] (truncation keeps the [SEP])"""
+    last id): the WordPiece stand-in, every note between [CLS] and [SEP] (truncation keeps the [SEP]); last id None: the Llama stand-in,
+    the begin-of-text token in front only"""
     padding_side = "right"
 
     def __init__(self, frame=None):
@@ -44,7 +48,8 @@ class ByteTokenizer:
         for r, t in enumerate(texts):
             b = list(t.encode("utf-8"))[:max_length]
             if self.frame:
-                b = [self.frame[0]] + b[:max_length - 2] + [self.frame[1]]
+                tail = [] if self.frame[1] is None else [self.frame[1]]
+                b = [self.frame[0]] + b[:max_length - 1 - len(tail)] + tail
             ids[r, :len(b)] = torch.tensor(b, dtype=torch.long)
             attn[r, :len(b)] = 1
         return type("Enc", (), {"input_ids": ids, "attention_mask": attn})()
@@ -58,7 +63,8 @@ def note_lengths(n, cap=MAX_LENGTH):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--model", choices=("gpt2", "bert"), default="gpt2")
+    ap.add_argument("--model", choices=("gpt2", "bert", "llama"), default="gpt2")
+    ap.add_argument("--layers", type=int, default=2, help="layers of the --model llama body")
     ap.add_argument("--notes", type=int, default=32)
     ap.add_argument("--single", type=int, default=8, help="notes of the one-call-per-note workload (the first ones of the mix)")
     ap.add_argument("--passes", type=int, default=3)
@@ -66,7 +72,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
-    from transformers import BertConfig, BertModel, GPT2Config, GPT2Model
+    from transformers import BertConfig, BertModel, GPT2Config, GPT2Model, LlamaConfig, LlamaModel
 
     from fusions import load_llm as L
     from immtsf import config
@@ -78,6 +84,17 @@ def main():
         tok = ByteTokenizer(frame=(256, 257))
         lengths = note_lengths(args.notes, max_length)
         notes = [chr(97 + i % 26) * (n - 2) for i, n in enumerate(lengths)]
+    elif args.model == "llama":
+        max_length, layers = MAX_LENGTH, args.layers
+        cfg = LlamaConfig(vocab_size=257, hidden_size=4096, num_hidden_layers=layers, num_attention_heads=32, num_key_value_heads=8,
+                          intermediate_size=14336, max_position_embeddings=131072, bos_token_id=256, eos_token_id=0, pad_token_id=None,
+                          rope_parameters={"rope_type": "llama3", "rope_theta": 500000.0, "factor": 8.0, "low_freq_factor": 1.0,
+                                           "high_freq_factor": 4.0, "original_max_position_embeddings": 8192})
+        with torch.device(dev):            # (a layer is 218 M parameters: initialised on the device)
+            model = LlamaModel(cfg)
+        tok = ByteTokenizer(frame=(256, None))
+        lengths = note_lengths(args.notes)
+        notes = [chr(97 + i % 26) * (n - 1) for i, n in enumerate(lengths)]
     else:
         max_length, layers = MAX_LENGTH, 12
         model = GPT2Model(GPT2Config(vocab_size=256, bos_token_id=0, eos_token_id=0))
@@ -114,7 +131,7 @@ def main():
     lines = []
     for prec in ("fp32", "bf16"):
         config.precision = prec
-        line = {"tool": "note_embed_bench", "model": args.model, "precision": prec, "layers": layers, "d": 768, "max_length": max_length,
+        line = {"tool": "note_embed_bench", "model": args.model, "precision": prec, "layers": layers, "d": int(getattr(model.config, "hidden_size", 768)), "max_length": max_length,
                 "notes": len(notes), "row_ratio": round(ratio, 4), "single_notes": args.single, "single_row_ratio":
                 round(sum(lengths[:args.single]) / (args.single * max_length), 4), "passes": args.passes}
         for what, fn in (("batch", batch), ("single", single)):
