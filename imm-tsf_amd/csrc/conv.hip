@@ -116,6 +116,19 @@ __global__ __launch_bounds__(256) void period_g0_kernel(const float* __restrict_
     *reinterpret_cast<bf16x4*>(g16 + at) = h;
 }
 // dx[row, :] = sum over the k images that hold the row (row < rows[z]) of dxk[z, row, :]   (one input shared by every period image)
+// Four channels per thread: only for C % 4 == 0 and 16-byte aligned bases (launch_period_sum) -- then `per` is a multiple of 4, a vector
+// stays inside one row and every slice z * per keeps the alignment.  Any other channel count takes the scalar form below: a vector there
+// would straddle two rows (the second may lie beyond rows[z]: never written) and, with per % 4 == 2, run two floats past dxk and dx.
+__global__ __launch_bounds__(256) void period_sum1_kernel(const float* __restrict__ dxk, int k, long per, const int* __restrict__ rows, int C,
+                                                           float* __restrict__ dx) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= per) return;
+    const int row = (int)(i / C);
+    float a = 0.f;
+    for (int z = 0; z < k; ++z)
+        if (row < rows[z]) a += dxk[(size_t)z * per + i];
+    dx[i] = a;
+}
 __global__ __launch_bounds__(256) void period_sum_kernel(const float* __restrict__ dxk, int k, long per, const int* __restrict__ rows, int C,
                                                           float* __restrict__ dx) {
     const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -129,6 +142,12 @@ __global__ __launch_bounds__(256) void period_sum_kernel(const float* __restrict
         }
     }
     *reinterpret_cast<float4*>(dx + i) = a;
+}
+static void launch_period_sum(const float* dxk, int k, long per, const int* rows, int C, float* dx, hipStream_t s) {
+    if ((C & 3) == 0 && (reinterpret_cast<uintptr_t>(dxk) & 15) == 0 && (reinterpret_cast<uintptr_t>(dx) & 15) == 0)
+        hipLaunchKernelGGL(period_sum_kernel, dim3((unsigned)((per / 4 + 255) / 256)), dim3(256), 0, s, dxk, k, per, rows, C, dx);
+    else
+        hipLaunchKernelGGL(period_sum1_kernel, dim3((unsigned)((per + 255) / 256)), dim3(256), 0, s, dxk, k, per, rows, C, dx);
 }
 __global__ __launch_bounds__(256) void gelu_rows_kernel(const float* __restrict__ z, float* __restrict__ y, int Cout, const int* __restrict__ rows) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x, n = (long)*rows * Cout;
@@ -784,8 +803,7 @@ int immtsf_conv2d_periods_backward(int32_t precision, const float* col, const fl
         }
     }
     if (dx && dx_shared) {
-        const long n4 = ((long)per_x + 3) / 4;
-        hipLaunchKernelGGL(period_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, dxk, k, (long)per_x, rows, Cin, dx);
+        launch_period_sum(dxk, k, (long)per_x, rows, Cin, dx, s);
         IMMTSF_LAUNCH_CHECK();
     }
     return IMMTSF_OK;
@@ -861,8 +879,7 @@ int immtsf_conv2d_periods_backward_x(int32_t precision, const float* x, int64_t 
             CHECK(launch_conv_period_mfma(B, Lmax, k, Cout, KS, period, rows, g0, (long)per_y, Wf16, nullptr, Cin, 0, nullptr, dx_shared ? dxk : dx,
                                           (long)per_x, s));
             if (dx_shared) {
-                const long m4 = ((long)per_x + 3) / 4;
-                hipLaunchKernelGGL(period_sum_kernel, dim3((unsigned)((m4 + 255) / 256)), dim3(256), 0, s, dxk, k, (long)per_x, rows, Cin, dx);
+                launch_period_sum(dxk, k, (long)per_x, rows, Cin, dx, s);
                 IMMTSF_LAUNCH_CHECK();
             }
         }
