@@ -3649,6 +3649,212 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         return pooled
 
 
+# ------------------------------------------------------------------------------------------------ TimeLLM: the frozen Llama body
+def llama_body_supported(llm_model, S_p, S_t):
+    """the limits of llama_body: llama_embed_notes_supported's conditions on the model (the LlamaModel class itself, head_dim 128,
+    H / H_kv in {1, 2, 4, 8}, silu, no attention or MLP bias, rope_type default / linear / llama3, fp32 parameters, widths multiples of
+    8), S_p >= 0, S_t >= 1 and S = S_p + S_t <= max_position_embeddings, <= 1024"""
+    if S_p < 0 or S_t < 1 or not llama_embed_notes_supported(llm_model, 1):
+        return False
+    cfg = llm_model.config
+    d, H, H_kv, _, inner = _llama_dims(cfg)
+    return bool(_lib.load().immtsf_llama_body_supported(d, H, H_kv, inner, int(S_p + S_t), int(cfg.max_position_embeddings)))
+
+
+class LlamaBodyFn(torch.autograd.Function):
+    """transformers' LlamaModel(inputs_embeds=cat([prefix, tail], 1)).last_hidden_state[:, -S_t:] on csrc/llama_body.hip, the forward row
+    kernels of csrc/llama_embed.hip and the GEMM family.  The body is frozen and only `tail` takes a gradient; there is no
+    attention mask, so positions are arange(S), attention is plain causal, no prefix row depends on a tail row and the backward runs
+    over the B S_t tail rows alone (exactly).  The last layer computes queries, o_proj and the MLP for the tail rows only.  Saved per
+    layer: the roped K and V of all rows and, for the tail rows, the block input, both rstd, the roped q, the attention output, the
+    log-sum-exp, the post-attention residual and the gate | up product."""
+
+    @staticmethod
+    def forward(ctx, tail, prefix, model, precision, need_bwd):
+        lib = _lib.load()
+        st = stream_ptr()
+        cfg = model.config
+        B, S_t, d = tail.shape
+        S_p = 0 if prefix is None else prefix.shape[1]
+        S, L = S_p + S_t, len(model.layers)
+        _, H, H_kv, hd, inner = _llama_dims(cfg)
+        dq, dkv = H * hd, H_kv * hd
+        dqkv = dq + 2 * dkv
+        dev = tail.device
+        bf = precision == 1
+        eps = float(cfg.rms_norm_eps)
+        scale = 1.0 / float(hd) ** 0.5
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
+        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)      # noqa: E731
+        adr = lambda t, off=0: None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
+
+        def mm(a, W, W16, M, out, ldc, w_row=0, n_out=None, c_off=0):
+            """out[:, c_off:c_off + n_out] = a (M, K) W[w_row:w_row + n_out]^T: W (N, K) is the nn.Linear weight as stored (layout 0)"""
+            K = W.shape[1]
+            n_out = W.shape[0] if n_out is None else n_out
+            check(lib.immtsf_gpt2_gemm(0, precision, None if bf else ptr(a), ptr(a) if bf else None, K, adr(W, w_row * K),
+                                       adr(W16, w_row * K) if bf else None, K, adr(out, c_off), ldc, None, M, n_out, K, st), "gpt2_gemm")
+
+        def lin(a, dense, M, out):
+            mm(a, dense.weight, _gpt2_w16(model, dense.weight) if bf else None, M, out, dense.weight.shape[0])
+
+        def rms(xin, S_in, s_from, y, w, stats):
+            """(row sums xin + y or xin itself, normed operand, rstd) of the rows s_from .. S_in - 1, compact"""
+            n = B * (S_in - s_from)
+            xo = f32(n, d) if y is not None else None
+            h = b16(n, d) if bf else f32(n, d)
+            rstd = f32(n) if stats else None
+            check(lib.immtsf_llama_body_rmsnorm(ptr(xin), B, S_in, s_from, d, ptr(y), ptr(xo), ptr(w), eps, None if bf else ptr(h),
+                                                ptr(h) if bf else None, ptr(rstd), st), "llama_body_rmsnorm")
+            return (xin if xo is None else xo), h, rstd
+
+        def rope(buf, off, ld, rows, rows_per_b, pos0, heads):
+            check(lib.immtsf_llama_body_rope(adr(buf, off), ld, rows, rows_per_b, pos0, heads, S, ptr(cos_t), ptr(sin_t), 0, None, st),
+                  "llama_body_rope")
+
+        def tl(t, rows_per_b):        # the tail rows of a (B rows_per_b, ...) tensor, compact
+            if rows_per_b == S_t:
+                return t
+            return t.view(B, rows_per_b, -1)[:, rows_per_b - S_t:].contiguous().view(B * S_t, -1)
+
+        rot = model.rotary_emb
+        inv_freq = rot.inv_freq.detach().to(device=dev, dtype=torch.float32).contiguous()
+        cos_t, sin_t = f32(S, 64), f32(S, 64)
+        check(lib.immtsf_llama_embed_rope_table(ptr(inv_freq), float(rot.attention_scaling), S, ptr(cos_t), ptr(sin_t), st),
+              "llama_embed_rope_table")
+        x = tail.view(B * S_t, d) if prefix is None else torch.cat([prefix, tail], 1).view(B * S, d)
+        y, Sx = None, S               # y: the MLP output of the layer before, added behind the next norm; Sx: rows per sequence of x
+        saved = []
+        for li, layer in enumerate(model.layers):
+            att, mlp = layer.self_attn, layer.mlp
+            qf = S_p if li == L - 1 else 0
+            Sq = S - qf
+            x, h, rstd1 = rms(x, Sx, 0, y, layer.input_layernorm.weight, need_bwd)
+            W, W16 = _llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf)
+            if qf == 0:
+                qkv = f32(B * S, dqkv)
+                mm(h, W, W16, B * S, qkv, dqkv)
+                rope(qkv, 0, dqkv, B * S, S, 0, H + H_kv)
+                q, ldq, kv, ldkv, k_off = qkv, dqkv, qkv, dqkv, dq
+            else:           # the last layer: K and V of all rows, queries of the tail rows
+                kv = f32(B * S, 2 * dkv)
+                mm(h, W, W16, B * S, kv, 2 * dkv, w_row=dq, n_out=2 * dkv)
+                rope(kv, 0, 2 * dkv, B * S, S, 0, H_kv)
+                _, ht, _ = rms(x, S, qf, None, layer.input_layernorm.weight, False)
+                q = f32(B * Sq, dq)
+                mm(ht, W, W16, B * Sq, q, dq, n_out=dq)
+                rope(q, 0, dq, B * Sq, Sq, qf, H)
+                ldq, ldkv, k_off = dq, 2 * dkv, 0
+            ao32 = f32(B * Sq, dq) if (need_bwd or not bf) else None
+            ao16 = b16(B * Sq, dq) if bf else None
+            lse = f32(B * Sq, H) if need_bwd else None
+            check(lib.immtsf_llama_body_attention_forward(ptr(q), ldq, adr(kv, k_off), adr(kv, k_off + dkv), ldkv, B, S, H, H_kv, qf, scale,
+                                                          precision, ptr(ao32), ptr(ao16), ptr(lse), st), "llama_body_attention_forward")
+            pr = f32(B * Sq, d)
+            lin(ao16 if bf else ao32, att.o_proj, B * Sq, pr)
+            x1, g, rstd2 = rms(x, S, qf, pr, layer.post_attention_layernorm.weight, need_bwd)
+            gu = f32(B * Sq, 2 * inner)
+            mm(g, *_llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf), B * Sq, gu, 2 * inner)
+            act = b16(B * Sq, inner) if bf else f32(B * Sq, inner)
+            check(lib.immtsf_llama_embed_swiglu(ptr(gu), B * Sq, inner, None if bf else ptr(act), ptr(act) if bf else None, st),
+                  "llama_embed_swiglu")
+            mo = f32(B * Sq, d)
+            lin(act, mlp.down_proj, B * Sq, mo)
+            if need_bwd:
+                if qf == 0:
+                    q_t = tl(qkv[:, :dq], S)
+                    kv_all = qkv[:, dq:] if S_p == 0 else qkv[:, dq:].contiguous()      # (with no prefix the tail is the whole buffer)
+                    kv_ld = dqkv if S_p == 0 else 2 * dkv
+                else:
+                    q_t, kv_all, kv_ld = q, kv, 2 * dkv
+                saved.append((tl(x, S), tl(rstd1.view(-1, 1), S).view(-1), q_t if q_t.is_contiguous() else q_t.contiguous(), kv_all, kv_ld,
+                              tl(ao32, Sq), tl(lse, Sq), tl(x1, Sq), tl(rstd2.view(-1, 1), Sq).view(-1), tl(gu, Sq)))
+            x, y, Sx = x1, mo, Sq
+        out = f32(B, S_t, d)
+        xf = f32(B * S_t, d)
+        rstd_f = f32(B * S_t) if need_bwd else None
+        check(lib.immtsf_llama_body_rmsnorm(ptr(x), B, Sx, Sx - S_t, d, ptr(tl(y, Sx)), ptr(xf), ptr(model.norm.weight), eps, ptr(out), None,
+                                            ptr(rstd_f), st), "llama_body_rmsnorm")
+        if need_bwd:
+            ctx.saved, ctx.final = saved, (xf, rstd_f)
+            ctx.model, ctx.dims, ctx.precision, ctx.rope = model, (B, S_p, S_t, d, H, H_kv, hd, inner), precision, (cos_t, sin_t)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        st = stream_ptr()
+        model, prec = ctx.model, ctx.precision
+        B, S_p, S_t, d, H, H_kv, hd, inner = ctx.dims
+        S, M = S_p + S_t, B * S_t
+        dq, dkv = H * hd, H_kv * hd
+        dqkv = dq + 2 * dkv
+        bf = prec == 1
+        dev = dout.device
+        scale = 1.0 / float(hd) ** 0.5
+        cos_t, sin_t = ctx.rope
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
+        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev) if bf else None      # noqa: E731
+        adr = lambda t, off=0: C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
+
+        def mm_t(g32, g16, W, W16):       # g (M, N) W: W (N, K) is the nn.Linear weight as stored, read as it is (layout 1)
+            N, K = W.shape
+            o = f32(M, K)
+            check(lib.immtsf_gpt2_gemm(1, prec, None if bf else ptr(g32), ptr(g16) if bf else None, N, ptr(W), ptr(W16) if bf else None, K,
+                                       ptr(o), K, None, M, K, N, st), "gpt2_gemm (backward)")
+            return o
+
+        def lin_t(g32, g16, dense):
+            return mm_t(g32, g16, dense.weight, _gpt2_w16(model, dense.weight) if bf else None)
+
+        def rms_bwd(g, x, rstd, w, resid):
+            o, o16 = f32(M, d), b16(M, d)
+            check(lib.immtsf_llama_body_rmsnorm_backward(ptr(g), ptr(x), ptr(rstd), ptr(w), ptr(resid), M, d, ptr(o), ptr(o16), st),
+                  "llama_body_rmsnorm_backward")
+            return o, o16
+
+        xf, rstd_f = ctx.final
+        dx, dx16 = rms_bwd(dout.contiguous().view(M, d), xf, rstd_f, model.norm.weight, None)
+        for li in reversed(range(len(model.layers))):
+            layer = model.layers[li]
+            att, mlp = layer.self_attn, layer.mlp
+            x_t, rstd1, q_t, kv, kv_ld, ao_t, lse_t, x1_t, rstd2, gu_t = ctx.saved[li]
+            dact = lin_t(dx, dx16, mlp.down_proj)
+            dgu, dgu16 = (None, b16(M, 2 * inner)) if bf else (f32(M, 2 * inner), None)
+            check(lib.immtsf_llama_body_swiglu_backward(ptr(gu_t), ptr(dact), M, inner, ptr(dgu), ptr(dgu16), st),
+                  "llama_body_swiglu_backward")
+            dg = mm_t(dgu, dgu16, *_llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf))
+            dx1, dx1_16 = rms_bwd(dg, x1_t, rstd2, layer.post_attention_layernorm.weight, dx)
+            dao = lin_t(dx1, dx1_16, att.o_proj)
+            dbuf, dbuf16 = f32(M, dqkv), b16(M, dqkv)
+            kp = C.c_void_p(kv.data_ptr())            # (a view into the q | k | v buffer starts at its K columns)
+            check(lib.immtsf_llama_body_attention_backward(ptr(q_t), dq, kp, C.c_void_p(kv.data_ptr() + 4 * dkv), kv_ld, ptr(dao), ptr(ao_t),
+                                                           ptr(lse_t), B, S, H, H_kv, S_p, scale, ptr(dbuf), adr(dbuf, dq),
+                                                           adr(dbuf, dq + dkv), dqkv, st), "llama_body_attention_backward")
+            check(lib.immtsf_llama_body_rope(ptr(dbuf), dqkv, M, S_t, S_p, H + H_kv, S, ptr(cos_t), ptr(sin_t), 1, ptr(dbuf16), st),
+                  "llama_body_rope (backward)")
+            dh = mm_t(dbuf, dbuf16, *_llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf))
+            dx, dx16 = rms_bwd(dh, x_t, rstd1, layer.input_layernorm.weight, dx1)
+        return dx.view(B, S_t, d), None, None, None, None
+
+
+def llama_body(llm_model, prefix_embeds, tail_embeds, training, precision=None):
+    """hidden_tail (B, S_t, d) = the final norm's output for the last S_t rows of the frozen Llama body over [prefix_embeds | tail_embeds].
+    Only tail_embeds takes a gradient (prefix_embeds may require one; it gets none).  Llama's only dropout is attention_dropout:
+    `training` with config.attention_dropout > 0 is not supported (callers take the stock path).  The model's parameters are read in
+    place, but for the cached q | k | v and gate | up concatenations and, in bf16 mode, the cached bf16 weight images (shared with
+    llama_embed_notes).  Outside llama_body_supported this raises: callers check."""
+    tail = _c(tail_embeds.float())
+    prefix = None if prefix_embeds is None or prefix_embeds.shape[1] == 0 else _c(prefix_embeds.detach().float())
+    _need_gpu(tail, prefix)
+    if not llama_body_supported(llm_model, 0 if prefix is None else prefix.shape[1], tail.shape[1]):
+        raise _lib.ImmtsfError("llama_body: this body / sequence length is outside llama_body_supported")
+    if training and float(getattr(llm_model.config, "attention_dropout", 0.0) or 0.0) > 0.0:
+        raise _lib.ImmtsfError("llama_body: attention dropout in training mode is not supported (take the stock path)")
+    need_bwd = torch.is_grad_enabled() and tail.requires_grad
+    return LlamaBodyFn.apply(tail, prefix, llm_model, config.precision_code(precision), need_bwd)
+
+
 # ------------------------------------------------------------------------------------------------ LatentODE backbone
 def _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents):
     return _lib.LatentODEDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(units), int(gru_units), int(latents))

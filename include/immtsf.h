@@ -882,6 +882,49 @@ int immtsf_llama_embed_swiglu(const float* gu, int64_t rows, int32_t inner, floa
 int immtsf_llama_embed_pool(float* x, const float* y, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const float* w, float eps,
                             float* rstd, float* pooled, immtsf_stream_t stream);
 
+/* ---- TimeLLM's frozen Llama body (added within ABI 7: new functions only; csrc/llama_body.hip): what immtsf.ops.llama_body composes with
+ * immtsf_gpt2_gemm (layout 0 forward on the nn.Linear weights as stored, layout 1 backward on the same weights), ..._llama_embed_rope_table
+ * and ..._llama_embed_swiglu into LlamaModel(inputs_embeds=cat([prefix, tail], 1)).last_hidden_state[:, -S_t:] and its gradient with
+ * respect to `tail`.  Rows are dense: (b, s), s < S = S_p + S_t, positions arange(S), plain causal attention, so no prefix row depends
+ * on a tail row and the backward runs over the B S_t tail rows alone.  head_dim 128, G = H / H_kv in {1, 2, 4, 8}.  No dropout, no
+ * atomics, one writer per output element, fixed summation order (the same inputs give the same bits).
+ * ..._supported: d, inner > 0 and multiples of 8, G in {1, 2, 4, 8}, H <= 65535, 1 <= S <= max_positions, S <= 1024.
+ * ..._rmsnorm: for the rows (b, s_from + t), t < S_in - s_from, of xin (B, S_in, d), compact outputs (row r = b (S_in - s_from) + t):
+ *   y given: xout[r, :] = xin row + y[r, :] (xout required; it may be xin when s_from == 0) and the norm is taken of that sum.
+ *   out32 / out16[r, :] = row rsqrt(mean(row^2) + eps) w[:]; rstd[r] = that rsqrt.  Any output may be null, not all.  d % 4 == 0.
+ * ..._rmsnorm_backward: dx[r, :] = resid[r, :] + rstd[r] (w dy[r, :] - x[r, :] rstd[r]^2 mean(w dy[r, :] x[r, :])) over `rows` compact
+ *   rows, into dx32 and / or its bf16 image dx16; resid may be null.  The weights are frozen: no weight gradient.
+ * ..._rope: rotates in place the first `heads` heads of each of `rows` rows of buf (pitch ld) by position pos0 + (r mod rows_per_b),
+ *   clamped into [0, max_len): rotate_half's pairing (i, i + 64), cos_t / sin_t (max_len, 64) from ..._llama_embed_rope_table.
+ *   transposed != 0 rotates by the negated angle (the backward of the rotation).  img16 (rows, ld) bf16, may be null: the image of the
+ *   whole row after the rotation, the columns behind the rotated heads included.
+ * ..._attention_forward: q holds the queries of positions q_from .. S - 1 (row b (S - q_from) + p - q_from, pitch ldq, head h at columns
+ *   128 h), k / v the keys and values of all S positions (row b S + j, pitch ldkv, K/V head at columns 128 kvh); query p of head h sees
+ *   keys 0 .. p of K/V head h / G.  out32 / out16 (B (S - q_from), 128 H): the layout o_proj reads (either may be null); lse
+ *   (B (S - q_from), H), may be null: log-sum-exp of the scaled scores.  precision 0: fp32 on the VALU; 1: both products on bf16 MFMA
+ *   with fp32 accumulation, fp32 online softmax.  Grid (b, K/V head, tile of 32 positions in reverse order), G waves a workgroup.
+ * ..._attention_backward: dout, out (B (S - q_from), 128 H) and lse as the forward wrote them; dq (pitch ldd, head h at columns 128 h) for
+ *   the tail queries; dk, dv (pitch ldd, K/V head at columns 128 kvh) for the keys q_from .. S - 1 only, each summed over the G query
+ *   heads of its K/V head in head order, then in query order.  fp32 on the VALU in either precision mode.  Two launches.
+ * ..._swiglu_backward: gu (rows, 2 inner) = gate | up, dact (rows, inner) -> dgu (rows, 2 inner) = dact up silu'(gate) | dact silu(gate),
+ *   into dgu32 and / or its bf16 image dgu16.  inner % 4 == 0.
+ * Arguments outside these limits give IMMTSF_EINVAL / IMMTSF_EUNSUPPORTED before anything is launched; nothing allocates or synchronises. */
+int immtsf_llama_body_supported(int32_t d, int32_t H, int32_t H_kv, int32_t inner, int32_t S, int32_t max_positions);
+int immtsf_llama_body_rmsnorm(const float* xin, int32_t B, int32_t S_in, int32_t s_from, int32_t d, const float* y, float* xout, const float* w,
+                              float eps, float* out32, void* out16, float* rstd, immtsf_stream_t stream);
+int immtsf_llama_body_rmsnorm_backward(const float* dy, const float* x, const float* rstd, const float* w, const float* resid, int64_t rows,
+                                       int32_t d, float* dx32, void* dx16, immtsf_stream_t stream);
+int immtsf_llama_body_rope(float* buf, int32_t ld, int64_t rows, int32_t rows_per_b, int32_t pos0, int32_t heads, int32_t max_len,
+                           const float* cos_t, const float* sin_t, int32_t transposed, void* img16, immtsf_stream_t stream);
+int immtsf_llama_body_attention_forward(const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, int32_t B, int32_t S,
+                                        int32_t H, int32_t H_kv, int32_t q_from, float scale, int32_t precision, float* out32, void* out16,
+                                        float* lse, immtsf_stream_t stream);
+int immtsf_llama_body_attention_backward(const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, const float* dout,
+                                         const float* out, const float* lse, int32_t B, int32_t S, int32_t H, int32_t H_kv, int32_t q_from,
+                                         float scale, float* dq, float* dk, float* dv, int32_t ldd, immtsf_stream_t stream);
+int immtsf_llama_body_swiglu_backward(const float* gu, const float* dact, int64_t rows, int32_t inner, float* dgu32, void* dgu16,
+                                      immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

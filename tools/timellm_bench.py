@@ -8,7 +8,11 @@ the host, so the step cannot be captured.  In ONE process, after warming both pa
 each, host clock around a pass with a synchronise at its end.  Prints one JSON line per mode: milliseconds per step, best pass and all
 passes (their spread is the noise).
 
-usage: python tools/timellm_bench.py [--iters 5] [--passes 5] [--batch 64] [--out FILE]
+--llm LLAMA: the same for the frozen Llama body (immtsf.ops.llama_body: csrc/llama_body.hip) on an offline stand-in of huggyllama/llama-7b's
+widths (hidden 4096, 32 heads over 32 K/V heads, intermediate 11008) with 2 layers, at the same B, S_p and S_t; the body alone, with
+the launches per direction of the fused plan in the line.
+
+usage: python tools/timellm_bench.py [--llm GPT2|LLAMA] [--iters 5] [--passes 5] [--batch 64] [--out FILE]
 """
 import argparse
 import json
@@ -31,7 +35,10 @@ def main():
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--llm", choices=("GPT2", "LLAMA"), default="GPT2")
     args = ap.parse_args()
+    llama = args.llm == "LLAMA"
+    layers = 2 if llama else LAYERS
     import torch
     from immtsf import config, ops
     from models.TimeLLM import TimeLLM
@@ -40,8 +47,9 @@ def main():
     torch.manual_seed(0)
     m = TimeLLM(types.SimpleNamespace(
         input_len=L, pred_len=L, use_norm=True, d_ff=32, ts_vocab_size=1000, input_token_len=16, stride=8, domain_des="synthetic", top_k=5,
-        C=C, llm_model_timellm="GPT2", llm_layers_timellm=LAYERS, dropout=0.1, d_model=16, n_heads=8, batch_size=B, device=str(dev),
-        immtsf_offline_llm=True)).to(dev).train()
+        C=C, llm_model_timellm=args.llm, llm_layers_timellm=layers, dropout=0.1, d_model=16, n_heads=8, batch_size=B, device=str(dev),
+        immtsf_offline_llm=dict(hidden_size=4096, num_attention_heads=32, num_key_value_heads=32, intermediate_size=11008) if llama
+        else True)).to(dev).train()
     m.word_embeddings = m.llm_model.get_input_embeddings().weight
     g = torch.Generator().manual_seed(1)
     mask = (torch.rand(B, L, C, generator=g) < 0.7).float().to(dev)
@@ -62,7 +70,7 @@ def main():
     def body(fused):
         tail.grad = None
         if fused:
-            out = ops.gpt2_body(m.llm_model, prefix, tail, True)
+            out = (ops.llama_body if llama else ops.gpt2_body)(m.llm_model, prefix, tail, True)
         else:
             out = m.llm_model(inputs_embeds=torch.cat([prefix, tail], 1)).last_hidden_state[:, -S_t:]
         (out * up_b).sum().backward()
@@ -83,9 +91,12 @@ def main():
     lines = []
     for prec in ("fp32", "bf16"):
         config.precision = prec
-        line = {"tool": "timellm_bench", "precision": prec, "B": B, "layers": LAYERS, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
+        line = {"tool": "timellm_bench", "precision": prec, "B": B, "layers": layers, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
                 "passes": args.passes}
-        for what, fn in (("body", body), ("forecasting", whole)):
+        if llama:       # the fused plan: 9 launches a layer + 3 for the last layer's tail queries + table and final norm;
+            #             10 a layer backward (the attention backward is two) + the final norm's
+            line.update(llm="LLAMA", launches_forward=9 * layers + 5, launches_backward=10 * layers + 1)
+        for what, fn in ((("body", body),) if llama else (("body", body), ("forecasting", whole))):
             for fused in (True, False):
                 for _ in range(2):
                     fn(fused)
