@@ -142,6 +142,10 @@ cru_fused = os.environ.get("IMMTSF_CRU_FUSED", "1") != "0"
 # the whole backward over the reprogrammed patch rows only, bf16 weight images in bf16 mode) wherever gpt2_body_supported allows;
 # IMMTSF_TIMELLM_FUSED=0: transformers' GPT2Model on stock PyTorch in fp32 -- the cross-check.  Follows config.precision
 timellm_fused = os.environ.get("IMMTSF_TIMELLM_FUSED", "1") != "0"
+# A BERT body (immtsf.ops.bert_body, csrc/bert_body.hip) takes the fused path in bf16 mode only: in fp32 mode it measured slower than the
+# stock call (178 vs 72 ms), so fp32 mode keeps the stock call unless IMMTSF_TIMELLM_BERT_FP32=1 asks for the operator (the
+# cross-check of the two paths at fp32 accuracy; less saved memory).  Under timellm_fused either way
+timellm_bert_fp32 = os.environ.get("IMMTSF_TIMELLM_BERT_FP32", "0") == "1"
 # Raw-text mode (fusions.load_llm.embed_notes, immtsf.text.embed_corpus): a frozen GPT2Model over the notes' REAL tokens only, packed
 # back to back (immtsf.ops.gpt2_embed_notes: csrc/note_embed.hip + the GEMM family + the row kernels of csrc/gpt2.hip), wherever
 # gpt2_embed_notes_supported allows and the tokenizer pads on the right; IMMTSF_NOTE_EMBED_FUSED=0: the reference's formulation (every

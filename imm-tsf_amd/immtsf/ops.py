@@ -3855,6 +3855,250 @@ def llama_body(llm_model, prefix_embeds, tail_embeds, training, precision=None):
     return LlamaBodyFn.apply(tail, prefix, llm_model, config.precision_code(precision), need_bwd)
 
 
+# ------------------------------------------------------------------------------------------------ TimeLLM's frozen BERT body
+BERT_SITE_EMBD = 131072          # include/immtsf.h IMMTSF_SITE_BERT_*
+
+
+def bert_sites(layer):
+    """(attention probabilities, attention-output dropout, feed-forward-output dropout) sites of layer `layer`; the embedding dropout is
+    BERT_SITE_EMBD"""
+    return 131073 + 3 * layer, 131074 + 3 * layer, 131075 + 3 * layer
+
+
+def bert_body_supported(llm_model, S_p, S_t):
+    """the limits of bert_body: bert_embed_notes_supported's conditions on the model (the BertModel class itself, head_dim 64, hidden_act
+    "gelu", absolute positions, neither a decoder nor cross attention, fp32 parameters, hidden_size and intermediate_size multiples of 8,
+    at least one layer), S_p >= 0, S_t >= 1 and S = S_p + S_t <= max_position_embeddings, <= 1024"""
+    if S_p < 0 or S_t < 1 or not bert_embed_notes_supported(llm_model, 1):
+        return False
+    cfg = llm_model.config
+    return bool(_lib.load().immtsf_bert_body_supported(int(cfg.hidden_size), int(cfg.num_attention_heads), int(S_p + S_t),
+                                                       int(cfg.max_position_embeddings)))
+
+
+class BertBodyFn(torch.autograd.Function):
+    """transformers' BertModel(inputs_embeds=cat([prefix, tail], 1)).last_hidden_state[:, -S_t:] on csrc/bert_body.hip, the erf GELU of
+    csrc/bert_embed.hip and the GEMM family.  The body is frozen and only `tail` takes a gradient.  BERT is bidirectional and
+    there is no attention mask: every row of every layer depends on every tail row, so a middle layer runs forward and backward over all
+    B S rows.  Two exact reductions.  Last layer, forward: only the tail rows leave the body, so K and V are computed for all rows but the
+    queries, the output dense, both add + LayerNorms and the feed-forward for the S_t tail rows only.  First layer, backward: the embedding
+    LayerNorm is row-wise and the prefix takes no gradient, so layer 0's dq and the dqkv -> dx0 product run over the tail rows only (its
+    dk / dv of the tail keys still sum over all of the layer's queries).  With one layer both hold in the same layer.  Saved per layer,
+    for the layer's rows: the q | k | v product (all rows), the attention output, the log-sum-exp, both pre-norm sums with their
+    statistics and the feed-forward pre-activation; for the embedding, the tail rows' pre-norm sum and statistics."""
+
+    @staticmethod
+    def forward(ctx, tail, prefix, model, p_drops, precision, seed, need_bwd):
+        lib = _lib.load()
+        st = stream_ptr()
+        cfg = model.config
+        B, S_t, d = tail.shape
+        S_p = 0 if prefix is None else prefix.shape[1]
+        S, H, inner, L = S_p + S_t, int(cfg.num_attention_heads), int(cfg.intermediate_size), len(model.encoder.layer)
+        M = B * S_t
+        dev = tail.device
+        bf = precision == 1
+        p_h, p_a = p_drops
+        eps = float(cfg.layer_norm_eps)
+        scale = 1.0 / float(d // H) ** 0.5
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
+        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev) if bf else None      # noqa: E731
+        adr = lambda t, off=0: None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
+
+        def mm(a32, a16, W, W16, bias, rows, out, ldc, w_row=0, n_out=None, c_off=0):
+            """out[:, c_off:c_off + n_out] = a (rows, K) W[w_row:w_row + n_out]^T + bias[w_row:..]: W (N, K) is the nn.Linear weight as
+            stored (layout 0)"""
+            K = W.shape[1]
+            n_out = W.shape[0] if n_out is None else n_out
+            check(lib.immtsf_gpt2_gemm(0, precision, None if bf else ptr(a32), ptr(a16) if bf else None, K, adr(W, w_row * K),
+                                       adr(W16, w_row * K) if bf else None, K, adr(out, c_off), ldc, adr(bias, w_row), rows, n_out, K, st),
+                  "gpt2_gemm")
+
+        def lin(a32, a16, dense, rows, out):
+            mm(a32, a16, dense.weight, _gpt2_w16(model, dense.weight) if bf else None, dense.bias, rows, out, dense.weight.shape[0])
+
+        def add_ln(xin, S_in, s_from, y, q_from, norm, site, out32, keep16):
+            """LayerNorm(xin rows + dropout(y)) -> (out32, bf16 image or None, pre-norm sum, mean, rstd)"""
+            n = B * (S_in - s_from)
+            o16 = b16(n, d) if keep16 else None
+            sm, mean, rstd = (f32(n, d), f32(n), f32(n)) if need_bwd else (None, None, None)
+            check(lib.immtsf_bert_body_add_layernorm(ptr(xin), B, S_in, s_from, ptr(y), S, q_from, d, ptr(norm.weight), ptr(norm.bias), eps, p_h,
+                                                     seed, site, ptr(out32), ptr(o16), ptr(sm), ptr(mean), ptr(rstd), st),
+                  "bert_body_add_layernorm")
+            return o16, sm, mean, rstd
+
+        def tl(t):        # the tail rows of a (B S, ...) tensor, compact
+            if t is None or S_p == 0:
+                return t
+            return t.view(B, S, -1)[:, S_p:].contiguous().view(M, -1)
+
+        emb = model.embeddings
+        x, x16 = f32(B * S, d), b16(B * S, d)
+        sum0, mean0, rstd0 = (f32(M, d), f32(M), f32(M)) if need_bwd else (None, None, None)
+        check(lib.immtsf_bert_body_embed(ptr(prefix), ptr(tail), ptr(emb.position_embeddings.weight), ptr(emb.token_type_embeddings.weight), B,
+                                         S_p, S_t, d, ptr(emb.LayerNorm.weight), ptr(emb.LayerNorm.bias), eps, p_h, seed, BERT_SITE_EMBD, ptr(x),
+                                         ptr(x16), ptr(sum0), ptr(mean0), ptr(rstd0), st), "bert_body_embed")
+        out = f32(B, S_t, d)
+        saved = []
+        for li, layer in enumerate(model.encoder.layer):
+            last = li == L - 1
+            qf = S_p if last else 0
+            Sq = S - qf
+            Mq = B * Sq
+            s_attn, s_h1, s_h2 = bert_sites(li)
+            att = layer.attention
+            W, bias, W16 = _bert_qkv(model, att.self, bf)
+            qkv = f32(B * S, 3 * d)
+            if qf == 0:
+                mm(x, x16, W, W16, bias, B * S, qkv, 3 * d)
+                q, ldq = qkv, 3 * d
+            else:           # the last layer: K and V of all rows, queries of the tail rows
+                mm(x, x16, W, W16, bias, B * S, qkv, 3 * d, w_row=d, n_out=2 * d, c_off=d)
+                q, ldq = f32(Mq, d), d
+                mm(None if bf else tl(x), tl(x16), W, W16, bias, Mq, q, d, n_out=d)
+            ao32 = f32(Mq, d) if (need_bwd or not bf) else None
+            ao16 = b16(Mq, d)
+            lse = f32(B, H, Sq) if need_bwd else None
+            check(lib.immtsf_bert_body_attention_forward(ptr(q), ldq, adr(qkv, d), adr(qkv, 2 * d), 3 * d, B, S, H, qf, scale, precision, p_a,
+                                                         seed, s_attn, ptr(ao32), ptr(ao16), ptr(lse), st), "bert_body_attention_forward")
+            pr = f32(Mq, d)
+            lin(ao32, ao16, att.output.dense, Mq, pr)
+            x1 = f32(Mq, d)
+            x1_16, sum1, mean1, rstd1 = add_ln(x, S, qf, pr, qf, att.output.LayerNorm, s_h1, x1, bf)
+            pre = f32(Mq, inner)
+            lin(x1, x1_16, layer.intermediate.dense, Mq, pre)
+            a32, a16 = (None, b16(Mq, inner)) if bf else (f32(Mq, inner), None)
+            check(lib.immtsf_bert_embed_gelu(ptr(pre), pre.numel(), ptr(a32), ptr(a16), st), "bert_embed_gelu")
+            mo = f32(Mq, d)
+            lin(a32, a16, layer.output.dense, Mq, mo)
+            x2 = out.view(M, d) if last else f32(Mq, d)
+            x2_16, sum2, mean2, rstd2 = add_ln(x1, Sq, 0, mo, qf, layer.output.LayerNorm, s_h2, x2, bf and not last)
+            if need_bwd:
+                saved.append((q, ldq, qkv, ao32, lse, sum1, mean1, rstd1, pre, sum2, mean2, rstd2))
+            x, x16 = x2, x2_16
+        if need_bwd:
+            ctx.saved, ctx.embed = saved, (sum0, mean0, rstd0)
+            ctx.model, ctx.dims, ctx.drops, ctx.seed, ctx.precision = model, (B, S_p, S_t, d, H, inner), p_drops, seed, precision
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        st = stream_ptr()
+        model, prec, seed = ctx.model, ctx.precision, ctx.seed
+        B, S_p, S_t, d, H, inner = ctx.dims
+        S, M, L = S_p + S_t, B * S_t, len(model.encoder.layer)
+        p_h, p_a = ctx.drops
+        bf = prec == 1
+        dev = dout.device
+        scale = 1.0 / float(d // H) ** 0.5
+        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
+        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev) if bf else None      # noqa: E731
+        adr = lambda t, off=0: C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
+
+        def mm_t(g32, g16, W, W16, rows):       # g (rows, N) W: W (N, K) is the nn.Linear weight as stored, read as it is (layout 1)
+            N, K = W.shape
+            o = f32(rows, K)
+            check(lib.immtsf_gpt2_gemm(1, prec, None if bf else ptr(g32), ptr(g16) if bf else None, N, ptr(W), ptr(W16) if bf else None, K,
+                                       ptr(o), K, None, rows, K, N, st), "gpt2_gemm (backward)")
+            return o
+
+        def lin_t(g32, g16, dense, rows):
+            return mm_t(g32, g16, dense.weight, _gpt2_w16(model, dense.weight) if bf else None, rows)
+
+        def ln_bwd(dy, Sn, sm, mean, rstd, norm, q_from, site):
+            """dy = (dy_a, Sa, sa_from, dy_b, tb_from) -> (d_sum fp32, the branch's gradient as the next product reads it: fp32, bf16)"""
+            dy_a, Sa, sa_from, dy_b, tb_from = dy
+            n = B * Sn
+            dsum = f32(n, d)
+            br32 = f32(n, d) if (not bf and p_h > 0.0) else None
+            br16 = b16(n, d)
+            check(lib.immtsf_bert_body_layernorm_backward(ptr(dy_a), B, Sa, sa_from, Sn, ptr(dy_b), tb_from, ptr(sm), ptr(mean), ptr(rstd),
+                                                          ptr(norm.weight), d, S, q_from, p_h, seed, site, 0, ptr(dsum), ptr(br32), ptr(br16),
+                                                          st), "bert_body_layernorm_backward")
+            return dsum, (None if bf else (dsum if br32 is None else br32)), br16
+
+        dy = (dout.contiguous().view(M, d), S_t, 0, None, 0)
+        for li in reversed(range(L)):
+            layer = model.encoder.layer[li]
+            att = layer.attention
+            first, last = li == 0, li == L - 1
+            qf = S_p if last else 0
+            Sq = S - qf
+            Mq = B * Sq
+            q, ldq, qkv, ao32, lse, sum1, mean1, rstd1, pre, sum2, mean2, rstd2 = ctx.saved[li]
+            s_attn, s_h1, s_h2 = bert_sites(li)
+            dsum2, dmo32, dmo16 = ln_bwd(dy, Sq, sum2, mean2, rstd2, layer.output.LayerNorm, qf, s_h2)
+            dact = lin_t(dmo32, dmo16, layer.output.dense, Mq)
+            dpre32, dpre16 = (None, b16(Mq, inner)) if bf else (f32(Mq, inner), None)
+            check(lib.immtsf_bert_body_gelu_backward(ptr(pre), ptr(dact), dact.numel(), ptr(dpre32), ptr(dpre16), st), "bert_body_gelu_backward")
+            g1 = lin_t(dpre32, dpre16, layer.intermediate.dense, Mq)
+            dsum1, dpr32, dpr16 = ln_bwd((dsum2, Sq, 0, g1, 0), Sq, sum1, mean1, rstd1, att.output.LayerNorm, qf, s_h1)
+            dao = lin_t(dpr32, dpr16, att.output.dense, Mq)
+            # dq for the queries whose rows take a gradient through q, dk / dv for the keys whose rows do, each summed over all Sq queries
+            dq_from = S_p if (first or last) else 0
+            k_from = S_p if first else 0
+            if first:           # the dqkv -> dx0 product over the tail rows only
+                rows_b, dq_off = S_t, 0
+            else:
+                rows_b, dq_off = S, dq_from * 3 * d
+            dqkv = f32(B * rows_b, 3 * d)
+            if dq_off:          # the last layer of several: the prefix rows have keys and values but no query
+                dqkv.view(B, S, 3 * d)[:, :S_p, :d].zero_()
+            dsum = f32(Mq, H) if bf else None
+            check(lib.immtsf_bert_body_attention_backward(ptr(q), ldq, adr(qkv, d), adr(qkv, 2 * d), 3 * d, ptr(dao), ptr(ao32), ptr(lse), B, S, H,
+                                                          qf, dq_from, k_from, scale, prec, p_a, seed, s_attn, adr(dqkv, dq_off), rows_b,
+                                                          adr(dqkv, d), adr(dqkv, 2 * d), rows_b, 3 * d, ptr(dsum), st),
+                  "bert_body_attention_backward")
+            dqkv16 = b16(B * rows_b, 3 * d)
+            if bf:
+                check(lib.immtsf_f32_to_bf16(ptr(dqkv), ptr(dqkv16), dqkv.numel(), st), "f32_to_bf16")
+            W, _, W16 = _bert_qkv(model, att.self, bf)
+            gq = mm_t(dqkv, dqkv16, W, W16, B * rows_b)
+            if first:
+                dy = (dsum1, Sq, S_p - qf, gq, 0)
+            elif last:
+                dy = (gq, S, 0, dsum1, S_p)
+            else:
+                dy = (dsum1, S, 0, gq, 0)
+        sum0, mean0, rstd0 = ctx.embed
+        dy_a, Sa, sa_from, dy_b, tb_from = dy
+        dtail = f32(M, d)
+        norm = model.embeddings.LayerNorm
+        check(lib.immtsf_bert_body_layernorm_backward(ptr(dy_a), B, Sa, sa_from, S_t, ptr(dy_b), tb_from, ptr(sum0), ptr(mean0), ptr(rstd0),
+                                                      ptr(norm.weight), d, S, S_p, p_h, seed, BERT_SITE_EMBD, 1, ptr(dtail), None, None, st),
+              "bert_body_layernorm_backward (embedding)")
+        return dtail.view(B, S_t, d), None, None, None, None, None, None
+
+
+def bert_body(llm_model, prefix_embeds, tail_embeds, training, precision=None, seed=None):
+    """hidden_tail (B, S_t, d) fp32 = the last S_t rows of the frozen BertModel's last hidden state over [prefix_embeds | tail_embeds]
+    (token type 0, absolute positions, no attention mask: the padded prompt tokens are attended, as the reference calls the model).  Only
+    tail_embeds takes a gradient (prefix_embeds may require one; it gets none); under no_grad, or with a tail that needs no gradient,
+    nothing is saved.  Two exact reductions: the last layer computes K and V for all rows but queries, the output dense, both add +
+    LayerNorms and the feed-forward for the tail rows only; the backward of the first layer computes dq and the dqkv -> dx0 product for
+    the tail rows only (the embedding LayerNorm is row-wise and the prefix takes no gradient).  Every other layer runs over all B S rows
+    in both directions: attention is bidirectional.  training: the body's four dropouts (embedding, attention probabilities and the two
+    hidden dropouts of each layer; hidden_dropout_prob / attention_probs_dropout_prob of its config) are drawn from immtsf's generator --
+    ops.dropout_keep_mask(seed, site, ...) reproduces them (BERT_SITE_EMBD, bert_sites(layer)); seed: the Philox key, config.next_seed()
+    by default.  The model's parameters are read in place, but for the cached query | key | value concatenation and, in bf16 mode, the
+    cached bf16 weight images (shared with bert_embed_notes).  Outside bert_body_supported this raises: callers check."""
+    tail = _c(tail_embeds.float())
+    prefix = None if prefix_embeds is None or prefix_embeds.shape[1] == 0 else _c(prefix_embeds.detach().float())
+    _need_gpu(tail, prefix)
+    if not bert_body_supported(llm_model, 0 if prefix is None else prefix.shape[1], tail.shape[1]):
+        raise _lib.ImmtsfError("bert_body: this body / sequence length is outside bert_body_supported")
+    if tail.dim() != 3 or tail.shape[2] != llm_model.config.hidden_size or \
+            (prefix is not None and (prefix.shape[0] != tail.shape[0] or prefix.shape[2] != tail.shape[2])):
+        raise _lib.ImmtsfError("bert_body: prefix (B, S_p, d) and tail (B, S_t, d) with d the body's hidden_size")
+    cfg = llm_model.config
+    drops = (float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)) if training else (0.0, 0.0)
+    if seed is None:
+        seed = config.next_seed() if any(p > 0.0 for p in drops) else 0
+    need_bwd = torch.is_grad_enabled() and tail.requires_grad
+    return BertBodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), int(seed) & 0xFFFFFFFFFFFFFFFF, need_bwd)
+
+
 # ------------------------------------------------------------------------------------------------ LatentODE backbone
 def _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents):
     return _lib.LatentODEDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(units), int(gru_units), int(latents))

@@ -2,8 +2,8 @@
 
 Same constructor / `forecasting` signature and state_dict keys.  The frozen LLM and its tokenizer come from the HF hub
 in the reference (:128-159); with no network they cannot be instantiated, so `configs.immtsf_offline_llm = True`
-builds a RANDOM-INIT GPT-2 (or, for "LLAMA", LlamaModel: a dict gives LlamaConfig fields, and d_llm follows its hidden_size in
-this mode only) of the requested depth and a deterministic byte-level tokenizer stand-in.  The wrapper's
+builds a RANDOM-INIT GPT-2 (or, for "LLAMA" / "BERT", LlamaModel / BertModel: a dict gives LlamaConfig / BertConfig fields, and d_llm
+follows its hidden_size in this mode only) of the requested depth and a deterministic byte-level tokenizer stand-in.  The wrapper's
 composition (prompt -> tokens -> two patch embeddings -> reprogramming -> LLM -> hidden[:, -total:, :d_ff] -> head) is pinned
 against the reference run the same way (its loader patched to the same stand-ins, tests/golden/make_golden.py gen_timellm ->
 tests/golden/model_timellm.npz, test_gpu_fusion.py::test_timellm_forecasting_vs_reference_golden); parity with PRETRAINED
@@ -11,8 +11,11 @@ weights stays unpinned.  The sub-layers on the
 hot-path scope -- PatchEmbedding on values and on timestamps, ReprogrammingLayer projections, FlattenHead -- use the
 HIP GEMM.  A GPT-2 body inside immtsf.ops.gpt2_body_supported runs on immtsf.ops.gpt2_body (csrc/gpt2.hip, DESIGN 4l: the frozen body
 with its backward over the patch rows only; config.timellm_fused / IMMTSF_TIMELLM_FUSED=0 turns it off, `fused_body_calls` counts),
-a Llama body inside immtsf.ops.llama_body_supported on immtsf.ops.llama_body (csrc/llama_body.hip, DESIGN 4r) under the same knob;
-`self.llm_model` stays the transformers model, and every other body runs the stock call."""
+a Llama body inside immtsf.ops.llama_body_supported on immtsf.ops.llama_body (csrc/llama_body.hip) and a BERT body inside
+immtsf.ops.bert_body_supported on immtsf.ops.bert_body (csrc/bert_body.hip, DESIGN 4s: bidirectional, so its backward runs through the
+prompt rows too; its dropouts are drawn in the kernels; in bf16 mode only, where it measured 2.8x the stock call -- in fp32 mode the
+stock call is faster and stays, unless config.timellm_bert_fp32 / IMMTSF_TIMELLM_BERT_FP32=1) under the same knob; `self.llm_model` stays the transformers model, and every
+other body (a sequence past max_position_embeddings included) runs the stock call."""
 from math import sqrt
 
 import torch
@@ -20,7 +23,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from immtsf import config
-from immtsf.ops import gpt2_body, gpt2_body_supported, linear, llama_body, llama_body_supported, shared_kv_attention
+from immtsf.ops import (bert_body, bert_body_supported, gpt2_body, gpt2_body_supported, linear, llama_body, llama_body_supported,
+                        shared_kv_attention)
 from layers.Embed import PatchEmbedding
 from models._common import masked_instance_norm
 
@@ -103,7 +107,7 @@ class TimeLLM(nn.Module):
         self.head_nf = self.d_ff * self.patch_nums
         self._get_model_and_tokenizer(configs.llm_model_timellm, configs.llm_layers_timellm,
                                       getattr(configs, "immtsf_offline_llm", False))
-        if configs.llm_model_timellm == "LLAMA" and getattr(configs, "immtsf_offline_llm", False):
+        if configs.llm_model_timellm in ("LLAMA", "BERT") and getattr(configs, "immtsf_offline_llm", False):
             self.d_llm = int(self.llm_model.config.hidden_size)      # offline only: a stand-in need not be 4096 wide
         self._get_llm_pad_token()
         for p in self.llm_model.parameters():
@@ -115,7 +119,7 @@ class TimeLLM(nn.Module):
         self.reprogramming_layer = ReprogrammingLayer(configs.d_model, configs.n_heads, d_llm=self.d_llm)
         self.output_projection = FlattenHead(self.head_nf, self.pred_len, head_dropout=configs.dropout)
         self.zeros_pad = torch.zeros(configs.batch_size, max(self.input_len, self.pred_len), self.C, device=configs.device)
-        self.fused_body_calls = 0          # forecasting() calls whose frozen body ran on immtsf.ops.gpt2_body / llama_body
+        self.fused_body_calls = 0          # forecasting() calls whose frozen body ran on immtsf.ops.gpt2_body / llama_body / bert_body
 
     def _get_model_and_tokenizer(self, model_name, layers, offline):
         from transformers import BertConfig, BertModel, BertTokenizer, GPT2Config, GPT2Model, GPT2Tokenizer
@@ -127,15 +131,19 @@ class TimeLLM(nn.Module):
             raise ValueError("Unsupported LLM")
         repo, Cfg, Model, Tok = table[model_name]
         if offline:
-            if model_name not in ("GPT2", "LLAMA"):
-                raise ValueError("immtsf_offline_llm supports GPT2 and LLAMA only")
-            # (a dict: extra GPT2Config / LlamaConfig fields -- the parity fixture uses a 320-entry vocabulary, tests/golden/make_golden.py)
+            # (a dict: extra GPT2Config / LlamaConfig / BertConfig fields -- the parity fixture uses a 320-entry vocabulary,
+            # tests/golden/make_golden.py)
             extra = offline if isinstance(offline, dict) else {}
             if model_name == "LLAMA":
                 cfg = LlamaConfig(num_hidden_layers=layers, **extra)
                 if cfg.vocab_size < 256:
                     raise ValueError("immtsf_offline_llm: the byte tokenizer stand-in needs a vocabulary of at least 256")
                 self.llm_model = LlamaModel(cfg)
+            elif model_name == "BERT":
+                cfg = BertConfig(num_hidden_layers=layers, **extra)
+                if cfg.vocab_size < 256:
+                    raise ValueError("immtsf_offline_llm: the byte tokenizer stand-in needs a vocabulary of at least 256")
+                self.llm_model = BertModel(cfg)
             else:
                 self.llm_model = GPT2Model(GPT2Config(n_layer=layers, **extra))
             self.tokenizer = _ByteTokenizer()
@@ -202,6 +210,12 @@ class TimeLLM(nn.Module):
         elif (config.timellm_fused and rep.is_cuda and llama_body_supported(self.llm_model, prompt_embeds.size(1), total) and
               not (self.llm_model.training and self.llm_model.config.attention_dropout > 0)):
             hidden_tail = llama_body(self.llm_model, prompt_embeds, rep, self.llm_model.training)
+            self.fused_body_calls += 1
+        elif (config.timellm_fused and rep.is_cuda and (config.precision_code(None) == 1 or config.timellm_bert_fp32) and
+              bert_body_supported(self.llm_model, prompt_embeds.size(1), total)):
+            # bidirectional: the gradient of the patch rows flows through the prompt rows; the four dropouts are drawn in the kernels.
+            # bf16 mode only by default: in fp32 mode the stock call measured faster
+            hidden_tail = bert_body(self.llm_model, prompt_embeds, rep, self.llm_model.training)
             self.fused_body_calls += 1
         else:
             hidden_tail = self.llm_model(inputs_embeds=torch.cat([prompt_embeds, rep], dim=1)).last_hidden_state[:, -total:]

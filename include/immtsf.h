@@ -925,6 +925,63 @@ int immtsf_llama_body_attention_backward(const float* q, int32_t ldq, const floa
 int immtsf_llama_body_swiglu_backward(const float* gu, const float* dact, int64_t rows, int32_t inner, float* dgu32, void* dgu16,
                                       immtsf_stream_t stream);
 
+/* ---- TimeLLM's frozen BERT body (added within ABI 7: new functions only; csrc/bert_body.hip): what immtsf.ops.bert_body composes with
+ * immtsf_gpt2_gemm (layout 0 forward on the nn.Linear weights as stored, layout 1 backward on the same weights) and ..._bert_embed_gelu
+ * into BertModel(inputs_embeds=cat([prefix, tail], 1)).last_hidden_state[:, -S_t:] and its gradient with respect to `tail`.  Rows are
+ * dense: (b, s), s < S = S_p + S_t, token type 0, absolute positions arange(S), NO attention mask: attention is bidirectional, every row
+ * depends on every tail row, and the backward of a middle layer covers all B S rows.  head_dim 64, d = 64 H, post-LN.  No atomics, one
+ * writer per output element, fixed summation order (the same inputs give the same bits).
+ * ..._supported: d == 64 H, H <= 65535, 1 <= S <= max_positions, S <= 1024.
+ * ..._embed: out32 (B, S, d) = dropout(LayerNorm([prefix | tail] + pos[0:S] + type0)) without the concatenated copy (prefix may be NULL
+ *   when S_p == 0), out16 its bf16 image (may be NULL).  For the tail rows (row b S_t + t), when given: sum_tail (B S_t, d) the pre-norm
+ *   sum, mean_tail / rstd_tail (B S_t) the statistics.  Dropout index (b S + s) d + e.
+ * ..._add_layernorm: for the rows (b, s_from + t), t < Sn = S_in - s_from, of xin (B, S_in, d) and the compact branch y (B Sn, d):
+ *   LayerNorm(xin row + dropout(y row)) into the compact out32 and / or out16 (bf16 image); sum (B Sn, d) the pre-norm sum, mean / rstd
+ *   (B Sn) the statistics, each when given.  out32 or sum must be given (the row is staged there).  The dropout mask is that of row
+ *   (b, q_from + t) of a (B, S, d) tensor, index (b S + s) d + e.
+ * ..._layernorm_backward: the data gradient of both, over the rows (b, t), t < Sn: dy = dy_a[b, sa_from + t] (dy_a (B, Sa, d)) + dy_b[b, t -
+ *   tb_from] for t >= tb_from (dy_b (B, Sn - tb_from, d), may be NULL); sum / mean / rstd compact (B Sn ..) as the forward wrote them.
+ *   drop_first 0: d_sum = LayerNorm'(dy) -> dx32; undrop(d_sum) -> dbr32 / dbr16 (the branch's gradient, fp32 / bf16 image).  drop_first
+ *   1 (the embedding, whose dropout is behind the norm): d_sum = LayerNorm'(undrop(dy)) -> dx32.  Outputs compact; any may be NULL, not
+ *   all.  No parameter gradients: the body is frozen.
+ * ..._gelu_backward: dpre = dact gelu'(pre), gelu in the erf form (the forward is ..._bert_embed_gelu), into dpre32 and / or dpre16.
+ * ..._attention_forward: non-causal softmax(scale q k^T) v.  k, v: rows b S + j with pitch ldkv, head h at columns 64 h (the fused
+ *   q | k | v product as it lies); q: the queries of positions q_from .. S-1, row b (S - q_from) + t with pitch ldq; out32 / out16
+ *   (B (S - q_from), 64 H) in the layout the output dense reads; lse (B, H, S - q_from) = log-sum-exp of the scaled scores (may be NULL).
+ *   Dropout on the probabilities, index ((b H + h) S + i) 1024 + j for query position i and key j.  precision 0: fp32 on the VALU; 1:
+ *   both products on bf16 MFMA 16x16x32 with fp32 online softmax and accumulators.  A key at or past S in a partial tile adds nothing.
+ * ..._attention_backward: q, dout, out, lse in the forward's layouts for the queries q_from .. S-1.  dq for the queries dq_from .. S-1
+ *   (q_from <= dq_from) against all keys: row b dq_rows + (i - dq_from), pitch ldd.  dk / dv for the keys k_from .. S-1, each summed over
+ *   ALL the queries q_from .. S-1 in query order: row b dkv_rows + (j - k_from), pitch ldd.  Probabilities are recomputed from lse and the
+ *   mask is redrawn.  precision 0: fp32 on the VALU, two launches; 1: the four products on bf16 MFMA with fp32 softmax arithmetic and
+ *   accumulators, three launches (the first writes dsum (B (S - q_from), H) = dout . out per row and head; dsum may be NULL at
+ *   precision 0).
+ * Arguments outside these limits give IMMTSF_EINVAL / IMMTSF_EUNSUPPORTED before anything is launched; nothing allocates or synchronises. */
+#define IMMTSF_SITE_BERT_EMBD 131072  /* index (b*S+s)*d+e */
+#define IMMTSF_SITE_BERT_ATTN 131073  /* + 3*layer; index ((b*H+h)*S+i)*1024+j */
+#define IMMTSF_SITE_BERT_HID1 131074  /* + 3*layer; index (b*S+s)*d+e: the attention output's dropout */
+#define IMMTSF_SITE_BERT_HID2 131075  /* + 3*layer; index (b*S+s)*d+e: the feed-forward output's dropout */
+int immtsf_bert_body_supported(int32_t d, int32_t H, int32_t S, int32_t max_positions);
+int immtsf_bert_body_embed(const float* prefix, const float* tail, const float* pos, const float* type0, int32_t B, int32_t S_p, int32_t S_t,
+                           int32_t d, const float* gamma, const float* beta, float eps, float p_drop, uint64_t seed, uint64_t site,
+                           float* out32, void* out16, float* sum_tail, float* mean_tail, float* rstd_tail, immtsf_stream_t stream);
+int immtsf_bert_body_add_layernorm(const float* xin, int32_t B, int32_t S_in, int32_t s_from, const float* y, int32_t S, int32_t q_from,
+                                   int32_t d, const float* gamma, const float* beta, float eps, float p_drop, uint64_t seed, uint64_t site,
+                                   float* out32, void* out16, float* sum, float* mean, float* rstd, immtsf_stream_t stream);
+int immtsf_bert_body_layernorm_backward(const float* dy_a, int32_t B, int32_t Sa, int32_t sa_from, int32_t Sn, const float* dy_b,
+                                        int32_t tb_from, const float* sum, const float* mean, const float* rstd, const float* gamma, int32_t d,
+                                        int32_t S, int32_t q_from, float p_drop, uint64_t seed, uint64_t site, int32_t drop_first, float* dx32,
+                                        float* dbr32, void* dbr16, immtsf_stream_t stream);
+int immtsf_bert_body_gelu_backward(const float* pre, const float* dact, uint64_t n, float* dpre32, void* dpre16, immtsf_stream_t stream);
+int immtsf_bert_body_attention_forward(const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, int32_t B, int32_t S,
+                                       int32_t H, int32_t q_from, float scale, int32_t precision, float p_drop, uint64_t seed, uint64_t site,
+                                       float* out32, void* out16, float* lse, immtsf_stream_t stream);
+int immtsf_bert_body_attention_backward(const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, const float* dout,
+                                        const float* out, const float* lse, int32_t B, int32_t S, int32_t H, int32_t q_from, int32_t dq_from,
+                                        int32_t k_from, float scale, int32_t precision, float p_drop, uint64_t seed, uint64_t site, float* dq,
+                                        int32_t dq_rows, float* dk, float* dv, int32_t dkv_rows, int32_t ldd, float* dsum,
+                                        immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

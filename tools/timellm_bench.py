@@ -12,7 +12,12 @@ passes (their spread is the noise).
 widths (hidden 4096, 32 heads over 32 K/V heads, intermediate 11008) with 2 layers, at the same B, S_p and S_t; the body alone, with
 the launches per direction of the fused plan in the line.
 
-usage: python tools/timellm_bench.py [--llm GPT2|LLAMA] [--iters 5] [--passes 5] [--batch 64] [--out FILE]
+--llm BERT: the same for the frozen BERT body (immtsf.ops.bert_body: csrc/bert_body.hip) on an offline stand-in of bert-base's widths
+(hidden 768, 12 heads, intermediate 3072; max_position_embeddings 1024 so that the prompt and the patches fit) with 6 layers, at the
+same B, S_p and S_t, in train mode (the body's dropouts at BertConfig's 0.1 on both paths); the body alone, with the launches per
+direction of the fused plan in the line.
+
+usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--iters 5] [--passes 5] [--batch 64] [--out FILE]
 """
 import argparse
 import json
@@ -35,9 +40,9 @@ def main():
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--llm", choices=("GPT2", "LLAMA"), default="GPT2")
+    ap.add_argument("--llm", choices=("GPT2", "LLAMA", "BERT"), default="GPT2")
     args = ap.parse_args()
-    llama = args.llm == "LLAMA"
+    llama, bert = args.llm == "LLAMA", args.llm == "BERT"
     layers = 2 if llama else LAYERS
     import torch
     from immtsf import config, ops
@@ -49,6 +54,7 @@ def main():
         input_len=L, pred_len=L, use_norm=True, d_ff=32, ts_vocab_size=1000, input_token_len=16, stride=8, domain_des="synthetic", top_k=5,
         C=C, llm_model_timellm=args.llm, llm_layers_timellm=layers, dropout=0.1, d_model=16, n_heads=8, batch_size=B, device=str(dev),
         immtsf_offline_llm=dict(hidden_size=4096, num_attention_heads=32, num_key_value_heads=32, intermediate_size=11008) if llama
+        else dict(hidden_size=768, num_attention_heads=12, intermediate_size=3072, max_position_embeddings=1024) if bert
         else True)).to(dev).train()
     m.word_embeddings = m.llm_model.get_input_embeddings().weight
     g = torch.Generator().manual_seed(1)
@@ -70,7 +76,7 @@ def main():
     def body(fused):
         tail.grad = None
         if fused:
-            out = (ops.llama_body if llama else ops.gpt2_body)(m.llm_model, prefix, tail, True)
+            out = (ops.llama_body if llama else ops.bert_body if bert else ops.gpt2_body)(m.llm_model, prefix, tail, True)
         else:
             out = m.llm_model(inputs_embeds=torch.cat([prefix, tail], 1)).last_hidden_state[:, -S_t:]
         (out * up_b).sum().backward()
@@ -96,7 +102,11 @@ def main():
         if llama:       # the fused plan: 9 launches a layer + 3 for the last layer's tail queries + table and final norm;
             #             10 a layer backward (the attention backward is two) + the final norm's
             line.update(llm="LLAMA", launches_forward=9 * layers + 5, launches_backward=10 * layers + 1)
-        for what, fn in ((("body", body),) if llama else (("body", body), ("forecasting", whole))):
+        if bert:        # the fused plan: 8 launches a layer + the embedding + the last layer's tail-query product and the
+            #             copy that gathers its rows; backward 9 a layer in fp32 mode (the attention backward is two), 11 in bf16 mode
+            #             (three, and the bf16 image of dqkv), + the embedding's and the fill of the last layer's prompt dq rows
+            line.update(llm="BERT", launches_forward=8 * layers + 3, launches_backward=(11 if prec == "bf16" else 9) * layers + 2)
+        for what, fn in ((("body", body),) if (llama or bert) else (("body", body), ("forecasting", whole))):
             for fused in (True, False):
                 for _ in range(2):
                     fn(fused)
