@@ -262,6 +262,8 @@ _PROTOS = {
     "immtsf_bert_body_attention_backward": (C.c_int, [c_f32p, C.c_int32, c_f32p, c_f32p, C.c_int32, c_f32p, c_f32p, c_f32p] + [C.c_int32] * 6 +
                                             [C.c_float, C.c_int32, C.c_float, C.c_uint64, C.c_uint64, c_f32p, C.c_int32, c_f32p, c_f32p,
                                              C.c_int32, C.c_int32, c_f32p, c_stream]),
+    "immtsf_timellm_prompt_supported": (C.c_int, [C.c_int32] * 3),
+    "immtsf_timellm_prompt_stats": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, c_stream]),
     "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,

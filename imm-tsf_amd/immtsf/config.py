@@ -146,6 +146,11 @@ timellm_fused = os.environ.get("IMMTSF_TIMELLM_FUSED", "1") != "0"
 # stock call (178 vs 72 ms), so fp32 mode keeps the stock call unless IMMTSF_TIMELLM_BERT_FP32=1 asks for the operator (the
 # cross-check of the two paths at fp32 accuracy; less saved memory).  Under timellm_fused either way
 timellm_bert_fp32 = os.environ.get("IMMTSF_TIMELLM_BERT_FP32", "0") == "1"
+# TimeLLM's prompt statistics (min, max, median, trend, top lags of every window) in ONE launch and ONE device-to-host copy per
+# forecasting() call (immtsf.ops.timellm_prompt_stats, csrc/timellm_prompt.hip) wherever timellm_prompt_supported allows;
+# IMMTSF_TIMELLM_PROMPT_FUSED=0: the torch expressions with rfft / irfft and five host reads per window -- the cross-check.  The text is
+# formatted and tokenised on the host either way
+timellm_prompt_fused = os.environ.get("IMMTSF_TIMELLM_PROMPT_FUSED", "1") != "0"
 # Raw-text mode (fusions.load_llm.embed_notes, immtsf.text.embed_corpus): a frozen GPT2Model over the notes' REAL tokens only, packed
 # back to back (immtsf.ops.gpt2_embed_notes: csrc/note_embed.hip + the GEMM family + the row kernels of csrc/gpt2.hip), wherever
 # gpt2_embed_notes_supported allows and the tokenizer pads on the right; IMMTSF_NOTE_EMBED_FUSED=0: the reference's formulation (every

@@ -4099,6 +4099,44 @@ def bert_body(llm_model, prefix_embeds, tail_embeds, training, precision=None, s
     return BertBodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), int(seed) & 0xFFFFFFFFFFFFFFFF, need_bwd)
 
 
+# ---- TimeLLM's prompt statistics (csrc/timellm_prompt.hip) -------------------------------------------------------------------------------
+def timellm_prompt_supported(L, C, top_k):
+    """the limits of the prompt-statistics kernel (immtsf_timellm_prompt_supported): 1 <= L <= 2048, 1 <= C <= 64, 1 <= top_k <= 64 and the
+    (L, C) tile within 64 KB of LDS (L C <= 16384)"""
+    return bool(_lib.load().immtsf_timellm_prompt_supported(int(L), int(C), int(top_k)))
+
+
+def timellm_prompt_split(packed, C):
+    """the (B, 3 C + 1) float32 and (B, top_k) int32 views of a packed (B, 3 C + 1 + top_k) buffer, on whichever device it lies"""
+    n = 3 * int(C) + 1
+    return packed[:, :n], packed[:, n:].view(torch.int32)
+
+
+def timellm_prompt_packed(x, top_k):
+    """one launch for the batch: x (B, L, C) -> the packed (B, 3 C + 1 + top_k) buffer of four-byte words timellm_prompt_split reads
+    (a float32 tensor whose last top_k columns hold int32 bits), so that ONE copy brings every statistic to the host.  No autograd (the
+    prompt carries no gradient), no host sync.  Outside timellm_prompt_supported this raises: callers check."""
+    if x.dim() != 3:
+        raise _lib.ImmtsfError(f"timellm_prompt_stats: x (B, L, C), got {tuple(x.shape)}")
+    x = _c(x.detach().float())
+    _need_gpu(x)
+    B, L, Cc = x.shape
+    top_k = int(top_k)
+    if L < 1 or Cc < 1 or top_k < 1 or not timellm_prompt_supported(L, Cc, top_k):
+        raise _lib.ImmtsfError(f"timellm_prompt_stats: L {L}, C {Cc}, top_k {top_k} is outside timellm_prompt_supported")
+    packed = torch.empty(B, 3 * Cc + 1 + top_k, dtype=torch.float32, device=x.device)
+    check(_lib.load().immtsf_timellm_prompt_stats(ptr(x), B, L, Cc, top_k, ptr(packed), stream_ptr()), "timellm_prompt_stats")
+    return packed
+
+
+def timellm_prompt_stats(x, top_k):
+    """TimeLLM's five prompt statistics of x (B, L, C) in one launch: (stats, lags), a (B, 3 C + 1) float32 view -- min, max and lower
+    median per channel, then the trend value x.diff(1).sum(1).mean(1), whose sign the prompt spells -- and a (B, top_k) int32 view -- the
+    lags of the min(top_k, L) largest circular autocorrelations, descending, ties to the lower lag, padded with the last -- of ONE device
+    buffer (timellm_prompt_packed's).  Semantics: include/immtsf.h."""
+    return timellm_prompt_split(timellm_prompt_packed(x, top_k), x.shape[2])
+
+
 # ------------------------------------------------------------------------------------------------ LatentODE backbone
 def _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents):
     return _lib.LatentODEDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(units), int(gru_units), int(latents))

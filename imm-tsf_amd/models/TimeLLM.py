@@ -15,7 +15,10 @@ a Llama body inside immtsf.ops.llama_body_supported on immtsf.ops.llama_body (cs
 immtsf.ops.bert_body_supported on immtsf.ops.bert_body (csrc/bert_body.hip, DESIGN 4s: bidirectional, so its backward runs through the
 prompt rows too; its dropouts are drawn in the kernels; in bf16 mode only, where it measured 2.8x the stock call -- in fp32 mode the
 stock call is faster and stays, unless config.timellm_bert_fp32 / IMMTSF_TIMELLM_BERT_FP32=1) under the same knob; `self.llm_model` stays the transformers model, and every
-other body (a sequence past max_position_embeddings included) runs the stock call."""
+other body (a sequence past max_position_embeddings included) runs the stock call.  The prompt's statistics (min, max, median, trend,
+top lags of every window) come from immtsf.ops.timellm_prompt_stats (csrc/timellm_prompt.hip: one launch, and ONE copy to the host per
+forecasting() call instead of five reads per window; config.timellm_prompt_fused / IMMTSF_TIMELLM_PROMPT_FUSED=0 turns it off,
+`prompt_stat_calls` counts); the text is formatted and tokenised on the host, so the step still cannot be captured."""
 from math import sqrt
 
 import torch
@@ -24,7 +27,7 @@ import torch.nn.functional as F
 
 from immtsf import config
 from immtsf.ops import (bert_body, bert_body_supported, gpt2_body, gpt2_body_supported, linear, llama_body, llama_body_supported,
-                        shared_kv_attention)
+                        shared_kv_attention, timellm_prompt_packed, timellm_prompt_split, timellm_prompt_supported)
 from layers.Embed import PatchEmbedding
 from models._common import masked_instance_norm
 
@@ -120,6 +123,7 @@ class TimeLLM(nn.Module):
         self.output_projection = FlattenHead(self.head_nf, self.pred_len, head_dropout=configs.dropout)
         self.zeros_pad = torch.zeros(configs.batch_size, max(self.input_len, self.pred_len), self.C, device=configs.device)
         self.fused_body_calls = 0          # forecasting() calls whose frozen body ran on immtsf.ops.gpt2_body / llama_body / bert_body
+        self.prompt_stat_calls = 0         # _get_prompt() calls whose statistics came from immtsf.ops.timellm_prompt_stats
 
     def _get_model_and_tokenizer(self, model_name, layers, offline):
         from transformers import BertConfig, BertModel, BertTokenizer, GPT2Config, GPT2Model, GPT2Tokenizer
@@ -162,8 +166,27 @@ class TimeLLM(nn.Module):
             self.tokenizer.add_special_tokens({"pad_token": "[PAD]"})
             self.tokenizer.pad_token = "[PAD]"
 
+    def _prompt_text(self, mn, mx, md, up, lg):
+        """the reference's prompt (:186-194) from one window's numbers as Python lists"""
+        tr = "upward" if up else "downward"
+        return (f"<|start_prompt|>Dataset: {self.domain_des}. Forecast next {self.pred_len} from past "
+                f"{self.input_len}. Min {mn}, Max {mx}, Median {md}, "
+                f"Trend {tr}, Top lags {lg}.<|end_prompt|>")
+
+    def _format_prompts(self, stats, lags):
+        """the B prompts from HOST tensors only: stats (B, 3 N + 1) float32 = min | max | median per channel, then the trend value;
+        lags (B, top_k) integer -- the two views of immtsf.ops.timellm_prompt_stats' buffer after its one copy to the host"""
+        N = (stats.size(1) - 1) // 3
+        st, lg = stats.tolist(), lags.tolist()
+        return [self._prompt_text(r[:N], r[N:2 * N], r[2 * N:3 * N], r[3 * N] > 0, lg[b]) for b, r in enumerate(st)]
+
     def _get_prompt(self, x_enc):
         B, L, N = x_enc.shape
+        if x_enc.is_cuda and config.timellm_prompt_fused and B > 0 and timellm_prompt_supported(L, N, self.top_k):
+            # the five statistics of every window in one launch, ONE copy to the host (csrc/timellm_prompt.hip); the text is Python's
+            host = timellm_prompt_packed(x_enc, self.top_k).cpu()
+            self.prompt_stat_calls += 1
+            return self._format_prompts(*timellm_prompt_split(host, N))
         mins, maxs = x_enc.min(dim=1)[0], x_enc.max(dim=1)[0]
         meds = x_enc.median(dim=1).values
         trend = x_enc.diff(dim=1).sum(dim=1).mean(dim=1)
@@ -174,10 +197,7 @@ class TimeLLM(nn.Module):
             lags = torch.cat([lags, lags[:, -1, None].repeat(1, self.top_k - lags.size(1))], dim=-1)
         prompts = []
         for b in range(B):
-            tr = "upward" if trend[b].item() > 0 else "downward"
-            prompts.append(f"<|start_prompt|>Dataset: {self.domain_des}. Forecast next {self.pred_len} from past "
-                           f"{self.input_len}. Min {mins[b].tolist()}, Max {maxs[b].tolist()}, Median {meds[b].tolist()}, "
-                           f"Trend {tr}, Top lags {lags[b].tolist()}.<|end_prompt|>")
+            prompts.append(self._prompt_text(mins[b].tolist(), maxs[b].tolist(), meds[b].tolist(), trend[b].item() > 0, lags[b].tolist()))
         return prompts
 
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):

@@ -982,6 +982,22 @@ int immtsf_bert_body_attention_backward(const float* q, int32_t ldq, const float
                                         int32_t dq_rows, float* dk, float* dv, int32_t dkv_rows, int32_t ldd, float* dsum,
                                         immtsf_stream_t stream);
 
+/* ---- TimeLLM's prompt statistics (added within ABI 7: new functions only; csrc/timellm_prompt.hip): the five per-window statistics
+ * the prompt text spells, for the whole batch in ONE launch (a workgroup per window, its tile in LDS).  x (B, L, C) fp32 contiguous;
+ * out: B rows of 3 C + 1 + top_k four-byte words in one allocation, so one copy brings everything to the host:
+ *   [0, C) min, [C, 2C) max, [2C, 3C) median per channel, [3C] trend (floats), then top_k int32 lags.
+ * min / max: the float x.min(dim=1) / x.max(dim=1) select; among elements that compare equal (-0.0, 0.0) the one of lowest time
+ *   index; a NaN in the channel gives NaN.  median: the lower median, the element of sorted position (L - 1) / 2, by rank counting with
+ *   ties to the lower time index; NaN in the channel gives NaN.  trend: x.diff(dim=1).sum(dim=1).mean(dim=1), the differences summed in
+ *   time order and the channels in index order, in fp32; 0 at L == 1; the caller takes > 0.  lags: corr[tau] = mean_c sum_t x[t, c]
+ *   x[(t + tau) mod L, c] computed directly for tau <= L / 2 and mirrored bit for bit into corr[L - tau]; the min(top_k, L) largest by
+ *   rank counting with ties to the lower lag (NaN counts as -inf), descending; entries past L repeat the last lag.
+ * No atomics, one writer per output word, fixed summation order (the same inputs give the same bits).
+ * ..._supported: 1 <= L <= 2048, 1 <= C <= 64, 1 <= top_k <= 64, L C <= 16384 (the tile within 64 KB of LDS).
+ * Outside these limits ..._stats returns IMMTSF_EUNSUPPORTED and launches nothing; nothing allocates or synchronises. */
+int immtsf_timellm_prompt_supported(int32_t L, int32_t C, int32_t top_k);
+int immtsf_timellm_prompt_stats(const float* x, int64_t B, int32_t L, int32_t C, int32_t top_k, void* out, immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

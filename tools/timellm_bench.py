@@ -17,7 +17,12 @@ the launches per direction of the fused plan in the line.
 same B, S_p and S_t, in train mode (the body's dropouts at BertConfig's 0.1 on both paths); the body alone, with the launches per
 direction of the fused plan in the line.
 
-usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--iters 5] [--passes 5] [--batch 64] [--out FILE]
+--prompt: the prompt's statistics in one launch and one host copy (immtsf.ops.timellm_prompt_stats: csrc/timellm_prompt.hip) against
+IMMTSF_TIMELLM_PROMPT_FUSED=0 (the torch expressions, five host reads per window) with the GPT-2 body fused on both sides, at the same
+shape (B 64, L 32, C 8, top_k 5): _get_prompt() alone on the normalised batch and the whole forecasting() + backward, the same
+alternating passes; one JSON line per precision mode with the best pass, all passes and their range (lo, hi) per side.
+
+usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--prompt] [--iters 5] [--passes 5] [--batch 64] [--out FILE]
 """
 import argparse
 import json
@@ -41,7 +46,10 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--llm", choices=("GPT2", "LLAMA", "BERT"), default="GPT2")
+    ap.add_argument("--prompt", action="store_true", help="time the prompt statistics, knob on against knob off (GPT-2 body)")
     args = ap.parse_args()
+    if args.prompt and args.llm != "GPT2":
+        ap.error("--prompt runs with the GPT-2 body")
     llama, bert = args.llm == "LLAMA", args.llm == "BERT"
     layers = 2 if llama else LAYERS
     import torch
@@ -95,7 +103,39 @@ def main():
         return (time.perf_counter() - t0) * 1e3 / n
 
     lines = []
-    for prec in ("fp32", "bf16"):
+    if args.prompt:
+        x_norm = masked_instance_norm(data, mask)[0]
+
+        def prompt(on):
+            config.timellm_prompt_fused = on
+            m._get_prompt(x_norm)
+
+        def whole_prompt(on):
+            config.timellm_prompt_fused = on
+            whole(True)
+
+        default = config.timellm_prompt_fused
+        for prec in ("fp32", "bf16"):
+            config.precision = prec
+            line = {"tool": "timellm_bench", "leg": "prompt", "precision": prec, "B": B, "L": L, "C": C, "top_k": m.top_k, "S_p": S_p,
+                    "iters": args.iters, "passes": args.passes}
+            for what, fn in (("get_prompt", prompt), ("forecasting", whole_prompt)):
+                for on in (True, False):
+                    for _ in range(2):
+                        fn(on)
+                t = {True: [], False: []}
+                for _ in range(args.passes):
+                    for on in (True, False):
+                        t[on].append(timed(lambda: fn(on), args.iters))
+                for on, name in ((True, "on"), (False, "off")):
+                    line[f"{what}_{name}_ms"] = round(min(t[on]), 3)
+                    line[f"{what}_{name}_ms_range"] = [round(min(t[on]), 3), round(max(t[on]), 3)]
+                    line[f"{what}_{name}_ms_passes"] = [round(v, 3) for v in t[on]]
+                line[f"{what}_speedup"] = round(min(t[False]) / min(t[True]), 2)
+            print(json.dumps(line), flush=True)
+            lines.append(json.dumps(line))
+        config.timellm_prompt_fused = default
+    for prec in (() if args.prompt else ("fp32", "bf16")):
         config.precision = prec
         line = {"tool": "timellm_bench", "precision": prec, "B": B, "layers": layers, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
                 "passes": args.passes}
