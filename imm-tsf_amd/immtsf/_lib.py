@@ -264,6 +264,12 @@ _PROTOS = {
                                              C.c_int32, C.c_int32, c_f32p, c_stream]),
     "immtsf_timellm_prompt_supported": (C.c_int, [C.c_int32] * 3),
     "immtsf_timellm_prompt_stats": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, c_stream]),
+    "immtsf_timellm_prototypes_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "immtsf_timellm_prototypes_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "immtsf_timellm_prototypes_forward": (C.c_int, [C.c_int32, c_f32p, C.c_void_p] + [c_f32p] * 6 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32] +
+                                          [c_f32p] * 4 + [C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_timellm_prototypes_backward": (C.c_int, [C.c_int32, c_f32p, C.c_void_p] + [c_f32p] * 6 + [C.c_int64, C.c_int64, C.c_int32, C.c_int32] +
+                                           [c_f32p] * 6 + [C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_ttm_mixer_supported": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_ttm_mixer_forward": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [c_f32p] * 9 + [C.c_float, c_f32p,

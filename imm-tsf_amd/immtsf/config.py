@@ -151,6 +151,12 @@ timellm_bert_fp32 = os.environ.get("IMMTSF_TIMELLM_BERT_FP32", "0") == "1"
 # IMMTSF_TIMELLM_PROMPT_FUSED=0: the torch expressions with rfft / irfft and five host reads per window -- the cross-check.  The text is
 # formatted and tokenised on the host either way
 timellm_prompt_fused = os.environ.get("IMMTSF_TIMELLM_PROMPT_FUSED", "1") != "0"
+# TimeLLM's word prototypes (the reprogramming layer's keys and values) in folded form: W_map (E [Wk^T | Wv^T]) instead of
+# (W_map E) Wk^T, (W_map E) Wv^T, so the (ts_vocab_size, d_llm) table is never formed and the mapping weight is read once per direction
+# (immtsf.ops.timellm_prototypes, csrc/timellm_reprogram.hip) wherever timellm_prototypes_supported allows and the fold has
+# fewer flops (ts_vocab_size d_llm > 2 D (d_llm + ts_vocab_size)); IMMTSF_TIMELLM_REPROGRAM_FUSED=0: the three linear() calls as the
+# reference writes them -- the cross-check
+timellm_reprogram_fused = os.environ.get("IMMTSF_TIMELLM_REPROGRAM_FUSED", "1") != "0"
 # Raw-text mode (fusions.load_llm.embed_notes, immtsf.text.embed_corpus): a frozen GPT2Model over the notes' REAL tokens only, packed
 # back to back (immtsf.ops.gpt2_embed_notes: csrc/note_embed.hip + the GEMM family + the row kernels of csrc/gpt2.hip), wherever
 # gpt2_embed_notes_supported allows and the tokenizer pads on the right; IMMTSF_NOTE_EMBED_FUSED=0: the reference's formulation (every

@@ -4137,6 +4137,100 @@ def timellm_prompt_stats(x, top_k):
     return timellm_prompt_split(timellm_prompt_packed(x, top_k), x.shape[2])
 
 
+# ---- TimeLLM's word prototypes in folded form (csrc/timellm_reprogram.hip) -----------------------------------------------------------------
+def timellm_prototypes_supported(E, W_map, Wk, Wv):
+    """the limits of the folded prototype operator: fp32 contiguous tensors on the GPU, E (V, d_llm) WITHOUT a gradient (the operator
+    returns none for it), W_map (S, V), Wk / Wv (D, d_llm) with 2 D <= 128 a multiple of 16 and d_llm a multiple of 8; any S, V >= 1"""
+    ts = (E, W_map, Wk, Wv)
+    if any(t is None or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() for t in ts):
+        return False
+    if E.requires_grad or Wk.shape != Wv.shape or W_map.shape[1] != E.shape[0] or Wk.shape[1] != E.shape[1]:
+        return False
+    return bool(_lib.load().immtsf_timellm_prototypes_supported(W_map.shape[0], E.shape[0], E.shape[1], Wk.shape[0]))
+
+
+def timellm_prototypes_pays(S, d_llm, D):
+    """the fold's flop count 2 D2 V (d_llm + S) against the as-written 2 S V d_llm (+ the two projections): it wins when
+    S d_llm > D2 (d_llm + S), D2 = 2 D"""
+    return S * d_llm > 2 * D * (d_llm + S)
+
+
+class TimeLLMPrototypesFn(torch.autograd.Function):
+    """(k, v) = key / value projection of mapping_layer(E^T)^T without the (S, d_llm) table: P = E [Wk^T | Wv^T], [k|v] = W_map P +
+    b_map (x) r + [bk|bv] (immtsf_timellm_prototypes_forward, 3 launches); backward 3 launches, W_map read once (include/immtsf.h).
+    Saved: P (V, 2 D) and r (2 D); nothing is kept across calls."""
+
+    @staticmethod
+    def forward(ctx, E, W_map, b_map, Wk, bk, Wv, bv, precision, cache_on):
+        lib = _lib.load()
+        S, V = W_map.shape
+        D, d = Wk.shape
+        dev = W_map.device
+        bf = precision == 1
+        E16 = _gpt2_w16(cache_on, E) if bf else None
+        P = torch.empty(V, 2 * D, dtype=torch.float32, device=dev)
+        r = torch.empty(2 * D, dtype=torch.float32, device=dev)
+        kv = torch.empty(2, S, D, dtype=torch.float32, device=dev)
+        nb = int(lib.immtsf_timellm_prototypes_scratch_bytes(S, V, d, D, 0))
+        scratch = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        check(lib.immtsf_timellm_prototypes_forward(precision, ptr(E), ptr(E16), ptr(W_map), ptr(b_map), ptr(Wk), ptr(bk), ptr(Wv), ptr(bv),
+                                                    S, V, d, D, ptr(P), ptr(r), ptr(kv[0]), ptr(kv[1]), ptr(scratch), nb, stream_ptr()),
+              "timellm_prototypes_forward")
+        ctx.save_for_backward(E, W_map, b_map, P, r)
+        ctx.E16, ctx.precision, ctx.dims = E16, precision, (S, V, d, D)
+        params = (W_map, b_map, Wk, bk, Wv, bv)
+        ctx.sinks = _sinks_of(params)
+        ctx.pre = all(s is not None and getattr(p, "_immtsf_grad_prezeroed", False) for p, s in zip(params, ctx.sinks))
+        return kv[0], kv[1]
+
+    @staticmethod
+    def backward(ctx, dk, dv):
+        lib = _lib.load()
+        E, W_map, b_map, P, r = ctx.saved_tensors
+        S, V, d, D = ctx.dims
+        dev = W_map.device
+        dk = torch.zeros(S, D, dtype=torch.float32, device=dev) if dk is None else dk.contiguous()
+        dv = torch.zeros(S, D, dtype=torch.float32, device=dev) if dv is None else dv.contiguous()
+        dk, dv = (g.clone() if g.data_ptr() % 16 else g for g in (dk, dv))      # (a view at an odd offset of a larger gradient buffer)
+        if ctx.pre:      # gradient sinks that their owner zero-fills every step: every word is written once, nothing returned
+            dW_map, db_map, dWk, dbk, dWv, dbv = ctx.sinks
+            ret = (None,) * 6
+        else:
+            dW_map = torch.empty(S, V, dtype=torch.float32, device=dev)
+            up8 = lambda n: (n + 7) // 8 * 8      # noqa: E731
+            flat = torch.empty(up8(S) + 2 * (up8(D * d) + up8(D)), dtype=torch.float32, device=dev)
+            off, small = 0, []
+            for n, shape in ((S, (S,)), (D * d, (D, d)), (D, (D,)), (D * d, (D, d)), (D, (D,))):
+                small.append(flat[off:off + n].view(shape))
+                off += up8(n)
+            db_map, dWk, dbk, dWv, dbv = small
+            ret = (dW_map, db_map, dWk, dbk, dWv, dbv)
+            del small
+        nb = int(lib.immtsf_timellm_prototypes_scratch_bytes(S, V, d, D, 1))
+        scratch = torch.empty(max(nb, 16), dtype=torch.uint8, device=dev)
+        check(lib.immtsf_timellm_prototypes_backward(ctx.precision, ptr(E), ptr(ctx.E16), ptr(W_map), ptr(b_map), ptr(P), ptr(r), ptr(dk),
+                                                     ptr(dv), S, V, d, D, ptr(dW_map), ptr(db_map), ptr(dWk), ptr(dbk), ptr(dWv), ptr(dbv),
+                                                     ptr(scratch), nb, stream_ptr()), "timellm_prototypes_backward")
+        need = ctx.needs_input_grad
+        return (None,) + tuple(g if need[1 + i] else None for i, g in enumerate(ret)) + (None, None)
+
+
+def timellm_prototypes(E, W_map, b_map, Wk, bk, Wv, bv, precision=None, cache_on=None):
+    """TimeLLM's word prototypes, the keys and values of its reprogramming layer, in folded form: (k, v), each (S, D) fp32, equal to
+    key_projection(src), value_projection(src) with src = mapping_layer(E^T)^T -- computed as W_map (E [Wk^T | Wv^T]) + ..., so the
+    (S, d_llm) table src is never formed and W_map is read once per direction.  Gradients for the six parameters, none for the frozen E.
+    In bf16 mode E is read through a bf16 image cached on `cache_on` (the model whose frozen weights the GPT-2 body caches; default: on
+    E itself), keyed by E's address and version.  Outside timellm_prototypes_supported this raises: callers check."""
+    if not timellm_prototypes_supported(E, W_map, Wk, Wv):
+        raise _lib.ImmtsfError("timellm_prototypes: outside timellm_prototypes_supported")
+    S, D = W_map.shape[0], Wk.shape[0]
+    b_map, bk, bv = _c(b_map), _c(bk), _c(bv)
+    _need_gpu(b_map, bk, bv)
+    if tuple(b_map.shape) != (S,) or tuple(bk.shape) != (D,) or tuple(bv.shape) != (D,):
+        raise _lib.ImmtsfError("timellm_prototypes: b_map (S), bk, bv (D)")
+    return TimeLLMPrototypesFn.apply(E, W_map, b_map, Wk, bk, Wv, bv, config.precision_code(precision), E if cache_on is None else cache_on)
+
+
 # ------------------------------------------------------------------------------------------------ LatentODE backbone
 def _latent_ode_dims(B, L, Lp, C, rec_dims, units, gru_units, latents):
     return _lib.LatentODEDims(int(B), int(L), int(Lp), int(C), int(rec_dims), int(units), int(gru_units), int(latents))

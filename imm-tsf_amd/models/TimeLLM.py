@@ -18,7 +18,11 @@ stock call is faster and stays, unless config.timellm_bert_fp32 / IMMTSF_TIMELLM
 other body (a sequence past max_position_embeddings included) runs the stock call.  The prompt's statistics (min, max, median, trend,
 top lags of every window) come from immtsf.ops.timellm_prompt_stats (csrc/timellm_prompt.hip: one launch, and ONE copy to the host per
 forecasting() call instead of five reads per window; config.timellm_prompt_fused / IMMTSF_TIMELLM_PROMPT_FUSED=0 turns it off,
-`prompt_stat_calls` counts); the text is formatted and tokenised on the host, so the step still cannot be captured."""
+`prompt_stat_calls` counts); the text is formatted and tokenised on the host, so the step still cannot be captured.  The word
+prototypes -- the reprogramming layer's keys and values, key / value_projection(mapping_layer(E^T)^T) -- come from
+immtsf.ops.timellm_prototypes (csrc/timellm_reprogram.hip, DESIGN 4t: the fold W_map (E [Wk^T | Wv^T]), the mapping weight read once
+per direction) where the fold has fewer flops; config.timellm_reprogram_fused / IMMTSF_TIMELLM_REPROGRAM_FUSED=0 turns it off,
+`reprogram_fused_calls` counts.  Nothing of it is kept across calls: the fused optimizer writes parameters without a version bump."""
 from math import sqrt
 
 import torch
@@ -27,7 +31,8 @@ import torch.nn.functional as F
 
 from immtsf import config
 from immtsf.ops import (bert_body, bert_body_supported, gpt2_body, gpt2_body_supported, linear, llama_body, llama_body_supported,
-                        shared_kv_attention, timellm_prompt_packed, timellm_prompt_split, timellm_prompt_supported)
+                        shared_kv_attention, timellm_prompt_packed, timellm_prompt_split, timellm_prompt_supported, timellm_prototypes,
+                        timellm_prototypes_pays, timellm_prototypes_supported)
 from layers.Embed import PatchEmbedding
 from models._common import masked_instance_norm
 
@@ -58,12 +63,31 @@ class ReprogrammingLayer(nn.Module):
         self.dropout = nn.Dropout(attention_dropout)
 
     def forward(self, Q, K_src, V_src):
+        k = linear(K_src, self.key_projection.weight, self.key_projection.bias)
+        v = linear(V_src, self.value_projection.weight, self.value_projection.bias)
+        return self._attend(Q, k, v, K_src.size(-1))
+
+    def folds(self, E, mapping_layer):
+        """whether forward_folded takes (E, mapping_layer): the knob, the GPU, the operator's limits, and fewer flops than the as-written
+        mapping + two projections (S d_llm > 2 D (d_llm + S): the small d_model TimeLLM is run with, not the toy shapes of the tests)"""
+        Wk, Wv = self.key_projection.weight, self.value_projection.weight
+        return (config.timellm_reprogram_fused and E.is_cuda and mapping_layer.bias is not None and self.key_projection.bias is not None and
+                self.value_projection.bias is not None and timellm_prototypes_supported(E, mapping_layer.weight, Wk, Wv) and
+                timellm_prototypes_pays(mapping_layer.weight.size(0), E.size(1), Wk.size(0)))
+
+    def forward_folded(self, Q, E, mapping_layer, cache_on=None):
+        """forward(Q, src, src) for src = mapping_layer(E^T)^T without forming src: the keys and values from
+        immtsf.ops.timellm_prototypes, then the same attention and out-projection.  E (V, d_llm) the frozen word embeddings"""
+        k, v = timellm_prototypes(E, mapping_layer.weight, mapping_layer.bias, self.key_projection.weight, self.key_projection.bias,
+                                  self.value_projection.weight, self.value_projection.bias, cache_on=cache_on)
+        return self._attend(Q, k, v, E.size(1))
+
+    def _attend(self, Q, k, v, d_llm):
         Bm, Lq, _ = Q.shape
-        Vs, H = K_src.shape[0], self.n_heads
+        Vs, H = k.shape[0], self.n_heads
         q = linear(Q, self.query_projection.weight, self.query_projection.bias).view(Bm, Lq, H, -1)
-        k = linear(K_src, self.key_projection.weight, self.key_projection.bias).view(Vs, H, -1)
-        v = linear(V_src, self.value_projection.weight, self.value_projection.bias).view(Vs, H, -1)
-        scale = 1.0 / sqrt(K_src.size(-1) // H)          # d_llm / H, as the reference has it (:51)
+        k, v = k.view(Vs, H, -1), v.view(Vs, H, -1)
+        scale = 1.0 / sqrt(d_llm // H)          # d_llm / H, as the reference has it (:51)
         p = float(self.dropout.p)
         training = self.training and p > 0.0
         out = shared_kv_attention(q, k, v, scale, p, training, config.next_seed() if training else 0, 16 + 1023)
@@ -124,6 +148,7 @@ class TimeLLM(nn.Module):
         self.zeros_pad = torch.zeros(configs.batch_size, max(self.input_len, self.pred_len), self.C, device=configs.device)
         self.fused_body_calls = 0          # forecasting() calls whose frozen body ran on immtsf.ops.gpt2_body / llama_body / bert_body
         self.prompt_stat_calls = 0         # _get_prompt() calls whose statistics came from immtsf.ops.timellm_prompt_stats
+        self.reprogram_fused_calls = 0     # forecasting() calls whose word prototypes came from immtsf.ops.timellm_prototypes
 
     def _get_model_and_tokenizer(self, model_name, layers, offline):
         from transformers import BertConfig, BertModel, BertTokenizer, GPT2Config, GPT2Model, GPT2Tokenizer
@@ -219,8 +244,13 @@ class TimeLLM(nn.Module):
             return self.patch_embedding(series)
         ts_out, n_vars = patches(x.permute(0, 2, 1))
         tp_out, _ = patches(observed_tp.unsqueeze(1).repeat(1, N, 1))
-        src = linear(self.word_embeddings.permute(1, 0), self.mapping_layer.weight, self.mapping_layer.bias).permute(1, 0)
-        rep = self.reprogramming_layer(ts_out + tp_out, src, src)
+        if self.reprogramming_layer.folds(self.word_embeddings, self.mapping_layer):
+            # the prototypes in folded form (csrc/timellm_reprogram.hip): the (ts_vocab_size, d_llm) table src is never formed
+            rep = self.reprogramming_layer.forward_folded(ts_out + tp_out, self.word_embeddings, self.mapping_layer, cache_on=self.llm_model)
+            self.reprogram_fused_calls += 1
+        else:
+            src = linear(self.word_embeddings.permute(1, 0), self.mapping_layer.weight, self.mapping_layer.bias).permute(1, 0)
+            rep = self.reprogramming_layer(ts_out + tp_out, src, src)
         rep = rep.view(B, N, self.patch_nums, self.d_llm).permute(0, 2, 1, 3).reshape(B, -1, self.d_llm)
         total = self.patch_nums * n_vars
         if config.timellm_fused and rep.is_cuda and gpt2_body_supported(self.llm_model, prompt_embeds.size(1), total):

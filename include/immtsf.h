@@ -998,6 +998,38 @@ int immtsf_bert_body_attention_backward(const float* q, int32_t ldq, const float
 int immtsf_timellm_prompt_supported(int32_t L, int32_t C, int32_t top_k);
 int immtsf_timellm_prompt_stats(const float* x, int64_t B, int32_t L, int32_t C, int32_t top_k, void* out, immtsf_stream_t stream);
 
+/* ---- TimeLLM's word prototypes in folded form (added within ABI 7: new functions only; csrc/timellm_reprogram.hip): the keys and
+ * values of the reprogramming layer, key/value_projection(mapping_layer(E^T)^T), regrouped so that the (S, d_llm) mapped table is never
+ * formed.  E (V, d_llm) the frozen input embeddings, W_map (S, V) / b_map (S) the mapping layer, Wk, Wv (D, d_llm) / bk, bv (D) the two
+ * projections, all fp32 contiguous; D2 = 2 D:
+ *   P     = E [Wk^T | Wv^T]                                 (V, D2) fp32, an output the backward takes again
+ *   r     = [rowsum(Wk) | rowsum(Wv)]                       (D2)    likewise
+ *   [k|v] = W_map P + b_map (x) r + [bk | bv]               k, v (S, D) each
+ * ..._forward: 3 launches -- P (a tile of 64 rows of E per workgroup); W_map P with V split over workgroups, each writing its partial
+ *   tile to `scratch` (one more workgroup sums r); the partials added in split order with the b_map (x) r and bias terms.  W_map is read
+ *   once.
+ * ..._backward, G = [dk | dv] (S, D2): 3 launches -- one pass over W_map, a workgroup per slab of 64 columns walking all S rows, writing
+ *   dW_map[:, slab] = G P[slab]^T and accumulating dP[slab] = W_map[:, slab]^T G from the same registers (dP lies in `scratch`);
+ *   dP^T E with V split over workgroups into partial tiles (further workgroups: d[bk|bv] = colsum(G), db_map = G r and
+ *   t = colsum(G * b_map[:, None])); the partials added in split order with t, the gradient through r, the same in every column of a row:
+ *   d[Wk; Wv] = dP^T E + t 1^T.  E takes no gradient.
+ * precision 0: every product on v_mfma_f32_16x16x4_f32 over fp32 operands; precision 1: on v_mfma_f32_16x16x32_bf16, W_map, P, G and dP
+ *   rounded to bf16 in registers and E read from the caller's bf16 image E16 (V, d_llm; null at precision 0); sums in fp32 either way.
+ * No atomics, one writer per output word, fixed summation order (the same inputs give the same bits).
+ * ..._supported: S >= 1, V >= 1, d_llm >= 8 and a multiple of 8, 16 <= 2 D <= 128 and a multiple of 16.  Outside these limits
+ * ..._forward / ..._backward return IMMTSF_EUNSUPPORTED and ..._scratch_bytes 0, and nothing is launched.  Pointers 16-byte aligned;
+ * `scratch` of at least ..._scratch_bytes(..., backward) bytes (IMMTSF_EWORKSPACE otherwise); nothing allocates or synchronises. */
+int immtsf_timellm_prototypes_supported(int64_t S, int64_t V, int32_t d_llm, int32_t D);
+size_t immtsf_timellm_prototypes_scratch_bytes(int64_t S, int64_t V, int32_t d_llm, int32_t D, int32_t backward);
+int immtsf_timellm_prototypes_forward(int32_t precision, const float* E, const void* E16, const float* W_map, const float* b_map,
+                                      const float* Wk, const float* bk, const float* Wv, const float* bv, int64_t S, int64_t V,
+                                      int32_t d_llm, int32_t D, float* P, float* r, float* k, float* v, void* scratch,
+                                      size_t scratch_bytes, immtsf_stream_t stream);
+int immtsf_timellm_prototypes_backward(int32_t precision, const float* E, const void* E16, const float* W_map, const float* b_map,
+                                       const float* P, const float* r, const float* dk, const float* dv, int64_t S, int64_t V,
+                                       int32_t d_llm, int32_t D, float* dW_map, float* db_map, float* dWk, float* dbk, float* dWv,
+                                       float* dbv, void* scratch, size_t scratch_bytes, immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

@@ -22,7 +22,13 @@ IMMTSF_TIMELLM_PROMPT_FUSED=0 (the torch expressions, five host reads per window
 shape (B 64, L 32, C 8, top_k 5): _get_prompt() alone on the normalised batch and the whole forecasting() + backward, the same
 alternating passes; one JSON line per precision mode with the best pass, all passes and their range (lo, hi) per side.
 
-usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--prompt] [--iters 5] [--passes 5] [--batch 64] [--out FILE]
+--reprogram: the word prototypes in folded form (immtsf.ops.timellm_prototypes: csrc/timellm_reprogram.hip) against
+IMMTSF_TIMELLM_REPROGRAM_FUSED=0 (the mapping layer and the two projections as three linear() calls) with the GPT-2 body fused on both
+sides: the stage alone, forward + backward (V 50257, S 1000, d_llm 768, H 8, d_keys 2: the model's own parameters), and the whole
+forecasting() + backward, the same alternating passes; one JSON line per precision mode with the best pass, all passes and their range
+(lo, hi) per side, whether every pass with the knob on lies below every pass with it off, and the operator's launches per direction.
+
+usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--prompt | --reprogram] [--iters 5] [--passes 5] [--batch 64] [--out FILE]
 """
 import argparse
 import json
@@ -47,9 +53,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--llm", choices=("GPT2", "LLAMA", "BERT"), default="GPT2")
     ap.add_argument("--prompt", action="store_true", help="time the prompt statistics, knob on against knob off (GPT-2 body)")
+    ap.add_argument("--reprogram", action="store_true", help="time the folded word prototypes, knob on against knob off (GPT-2 body)")
     args = ap.parse_args()
-    if args.prompt and args.llm != "GPT2":
-        ap.error("--prompt runs with the GPT-2 body")
+    if (args.prompt or args.reprogram) and args.llm != "GPT2":
+        ap.error("--prompt / --reprogram run with the GPT-2 body")
+    if args.prompt and args.reprogram:
+        ap.error("--prompt and --reprogram are separate legs")
     llama, bert = args.llm == "LLAMA", args.llm == "BERT"
     layers = 2 if llama else LAYERS
     import torch
@@ -135,7 +144,50 @@ def main():
             print(json.dumps(line), flush=True)
             lines.append(json.dumps(line))
         config.timellm_prompt_fused = default
-    for prec in (() if args.prompt else ("fp32", "bf16")):
+    if args.reprogram:
+        rl, E, mp = m.reprogramming_layer, m.word_embeddings, m.mapping_layer
+        S, D = m.num_tokens, rl.key_projection.weight.shape[0]
+        up_k, up_v = torch.randn(S, D, generator=g).to(dev), torch.randn(S, D, generator=g).to(dev)
+        trainable = [mp.weight, mp.bias, rl.key_projection.weight, rl.key_projection.bias, rl.value_projection.weight, rl.value_projection.bias]
+
+        def stage(on):
+            for p_ in trainable:
+                p_.grad = None
+            if on:
+                k, v = ops.timellm_prototypes(E, mp.weight, mp.bias, *trainable[2:], cache_on=m.llm_model)
+            else:       # as models/TimeLLM.py forecasting() and ReprogrammingLayer.forward write it
+                src = ops.linear(E.permute(1, 0), mp.weight, mp.bias).permute(1, 0)
+                k, v = ops.linear(src, trainable[2], trainable[3]), ops.linear(src, trainable[4], trainable[5])
+            torch.autograd.backward([k, v], [up_k, up_v])
+
+        def whole_reprogram(on):
+            config.timellm_reprogram_fused = on
+            whole(True)
+
+        default = config.timellm_reprogram_fused
+        for prec in ("fp32", "bf16"):
+            config.precision = prec
+            line = {"tool": "timellm_bench", "leg": "reprogram", "precision": prec, "B": B, "S": S, "V": E.shape[0], "d_llm": d, "D": D,
+                    "S_p": S_p, "iters": args.iters, "passes": args.passes, "launches_forward": 3, "launches_backward": 3}
+            for what, fn in (("stage", stage), ("forecasting", whole_reprogram)):
+                for on in (True, False):
+                    for _ in range(2):
+                        fn(on)
+                t = {True: [], False: []}
+                for _ in range(args.passes):
+                    for on in (True, False):
+                        t[on].append(timed(lambda: fn(on), args.iters))
+                for on, name in ((True, "on"), (False, "off")):
+                    line[f"{what}_{name}_ms"] = round(min(t[on]), 3)
+                    line[f"{what}_{name}_ms_range"] = [round(min(t[on]), 3), round(max(t[on]), 3)]
+                    line[f"{what}_{name}_ms_passes"] = [round(v, 3) for v in t[on]]
+                line[f"{what}_speedup"] = round(min(t[False]) / min(t[True]), 2)
+                line[f"{what}_every_pass_apart"] = max(t[True]) < min(t[False])
+            line["reprogram_fused_calls"] = m.reprogram_fused_calls
+            print(json.dumps(line), flush=True)
+            lines.append(json.dumps(line))
+        config.timellm_reprogram_fused = default
+    for prec in (() if (args.prompt or args.reprogram) else ("fp32", "bf16")):
         config.precision = prec
         line = {"tool": "timellm_bench", "precision": prec, "B": B, "layers": layers, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
                 "passes": args.passes}
