@@ -17,29 +17,19 @@
 //     key range summed over ALL the forward's queries in query order.  fp32 on the VALU, or all four products (S^T / dA^T and the two
 //     accumulations) on bf16 MFMA with fp32 softmax arithmetic and accumulators
 // One writer per output element, every sum in a fixed order, no atomics: two runs give the same bits.
+// The three fp32 VALU attention kernels are the non-CAUSAL instances of attn_dense64.hpp, which the GPT-2 body shares.
 #include "../../include/immtsf.h"
+#include "attn_dense64.hpp"
 #include "common.hpp"
 
 namespace {
 
-constexpr int HD = 64;           // head_dim
-constexpr int KT = 32;           // keys per LDS tile
-constexpr int KC = 4;            // keys per softmax chunk = keys per Philox call
-constexpr int ATT_STRIDE = 1024; // key stride of the attention-dropout index (= the largest S)
-constexpr int QT = 16;           // queries per LDS tile of the VALU dK / dV kernel
+using dense64::HD;               // head_dim 64
+using dense64::KT;               // 32 keys (or queries) per LDS tile, in the MFMA kernels as in the VALU ones
 constexpr int MQ = 32;           // rows (queries, or keys in the dK / dV kernel) a wave owns in the MFMA kernels
 constexpr int MW = 4;            // waves per workgroup of the MFMA kernels: they share the streamed tiles
 constexpr int RM_LD = HD + 8;    // bf16 tile, row-major [row][e]
 constexpr int TR_LD = KT + 8;    // bf16 tile, transposed [e][row]
-
-inline DropCfg mk_drop(float p, uint64_t seed) {
-    DropCfg d;
-    d.seed = seed;
-    d.p = p > 0.f ? p : 0.f;
-    d.inv_keep = d.p > 0.f ? 1.f / (1.f - d.p) : 1.f;
-    d.seed_dev = nullptr;
-    return d;
-}
 
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return float4{a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w}; }
 __device__ __forceinline__ bf16x4 to_bf4(float4 a) { return bf16x4{(bf16_t)a.x, (bf16_t)a.y, (bf16_t)a.z, (bf16_t)a.w}; }
@@ -201,267 +191,6 @@ __global__ void __launch_bounds__(256) bert_body_gelu_bwd_kernel(const float* __
         const float4 o = {g.x * gelu_erf_grad(v.x), g.y * gelu_erf_grad(v.y), g.z * gelu_erf_grad(v.z), g.w * gelu_erf_grad(v.w)};
         if (d32) reinterpret_cast<float4*>(d32)[i] = o;
         if (d16) reinterpret_cast<bf16x4*>(d16)[i] = to_bf4(o);
-    }
-}
-
-// ---- non-causal attention forward, fp32 on the VALU ---------------------------------------------------------------------------------------
-// one wave per 64 consecutive queries of one (b, head); a thread owns one query (q, the output row and the softmax state in registers),
-// K / V tiles of KT keys go through LDS and are read as broadcasts.  Query t (< Sq = S - q_from) is position q_from + t and its row in
-// q / out is b Sq + t; lse (B, H, Sq).  A key j >= S of the last tile scores -inf (key 0 is real, so the running maximum is finite).
-__global__ void __launch_bounds__(64) bert_body_attn_fwd_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
-                                                                const float* __restrict__ v, int ldkv, int S, int H, int q_from,
-                                                                float scale, DropCfg drop, uint64_t site, float* __restrict__ o32,
-                                                                bf16_t* __restrict__ o16, float* __restrict__ lse) {
-    __shared__ float4 Ks[KT * HD / 4];
-    __shared__ float4 Vs[KT * HD / 4];
-    const int Sq = S - q_from, lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int t0 = blockIdx.x * 64;
-    const bool live = t0 + lane < Sq;
-    const int t = live ? t0 + lane : Sq - 1;              // clamped: an idle lane repeats the last query and writes nothing
-    const int qi = q_from + t;
-    float qr[HD], acc[HD];
-    {
-        const float4* qp = reinterpret_cast<const float4*>(q + ((size_t)b * Sq + t) * ldq + h * HD);
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e) {
-            const float4 x = qp[e];
-            qr[4 * e] = x.x * scale; qr[4 * e + 1] = x.y * scale; qr[4 * e + 2] = x.z * scale; qr[4 * e + 3] = x.w * scale;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < HD; ++e) acc[e] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const size_t drow = (((size_t)b * H + h) * S + qi) * ATT_STRIDE;
-    for (int j0 = 0; j0 < S; j0 += KT) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KT * HD / 4 / 64; ++i) {
-            const int idx = lane + 64 * i, kk = idx >> 4, part = idx & 15, j = j0 + kk;
-            float4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
-            if (j < S) {
-                a = reinterpret_cast<const float4*>(k + ((size_t)b * S + j) * ldkv + h * HD)[part];
-                c = reinterpret_cast<const float4*>(v + ((size_t)b * S + j) * ldkv + h * HD)[part];
-            }
-            Ks[idx] = a;
-            Vs[idx] = c;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int c4 = 0; c4 < KT && j0 + c4 < S; c4 += KC) {
-            float sc[KC];
-            float cmax = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < KC; ++c) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 kk = Ks[(c4 + c) * (HD / 4) + e];
-                    a += qr[4 * e] * kk.x + qr[4 * e + 1] * kk.y + qr[4 * e + 2] * kk.z + qr[4 * e + 3] * kk.w;
-                }
-                sc[c] = (j0 + c4 + c < S) ? a : -INFINITY;
-                cmax = fmaxf(cmax, sc[c]);
-            }
-            if (cmax > m) {
-                const float corr = __expf(m - cmax);
-                m = cmax;
-                l *= corr;
-#pragma unroll
-                for (int e = 0; e < HD; ++e) acc[e] *= corr;
-            }
-            float ds[KC];
-            dropout_scale4(drop, site, drow + (size_t)(j0 + c4), ds);
-#pragma unroll
-            for (int c = 0; c < KC; ++c) {
-                const float p = __expf(sc[c] - m);
-                l += p;
-                const float pa = p * ds[c];
-#pragma unroll
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 vv = Vs[(c4 + c) * (HD / 4) + e];
-                    acc[4 * e] += pa * vv.x; acc[4 * e + 1] += pa * vv.y; acc[4 * e + 2] += pa * vv.z; acc[4 * e + 3] += pa * vv.w;
-                }
-            }
-        }
-    }
-    if (!live) return;
-    const float inv = 1.f / l;
-    const size_t orow = ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD;
-    if (o32) {
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e)
-            reinterpret_cast<float4*>(o32 + orow)[e] = float4{acc[4 * e] * inv, acc[4 * e + 1] * inv, acc[4 * e + 2] * inv, acc[4 * e + 3] * inv};
-    }
-    if (o16) {
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e)
-            reinterpret_cast<bf16x4*>(o16 + orow)[e] = bf16x4{(bf16_t)(acc[4 * e] * inv), (bf16_t)(acc[4 * e + 1] * inv),
-                                                             (bf16_t)(acc[4 * e + 2] * inv), (bf16_t)(acc[4 * e + 3] * inv)};
-    }
-    if (lse) lse[((size_t)b * H + h) * Sq + t] = m + __logf(l);
-}
-
-// ---- VALU backward: dQ of the queries dq_from .. S-1 against all keys ---------------------------------------------------------------------
-// q / dout / out / lse are the forward's (queries q_from .. S-1, q_from <= dq_from); dq row b dq_rows + (position - dq_from), pitch ldd.
-__global__ void __launch_bounds__(64) bert_body_attn_bwd_q_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
-                                                                  const float* __restrict__ v, int ldkv, const float* __restrict__ dout,
-                                                                  const float* __restrict__ out, const float* __restrict__ lse, int S, int H,
-                                                                  int q_from, int dq_from, float scale, DropCfg drop, uint64_t site,
-                                                                  float* __restrict__ dq, int dq_rows, int ldd) {
-    __shared__ float4 Ks[KT * HD / 4];
-    __shared__ float4 Vs[KT * HD / 4];
-    const int Sq = S - q_from, Sd = S - dq_from, lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int u0 = blockIdx.x * 64;
-    const bool live = u0 + lane < Sd;
-    const int u = live ? u0 + lane : Sd - 1;
-    const int qi = dq_from + u, t = qi - q_from;
-    float qr[HD], go[HD], acc[HD];
-    float D = 0.f;
-    {
-        const float4* qp = reinterpret_cast<const float4*>(q + ((size_t)b * Sq + t) * ldq + h * HD);
-        const float4* gp = reinterpret_cast<const float4*>(dout + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD);
-        const float4* op = reinterpret_cast<const float4*>(out + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD);
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e) {
-            const float4 x = qp[e], g = gp[e], o = op[e];
-            qr[4 * e] = x.x * scale; qr[4 * e + 1] = x.y * scale; qr[4 * e + 2] = x.z * scale; qr[4 * e + 3] = x.w * scale;
-            go[4 * e] = g.x; go[4 * e + 1] = g.y; go[4 * e + 2] = g.z; go[4 * e + 3] = g.w;
-            D += g.x * o.x + g.y * o.y + g.z * o.z + g.w * o.w;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < HD; ++e) acc[e] = 0.f;
-    const float L = lse[((size_t)b * H + h) * Sq + t];
-    const size_t drow = (((size_t)b * H + h) * S + qi) * ATT_STRIDE;
-    for (int j0 = 0; j0 < S; j0 += KT) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KT * HD / 4 / 64; ++i) {
-            const int idx = lane + 64 * i, kk = idx >> 4, part = idx & 15, j = j0 + kk;
-            float4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
-            if (j < S) {
-                a = reinterpret_cast<const float4*>(k + ((size_t)b * S + j) * ldkv + h * HD)[part];
-                c = reinterpret_cast<const float4*>(v + ((size_t)b * S + j) * ldkv + h * HD)[part];
-            }
-            Ks[idx] = a;
-            Vs[idx] = c;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int c4 = 0; c4 < KT && j0 + c4 < S; c4 += 4) {
-            float ds[4];
-            dropout_scale4(drop, site, drow + (size_t)(j0 + c4), ds);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float s = 0.f, dA = 0.f;
-#pragma unroll
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 kk = Ks[(c4 + c) * (HD / 4) + e], vv = Vs[(c4 + c) * (HD / 4) + e];
-                    s += qr[4 * e] * kk.x + qr[4 * e + 1] * kk.y + qr[4 * e + 2] * kk.z + qr[4 * e + 3] * kk.w;
-                    dA += go[4 * e] * vv.x + go[4 * e + 1] * vv.y + go[4 * e + 2] * vv.z + go[4 * e + 3] * vv.w;
-                }
-                const float p = (j0 + c4 + c < S) ? __expf(s - L) : 0.f;
-                const float dS = p * (ds[c] * dA - D);
-#pragma unroll
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 kk = Ks[(c4 + c) * (HD / 4) + e];
-                    acc[4 * e] += dS * kk.x; acc[4 * e + 1] += dS * kk.y; acc[4 * e + 2] += dS * kk.z; acc[4 * e + 3] += dS * kk.w;
-                }
-            }
-        }
-    }
-    if (!live) return;
-    float4* dp = reinterpret_cast<float4*>(dq + ((size_t)b * dq_rows + u) * ldd + h * HD);
-#pragma unroll
-    for (int e = 0; e < HD / 4; ++e) dp[e] = float4{acc[4 * e] * scale, acc[4 * e + 1] * scale, acc[4 * e + 2] * scale, acc[4 * e + 3] * scale};
-}
-
-// ---- VALU backward: dK / dV of the keys k_from .. S-1, summed over ALL the forward's queries q_from .. S-1 in query order -------------------
-// a thread owns key u (position k_from + u); the queries' q | dout rows, lse and D = dout . out go through LDS, QT at a time.
-// dk / dv row b dkv_rows + u, pitch ldd.
-__global__ void __launch_bounds__(64) bert_body_attn_bwd_kv_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
-                                                                   const float* __restrict__ v, int ldkv, const float* __restrict__ dout,
-                                                                   const float* __restrict__ out, const float* __restrict__ lse, int S, int H,
-                                                                   int q_from, int k_from, float scale, DropCfg drop, uint64_t site,
-                                                                   float* __restrict__ dk, float* __restrict__ dv, int dkv_rows, int ldd) {
-    __shared__ float4 Qs[QT * HD / 4];
-    __shared__ float4 Gs[QT * HD / 4];
-    __shared__ float Ls[QT], Ds[QT];
-    const int Sq = S - q_from, Sk = S - k_from, lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int u0 = blockIdx.x * 64;
-    const bool live = u0 + lane < Sk;
-    const int u = live ? u0 + lane : Sk - 1;
-    const int kj = k_from + u;
-    float kr[HD], vr[HD], ak[HD], av[HD];
-    {
-        const float4* kp = reinterpret_cast<const float4*>(k + ((size_t)b * S + kj) * ldkv + h * HD);
-        const float4* vp = reinterpret_cast<const float4*>(v + ((size_t)b * S + kj) * ldkv + h * HD);
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e) {
-            const float4 x = kp[e], y = vp[e];
-            kr[4 * e] = x.x; kr[4 * e + 1] = x.y; kr[4 * e + 2] = x.z; kr[4 * e + 3] = x.w;
-            vr[4 * e] = y.x; vr[4 * e + 1] = y.y; vr[4 * e + 2] = y.z; vr[4 * e + 3] = y.w;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < HD; ++e) { ak[e] = 0.f; av[e] = 0.f; }
-    for (int tq0 = 0; tq0 < Sq; tq0 += QT) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < QT * HD / 4 / 64; ++i) {
-            const int idx = lane + 64 * i, tt = idx >> 4, part = idx & 15, t = tq0 + tt;
-            float4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
-            if (t < Sq) {
-                a = reinterpret_cast<const float4*>(q + ((size_t)b * Sq + t) * ldq + h * HD)[part];
-                c = reinterpret_cast<const float4*>(dout + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD)[part];
-            }
-            Qs[idx] = a;
-            Gs[idx] = c;
-        }
-        if (lane < QT) {
-            const int t = tq0 + lane;
-            float L = 0.f, D = 0.f;
-            if (t < Sq) {
-                L = lse[((size_t)b * H + h) * Sq + t];
-                const float4* gp = reinterpret_cast<const float4*>(dout + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD);
-                const float4* op = reinterpret_cast<const float4*>(out + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD);
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 g = gp[e], o = op[e];
-                    D += g.x * o.x + g.y * o.y + g.z * o.z + g.w * o.w;
-                }
-            }
-            Ls[lane] = L;
-            Ds[lane] = D;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int c = 0; c < QT && tq0 + c < Sq; ++c) {
-            const int t = tq0 + c;
-            float s = 0.f, dA = 0.f;
-#pragma unroll
-            for (int e = 0; e < HD / 4; ++e) {
-                const float4 qq = Qs[c * (HD / 4) + e], gg = Gs[c * (HD / 4) + e];
-                s += kr[4 * e] * qq.x + kr[4 * e + 1] * qq.y + kr[4 * e + 2] * qq.z + kr[4 * e + 3] * qq.w;
-                dA += vr[4 * e] * gg.x + vr[4 * e + 1] * gg.y + vr[4 * e + 2] * gg.z + vr[4 * e + 3] * gg.w;
-            }
-            const float p = __expf(s * scale - Ls[c]);
-            const float dsc = dropout_scale(drop, site, (((size_t)b * H + h) * S + q_from + t) * ATT_STRIDE + (size_t)kj);
-            const float A = p * dsc;
-            const float dS = p * (dsc * dA - Ds[c]) * scale;
-#pragma unroll
-            for (int e = 0; e < HD / 4; ++e) {
-                const float4 qq = Qs[c * (HD / 4) + e], gg = Gs[c * (HD / 4) + e];
-                ak[4 * e] += dS * qq.x; ak[4 * e + 1] += dS * qq.y; ak[4 * e + 2] += dS * qq.z; ak[4 * e + 3] += dS * qq.w;
-                av[4 * e] += A * gg.x; av[4 * e + 1] += A * gg.y; av[4 * e + 2] += A * gg.z; av[4 * e + 3] += A * gg.w;
-            }
-        }
-    }
-    if (!live) return;
-    float4* dkp = reinterpret_cast<float4*>(dk + ((size_t)b * dkv_rows + u) * ldd + h * HD);
-    float4* dvp = reinterpret_cast<float4*>(dv + ((size_t)b * dkv_rows + u) * ldd + h * HD);
-#pragma unroll
-    for (int e = 0; e < HD / 4; ++e) {
-        dkp[e] = float4{ak[4 * e], ak[4 * e + 1], ak[4 * e + 2], ak[4 * e + 3]};
-        dvp[e] = float4{av[4 * e], av[4 * e + 1], av[4 * e + 2], av[4 * e + 3]};
     }
 }
 
@@ -839,12 +568,6 @@ __global__ void __launch_bounds__(64 * MW) bert_body_attn_bwd_kv_mfma_kernel(con
     }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-inline unsigned grid_for(size_t n, int per) {
-    const size_t g = (n + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : g > 65536 ? 65536 : g);
-}
 inline unsigned mfma_blocks(int S, int from) { return (unsigned)(((S + MQ - 1) / MQ - from / MQ + MW - 1) / MW); }
 
 int attn_args_ok(const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, int32_t B, int32_t S, int32_t H, int32_t q_from,
@@ -941,7 +664,7 @@ int immtsf_bert_body_attention_forward(const float* q, int32_t ldq, const float*
         hipLaunchKernelGGL(bert_body_attn_mfma_kernel, dim3((unsigned)B, (unsigned)H, mfma_blocks(S, q_from)), dim3(64 * MW), 0, s, q, ldq, k, v,
                            ldkv, S, H, q_from, scale, drop, site, out32, static_cast<bf16_t*>(out16), lse);
     else
-        hipLaunchKernelGGL(bert_body_attn_fwd_kernel, dim3((Sq + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, S, H, q_from, scale, drop,
+        hipLaunchKernelGGL(dense64::attn_fwd_kernel<false>, dim3((Sq + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, S, H, q_from, scale, drop,
                            site, out32, static_cast<bf16_t*>(out16), lse);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
@@ -971,10 +694,10 @@ int immtsf_bert_body_attention_backward(const float* q, int32_t ldq, const float
         IMMTSF_LAUNCH_CHECK();
         return IMMTSF_OK;
     }
-    hipLaunchKernelGGL(bert_body_attn_bwd_q_kernel, dim3((Sd + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, dout, out, lse, S, H, q_from,
+    hipLaunchKernelGGL(dense64::attn_bwd_q_kernel<false>, dim3((Sd + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, dout, out, lse, S, H, q_from,
                        dq_from, scale, drop, site, dq, dq_rows, ldd);
     IMMTSF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bert_body_attn_bwd_kv_kernel, dim3((Sk + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, dout, out, lse, S, H, q_from,
+    hipLaunchKernelGGL(dense64::attn_bwd_kv_kernel<false>, dim3((Sk + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, dout, out, lse, S, H, q_from,
                        k_from, scale, drop, site, dk, dv, dkv_rows, ldd);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;

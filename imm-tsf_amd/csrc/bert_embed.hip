@@ -121,12 +121,7 @@ __global__ void __launch_bounds__(256) bert_pool_kernel(const float* __restrict_
     pooled[(size_t)n * d + e] = acc / (float)(L > 1 ? L : 1);
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline unsigned grid_for(size_t n, int per) {
-    const size_t g = (n + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : g > 65536 ? 65536 : g);
-}
 
 }  // namespace
 
@@ -169,7 +164,7 @@ int immtsf_bert_embed_add_layernorm(const float* y, const float* x, int64_t rows
 
 int immtsf_bert_embed_gelu(const float* pre, uint64_t n, float* out32, void* out16, immtsf_stream_t stream) {
     if (!pre || (!out32 && !out16) || n == 0) return IMMTSF_EINVAL;
-    if ((n & 3) || !al16(pre) || (out32 && !al16(out32)) || (out16 && (reinterpret_cast<uintptr_t>(out16) & 7))) return IMMTSF_EUNSUPPORTED;
+    if ((n & 3) || !al16(pre) || (out32 && !al16(out32)) || (out16 && !al8(out16))) return IMMTSF_EUNSUPPORTED;
     hipLaunchKernelGGL(bert_gelu_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), pre, (size_t)(n / 4), out32,
                        static_cast<bf16_t*>(out16));
     IMMTSF_LAUNCH_CHECK();

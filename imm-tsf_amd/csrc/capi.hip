@@ -8,17 +8,6 @@
 #include "block_util.hpp"
 #include <atomic>
 
-namespace {
-inline DropCfg mk_drop(float p, uint64_t seed) {
-    DropCfg d;
-    d.seed = seed;
-    d.p = p > 0.f ? p : 0.f;
-    d.inv_keep = d.p > 0.f ? 1.f / (1.f - d.p) : 1.f;
-    d.seed_dev = nullptr;
-    return d;
-}
-}  // namespace
-
 namespace { std::atomic<int> g_side_enabled{0}; }   // measured slower under hipGraph replay at the cfg2 shapes (3.18 vs 2.64 ms/step): off by default
 
 extern "C" {

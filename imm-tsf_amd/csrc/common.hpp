@@ -191,6 +191,26 @@ __device__ __forceinline__ void dropout_scale4(const DropCfg& d, uint64_t site, 
     for (int e = 0; e < 4; ++e) s[e] = (float)(bits[e] >> 8) * (1.0f / 16777216.0f) >= d.p ? d.inv_keep : 0.f;
 }
 
+// ---- host-only helpers of the launchers ---------------------------------------------------------------
+inline DropCfg mk_drop(float p, uint64_t seed) {
+    DropCfg d;
+    d.seed = seed;
+    d.p = p > 0.f ? p : 0.f;
+    d.inv_keep = d.p > 0.f ? 1.f / (1.f - d.p) : 1.f;
+    d.seed_dev = nullptr;
+    return d;
+}
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+// blocks of a grid-stride launch over n items, `per` a block
+inline unsigned grid_for(size_t n, int per) {
+    const size_t g = (n + per - 1) / per;
+    return (unsigned)(g < 1 ? 1 : g > 65536 ? 65536 : g);
+}
+
+// key stride of the attention-dropout index ((b H + h) S + i) ATT_STRIDE + j of the frozen GPT-2 / BERT bodies (= their largest S)
+constexpr int ATT_STRIDE = 1024;
+
 // dropout sites (Philox subsequence ids) -- one per dropout call of the reference modules
 enum : uint64_t {
     SITE_T2V_ATTN = 1,   // fusions/TTF_T2V_XAttn.py:79-84  (attention-weight dropout inside MHA)

@@ -483,8 +483,6 @@ int launch2(int layout, const GemmArgs& g_in, int Mmax, int splits, hipStream_t 
 
 int g2_variant = 0, g2_splitk = 0, g2_xcd = -1;      // g2_xcd: -1 heuristic, 0 off, 1 contiguous ranges (1-D), 2 exact 2-D partition
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 static int g2_group_tile = 0;       // tile edge of the grouped weight-gradient launch: 0 = by tile count, 64 | 128 forced (tool switch: variant 1064 / 1128 / 1000)
@@ -529,7 +527,7 @@ int immtsf_launch_gemm2(int layout, GemmArgs& g, hipStream_t stream) {
     bool vc = (g.ldc % 4) == 0, vh = (ldch % 4) == 0, any_h = false, all_c = true;
     for (int i = 0; i < g.nprob; ++i) {
         if (g.p[i].C) vc = vc && al16(g.p[i].C); else all_c = false;
-        if (g.p[i].Ch) { any_h = true; vh = vh && ((reinterpret_cast<uintptr_t>(g.p[i].Ch) & 7) == 0); }
+        if (g.p[i].Ch) { any_h = true; vh = vh && al8(g.p[i].Ch); }
     }
     g.vecC = vc ? 1 : 0;
     g.vecB = vh ? 1 : 0;

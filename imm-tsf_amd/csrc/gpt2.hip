@@ -11,25 +11,15 @@
 //     (fp32 or bf16) and the statistics, residual + dropout, gelu_new (tanh form) and their backward forms over compact tail rows
 // The products go through the GEMM family (immtsf_gpt2_gemm: its launcher with split-K off, so that every sum has one order).
 // head_dim is 64; the arithmetic is fp32 on the VALU in either precision mode (bf16 mode differs in the GEMM operands only).
+// The three attention kernels are the CAUSAL instances of attn_dense64.hpp, which the BERT body shares.
 #include "../../include/immtsf.h"
+#include "attn_dense64.hpp"
 #include "block_util.hpp"
 #include "common.hpp"
 
 namespace {
 
-constexpr int HD = 64;           // head_dim
-constexpr int KT = 32;           // keys per LDS tile
-constexpr int KC = 4;            // keys per softmax chunk = keys per Philox call
-constexpr int ATT_STRIDE = 1024; // key stride of the attention-dropout index (= the largest S)
-
-inline DropCfg mk_drop(float p, uint64_t seed) {
-    DropCfg d;
-    d.seed = seed;
-    d.p = p > 0.f ? p : 0.f;
-    d.inv_keep = d.p > 0.f ? 1.f / (1.f - d.p) : 1.f;
-    d.seed_dev = nullptr;
-    return d;
-}
+using dense64::HD;
 
 __device__ __forceinline__ float gelu_new_f(float x) {
     const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
@@ -159,289 +149,6 @@ __global__ void __launch_bounds__(256) gpt2_gelu_bwd_kernel(const float* __restr
     }
 }
 
-// ---- causal attention forward ---------------------------------------------------------------------------------------------------------
-// one wave per 64 consecutive queries of one (b, head); a thread owns one query (q, the output row and the softmax state in registers),
-// K / V tiles of KT keys go through LDS and are read as broadcasts.  Query t (< Sq = S - q_from) is position q_from + t and its row in
-// q / out / lse is b Sq + t.
-__global__ void __launch_bounds__(64) gpt2_attn_fwd_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
-                                                           const float* __restrict__ v, int ldkv, int S, int H, int q_from, float scale,
-                                                           DropCfg drop, uint64_t site, float* __restrict__ o32, bf16_t* __restrict__ o16,
-                                                           float* __restrict__ lse) {
-    __shared__ float4 Ks[KT * HD / 4];
-    __shared__ float4 Vs[KT * HD / 4];
-    const int Sq = S - q_from, lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int t0 = blockIdx.x * 64;
-    const bool live = t0 + lane < Sq;
-    const int t = live ? t0 + lane : Sq - 1;              // clamped: an idle lane repeats the last query and writes nothing
-    const int qi = q_from + t;
-    float qr[HD], acc[HD];
-    {
-        const float4* qp = reinterpret_cast<const float4*>(q + ((size_t)b * Sq + t) * ldq + h * HD);
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e) {
-            const float4 x = qp[e];
-            qr[4 * e] = x.x * scale; qr[4 * e + 1] = x.y * scale; qr[4 * e + 2] = x.z * scale; qr[4 * e + 3] = x.w * scale;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < HD; ++e) acc[e] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const int t_hi = min(t0 + 63, Sq - 1);
-    const int kend = q_from + t_hi + 1;                   // keys 0 .. kend-1 are visible to some query of the wave (kend <= S)
-    const size_t drow = (((size_t)b * H + h) * S + qi) * ATT_STRIDE;
-    for (int j0 = 0; j0 < kend; j0 += KT) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KT * HD / 4 / 64; ++i) {
-            const int idx = lane + 64 * i, kk = idx >> 4, part = idx & 15, j = j0 + kk;
-            float4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
-            if (j < kend) {
-                a = reinterpret_cast<const float4*>(k + ((size_t)b * S + j) * ldkv + h * HD)[part];
-                c = reinterpret_cast<const float4*>(v + ((size_t)b * S + j) * ldkv + h * HD)[part];
-            }
-            Ks[idx] = a;
-            Vs[idx] = c;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int c4 = 0; c4 < KT && j0 + c4 < kend; c4 += KC) {
-            float sc[KC];
-            float cmax = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < KC; ++c) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 kk = Ks[(c4 + c) * (HD / 4) + e];
-                    a += qr[4 * e] * kk.x + qr[4 * e + 1] * kk.y + qr[4 * e + 2] * kk.z + qr[4 * e + 3] * kk.w;
-                }
-                sc[c] = (j0 + c4 + c <= qi) ? a : -INFINITY;
-                cmax = fmaxf(cmax, sc[c]);
-            }
-            // (the running maximum is finite from the first chunk on: key 0 is visible to every query; it rarely grows later, so the
-            // rescale of the output row is a branch most chunks skip)
-            if (cmax > m) {
-                const float corr = __expf(m - cmax);
-                m = cmax;
-                l *= corr;
-#pragma unroll
-                for (int e = 0; e < HD; ++e) acc[e] *= corr;
-            }
-            float ds[KC];
-            dropout_scale4(drop, site, drow + (size_t)(j0 + c4), ds);
-#pragma unroll
-            for (int c = 0; c < KC; ++c) {
-                const float p = __expf(sc[c] - m);
-                l += p;
-                const float pa = p * ds[c];
-#pragma unroll
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 vv = Vs[(c4 + c) * (HD / 4) + e];
-                    acc[4 * e] += pa * vv.x; acc[4 * e + 1] += pa * vv.y; acc[4 * e + 2] += pa * vv.z; acc[4 * e + 3] += pa * vv.w;
-                }
-            }
-        }
-    }
-    if (!live) return;
-    const float inv = 1.f / l;
-    const size_t orow = ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD;
-    if (o32) {
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e) {
-            const float4 o = {acc[4 * e] * inv, acc[4 * e + 1] * inv, acc[4 * e + 2] * inv, acc[4 * e + 3] * inv};
-            reinterpret_cast<float4*>(o32 + orow)[e] = o;
-        }
-    }
-    if (o16) {
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e) {
-            const bf16x4 o = {(bf16_t)(acc[4 * e] * inv), (bf16_t)(acc[4 * e + 1] * inv), (bf16_t)(acc[4 * e + 2] * inv),
-                              (bf16_t)(acc[4 * e + 3] * inv)};
-            reinterpret_cast<bf16x4*>(o16 + orow)[e] = o;
-        }
-    }
-    if (lse) lse[((size_t)b * H + h) * Sq + t] = m + __logf(l);
-}
-
-// ---- backward, tail queries: dQ against all keys ---------------------------------------------------------------------------------------
-// q / dout / out: the tail queries' rows b S_t + t (pitch ldq for q, H 64 for dout / out); lse (B, H, S_t); dq row pitch ldd.
-__global__ void __launch_bounds__(64) gpt2_attn_bwd_q_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
-                                                             const float* __restrict__ v, int ldkv, const float* __restrict__ dout,
-                                                             const float* __restrict__ out, const float* __restrict__ lse, int S, int H,
-                                                             int q_from, float scale, DropCfg drop, uint64_t site, float* __restrict__ dq,
-                                                             int ldd) {
-    __shared__ float4 Ks[KT * HD / 4];
-    __shared__ float4 Vs[KT * HD / 4];
-    const int Sq = S - q_from, lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int t0 = blockIdx.x * 64;
-    const bool live = t0 + lane < Sq;
-    const int t = live ? t0 + lane : Sq - 1;
-    const int qi = q_from + t;
-    float qr[HD], go[HD], acc[HD];
-    float D = 0.f;
-    {
-        const float4* qp = reinterpret_cast<const float4*>(q + ((size_t)b * Sq + t) * ldq + h * HD);
-        const float4* gp = reinterpret_cast<const float4*>(dout + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD);
-        const float4* op = reinterpret_cast<const float4*>(out + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD);
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e) {
-            const float4 x = qp[e], g = gp[e], o = op[e];
-            qr[4 * e] = x.x * scale; qr[4 * e + 1] = x.y * scale; qr[4 * e + 2] = x.z * scale; qr[4 * e + 3] = x.w * scale;
-            go[4 * e] = g.x; go[4 * e + 1] = g.y; go[4 * e + 2] = g.z; go[4 * e + 3] = g.w;
-            D += g.x * o.x + g.y * o.y + g.z * o.z + g.w * o.w;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < HD; ++e) acc[e] = 0.f;
-    const float L = lse[((size_t)b * H + h) * Sq + t];
-    const int t_hi = min(t0 + 63, Sq - 1);
-    const int kend = q_from + t_hi + 1;
-    const size_t drow = (((size_t)b * H + h) * S + qi) * ATT_STRIDE;
-    for (int j0 = 0; j0 < kend; j0 += KT) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KT * HD / 4 / 64; ++i) {
-            const int idx = lane + 64 * i, kk = idx >> 4, part = idx & 15, j = j0 + kk;
-            float4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
-            if (j < kend) {
-                a = reinterpret_cast<const float4*>(k + ((size_t)b * S + j) * ldkv + h * HD)[part];
-                c = reinterpret_cast<const float4*>(v + ((size_t)b * S + j) * ldkv + h * HD)[part];
-            }
-            Ks[idx] = a;
-            Vs[idx] = c;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int c4 = 0; c4 < KT && j0 + c4 < kend; c4 += 4) {
-            float ds[4];
-            dropout_scale4(drop, site, drow + (size_t)(j0 + c4), ds);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                float s = 0.f, dA = 0.f;
-#pragma unroll
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 kk = Ks[(c4 + c) * (HD / 4) + e], vv = Vs[(c4 + c) * (HD / 4) + e];
-                    s += qr[4 * e] * kk.x + qr[4 * e + 1] * kk.y + qr[4 * e + 2] * kk.z + qr[4 * e + 3] * kk.w;
-                    dA += go[4 * e] * vv.x + go[4 * e + 1] * vv.y + go[4 * e + 2] * vv.z + go[4 * e + 3] * vv.w;
-                }
-                const float p = (j0 + c4 + c <= qi) ? __expf(s - L) : 0.f;
-                const float dS = p * (ds[c] * dA - D);
-#pragma unroll
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 kk = Ks[(c4 + c) * (HD / 4) + e];
-                    acc[4 * e] += dS * kk.x; acc[4 * e + 1] += dS * kk.y; acc[4 * e + 2] += dS * kk.z; acc[4 * e + 3] += dS * kk.w;
-                }
-            }
-        }
-    }
-    if (!live) return;
-    float4* dp = reinterpret_cast<float4*>(dq + ((size_t)b * Sq + t) * ldd + h * HD);
-#pragma unroll
-    for (int e = 0; e < HD / 4; ++e) {
-        const float4 o = {acc[4 * e] * scale, acc[4 * e + 1] * scale, acc[4 * e + 2] * scale, acc[4 * e + 3] * scale};
-        dp[e] = o;
-    }
-}
-
-// ---- backward, tail keys: dK / dV from the tail queries (no other query sees a tail key) --------------------------------------------------
-// a thread owns tail key u (position q_from + u); the queries' q | dout rows, lse and D = dout . out go through LDS, QT at a time.
-constexpr int QT = 16;
-__global__ void __launch_bounds__(64) gpt2_attn_bwd_kv_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
-                                                              const float* __restrict__ v, int ldkv, const float* __restrict__ dout,
-                                                              const float* __restrict__ out, const float* __restrict__ lse, int S, int H,
-                                                              int q_from, float scale, DropCfg drop, uint64_t site, float* __restrict__ dk,
-                                                              float* __restrict__ dv, int ldd) {
-    __shared__ float4 Qs[QT * HD / 4];
-    __shared__ float4 Gs[QT * HD / 4];
-    __shared__ float Ls[QT], Ds[QT];
-    const int Sq = S - q_from, lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z;
-    const int u0 = blockIdx.x * 64;
-    const bool live = u0 + lane < Sq;
-    const int u = live ? u0 + lane : Sq - 1;
-    const int kj = q_from + u;
-    float kr[HD], vr[HD], ak[HD], av[HD];
-    {
-        const float4* kp = reinterpret_cast<const float4*>(k + ((size_t)b * S + kj) * ldkv + h * HD);
-        const float4* vp = reinterpret_cast<const float4*>(v + ((size_t)b * S + kj) * ldkv + h * HD);
-#pragma unroll
-        for (int e = 0; e < HD / 4; ++e) {
-            const float4 x = kp[e], y = vp[e];
-            kr[4 * e] = x.x; kr[4 * e + 1] = x.y; kr[4 * e + 2] = x.z; kr[4 * e + 3] = x.w;
-            vr[4 * e] = y.x; vr[4 * e + 1] = y.y; vr[4 * e + 2] = y.z; vr[4 * e + 3] = y.w;
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < HD; ++e) { ak[e] = 0.f; av[e] = 0.f; }
-    // queries t >= u0 (earlier ones see no key of this wave), in index order
-    for (int tq0 = u0; tq0 < Sq; tq0 += QT) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < QT * HD / 4 / 64; ++i) {
-            const int idx = lane + 64 * i, tt = idx >> 4, part = idx & 15, t = tq0 + tt;
-            float4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
-            if (t < Sq) {
-                a = reinterpret_cast<const float4*>(q + ((size_t)b * Sq + t) * ldq + h * HD)[part];
-                c = reinterpret_cast<const float4*>(dout + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD)[part];
-            }
-            Qs[idx] = a;
-            Gs[idx] = c;
-        }
-        if (lane < QT) {
-            const int t = tq0 + lane;
-            float L = 0.f, D = 0.f;
-            if (t < Sq) {
-                L = lse[((size_t)b * H + h) * Sq + t];
-                const float4* gp = reinterpret_cast<const float4*>(dout + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD);
-                const float4* op = reinterpret_cast<const float4*>(out + ((size_t)b * Sq + t) * ((size_t)H * HD) + h * HD);
-                for (int e = 0; e < HD / 4; ++e) {
-                    const float4 g = gp[e], o = op[e];
-                    D += g.x * o.x + g.y * o.y + g.z * o.z + g.w * o.w;
-                }
-            }
-            Ls[lane] = L;
-            Ds[lane] = D;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int c = 0; c < QT && tq0 + c < Sq; ++c) {
-            const int t = tq0 + c;
-            float s = 0.f, dA = 0.f;
-#pragma unroll
-            for (int e = 0; e < HD / 4; ++e) {
-                const float4 qq = Qs[c * (HD / 4) + e], gg = Gs[c * (HD / 4) + e];
-                s += kr[4 * e] * qq.x + kr[4 * e + 1] * qq.y + kr[4 * e + 2] * qq.z + kr[4 * e + 3] * qq.w;
-                dA += vr[4 * e] * gg.x + vr[4 * e + 1] * gg.y + vr[4 * e + 2] * gg.z + vr[4 * e + 3] * gg.w;
-            }
-            const float p = (u <= t) ? __expf(s * scale - Ls[c]) : 0.f;
-            const float dsc = dropout_scale(drop, site, (((size_t)b * H + h) * S + q_from + t) * ATT_STRIDE + (size_t)kj);
-            const float A = p * dsc;
-            const float dS = p * (dsc * dA - Ds[c]) * scale;
-#pragma unroll
-            for (int e = 0; e < HD / 4; ++e) {
-                const float4 qq = Qs[c * (HD / 4) + e], gg = Gs[c * (HD / 4) + e];
-                ak[4 * e] += dS * qq.x; ak[4 * e + 1] += dS * qq.y; ak[4 * e + 2] += dS * qq.z; ak[4 * e + 3] += dS * qq.w;
-                av[4 * e] += A * gg.x; av[4 * e + 1] += A * gg.y; av[4 * e + 2] += A * gg.z; av[4 * e + 3] += A * gg.w;
-            }
-        }
-    }
-    if (!live) return;
-    float4* dkp = reinterpret_cast<float4*>(dk + ((size_t)b * Sq + u) * ldd + h * HD);
-    float4* dvp = reinterpret_cast<float4*>(dv + ((size_t)b * Sq + u) * ldd + h * HD);
-#pragma unroll
-    for (int e = 0; e < HD / 4; ++e) {
-        const float4 a = {ak[4 * e], ak[4 * e + 1], ak[4 * e + 2], ak[4 * e + 3]};
-        const float4 c = {av[4 * e], av[4 * e + 1], av[4 * e + 2], av[4 * e + 3]};
-        dkp[e] = a;
-        dvp[e] = c;
-    }
-}
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline unsigned grid_for(size_t n, int per) {
-    const size_t g = (n + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : g > 65536 ? 65536 : g);
-}
-
 }  // namespace
 
 extern "C" {
@@ -507,7 +214,7 @@ int immtsf_gpt2_residual(const float* xin, int32_t B, int32_t S_in, int32_t s_of
 
 int immtsf_gpt2_gelu(const float* pre, uint64_t n, float* out32, void* out16, immtsf_stream_t stream) {
     if (!pre || (!out32 && !out16) || n == 0) return IMMTSF_EINVAL;
-    if ((n & 3) || !al16(pre) || (out32 && !al16(out32)) || (out16 && (reinterpret_cast<uintptr_t>(out16) & 7))) return IMMTSF_EUNSUPPORTED;
+    if ((n & 3) || !al16(pre) || (out32 && !al16(out32)) || (out16 && !al8(out16))) return IMMTSF_EUNSUPPORTED;
     hipLaunchKernelGGL(gpt2_gelu_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), pre, (size_t)(n / 4), out32,
                        static_cast<bf16_t*>(out16));
     IMMTSF_LAUNCH_CHECK();
@@ -536,10 +243,10 @@ int immtsf_gpt2_attention_forward(const float* q, int32_t ldq, const float* k, c
                                   float* lse, immtsf_stream_t stream) {
     if (int rc = attn_args_ok(q, ldq, k, v, ldkv, B, S, H, q_from)) return rc;
     if (!out32 && !out16) return IMMTSF_EINVAL;
-    if ((out32 && !al16(out32)) || (out16 && (reinterpret_cast<uintptr_t>(out16) & 7))) return IMMTSF_EUNSUPPORTED;
+    if ((out32 && !al16(out32)) || (out16 && !al8(out16))) return IMMTSF_EUNSUPPORTED;
     const int Sq = S - q_from;
-    hipLaunchKernelGGL(gpt2_attn_fwd_kernel, dim3((Sq + 63) / 64, H, B), dim3(64), 0, static_cast<hipStream_t>(stream), q, ldq, k, v, ldkv, S, H,
-                       q_from, scale, mk_drop(p_drop, seed), site, out32, static_cast<bf16_t*>(out16), lse);
+    hipLaunchKernelGGL(dense64::attn_fwd_kernel<true>, dim3((Sq + 63) / 64, H, B), dim3(64), 0, static_cast<hipStream_t>(stream), q, ldq, k, v,
+                       ldkv, S, H, q_from, scale, mk_drop(p_drop, seed), site, out32, static_cast<bf16_t*>(out16), lse);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
 }
@@ -554,11 +261,12 @@ int immtsf_gpt2_attention_backward(const float* q, int32_t ldq, const float* k, 
     const int Sq = S - q_from;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const DropCfg drop = mk_drop(p_drop, seed);
-    hipLaunchKernelGGL(gpt2_attn_bwd_q_kernel, dim3((Sq + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, dout, out, lse, S, H, q_from,
-                       scale, drop, site, dq, ldd);
+    // the shared kernels take a sub-range of the forward's queries / keys: here it is the whole tail (dq_from = k_from = q_from)
+    hipLaunchKernelGGL(dense64::attn_bwd_q_kernel<true>, dim3((Sq + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, dout, out, lse, S, H,
+                       q_from, q_from, scale, drop, site, dq, Sq, ldd);
     IMMTSF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gpt2_attn_bwd_kv_kernel, dim3((Sq + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, dout, out, lse, S, H, q_from,
-                       scale, drop, site, dk, dv, ldd);
+    hipLaunchKernelGGL(dense64::attn_bwd_kv_kernel<true>, dim3((Sq + 63) / 64, H, B), dim3(64), 0, s, q, ldq, k, v, ldkv, dout, out, lse, S, H,
+                       q_from, q_from, scale, drop, site, dk, dv, Sq, ldd);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
 }

@@ -9,25 +9,23 @@
 //   * RoPE over dense rows, in place, position pos0 + (row mod rows_per_b), forward or transposed (the backward: the rotation by the
 //     negated angle, same cos / sin table); optionally the bf16 image of the whole row for the next bf16-in-memory product
 //   * causal attention forward with a query offset q_from (the last layer computes the tail queries only): the kernels of
-//     llama_embed.hip over dense sequences -- fp32 on the VALU, or both products on bf16 MFMA 16x16x32 with fp32 online softmax -- that
-//     also write the per-(row, head) log-sum-exp.  Query tiles of 32 stay aligned to absolute positions, as the key tiles are
+//     attn_gqa128.hpp, which llama_embed.hip shares, over dense sequences -- fp32 on the VALU, or both products on bf16 MFMA 16x16x32
+//     with fp32 online softmax -- that also write the per-(row, head) log-sum-exp
 //   * its backward for the tail queries, fp32 on the VALU in either precision mode: probabilities recomputed from the log-sum-exp; dK and
 //     dV of a K/V head sum over its G query heads in head order, then in query order: one writer per output element, no atomics
 //   * SwiGLU backward: dgate | dup in one buffer from the saved gate | up product
 // No dropout (Llama has none but attention_dropout, which the caller keeps on the stock path).  Two runs give the same bits.
 #include "../../include/immtsf.h"
+#include "attn_gqa128.hpp"
 #include "common.hpp"
 
 namespace {
 
-constexpr int HD = 128;       // head_dim
+using gqa128::HD;             // head_dim 128
+using gqa128::QT;             // 32 queries per wave
+using gqa128::KT;             // 32 keys per LDS tile
 constexpr int HP = HD / 2;    // rotary pairs of a head
-constexpr int QT = 32;        // queries per wave
-constexpr int KT = 32;        // keys per LDS tile
-constexpr int KC = 4;         // keys per softmax chunk of the VALU form
 constexpr int MAXS = 1024;    // longest sequence
-constexpr int KS_LD = HD + 8; // bf16 K tile [key][e]
-constexpr int VT_LD = KT + 8; // bf16 V tile transposed [e][key]
 constexpr int UT = 16;        // tail keys per wave of the dK / dV kernel (four lanes a key)
 constexpr int QB = 16;        // queries per LDS tile of the dK / dV kernel
 
@@ -133,232 +131,26 @@ __global__ void __launch_bounds__(256) llama_body_rope_kernel(float* __restrict_
         for (int e = heads * HD + lane; e < ld; e += 64) img[e] = (bf16_t)row[e];
 }
 
-// ---- dense causal attention forward, fp32 on the VALU -------------------------------------------------------------------------------------
-// grid (b, K/V head, query tile REVERSED); wave w of the workgroup is query head G kvh + w.  A query tile is the 32 absolute positions
-// t0 .. t0 + 31 (aligned, like the key tiles); a position below q_from or at / past S is idle: it repeats a live query and writes nothing.
-// Query position p is row b Sq + p - q_from of q / out / lse (Sq = S - q_from).  Two lanes own one query, as in llama_embed.hip.
-template <int G>
-__global__ void __launch_bounds__(64 * G) llama_body_attn_valu_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
-                                                                      const float* __restrict__ v, int ldkv, int S, int H, int q_from,
-                                                                      int tiles, float scale, float* __restrict__ o32,
-                                                                      bf16_t* __restrict__ o16, float* __restrict__ lse) {
-    __shared__ float4 Ks[KT * HD / 4];
-    __shared__ float4 Vs[KT * HD / 4];
-    const int tid = threadIdx.x, lane = tid & 63, qi = lane >> 1, hf = lane & 1;
-    const int b = blockIdx.x, kvh = blockIdx.y, h = kvh * G + (tid >> 6);
-    const int t0 = (tiles - 1 - (int)blockIdx.z) * QT;
-    if (t0 >= S || t0 + QT <= q_from) return;
-    const int Sq = S - q_from, dq = H * HD;
-    const int pn = t0 + qi;                                  // the nominal position: what the causal bound reads
-    const bool live = pn >= q_from && pn < S;
-    const int pc = pn < q_from ? q_from : pn >= S ? S - 1 : pn;
-    const size_t qrow = (size_t)b * Sq + (pc - q_from);
-    const float* kb = k + (size_t)b * S * ldkv + kvh * HD;
-    const float* vb = v + (size_t)b * S * ldkv + kvh * HD;
-    float qr[HD / 2], acc[HD / 2];
-    {
-        const float4* qp = reinterpret_cast<const float4*>(q + qrow * ldq + h * HD + (HD / 2) * hf);
-#pragma unroll
-        for (int e = 0; e < HD / 8; ++e) {
-            const float4 x = qp[e];
-            qr[4 * e] = x.x * scale; qr[4 * e + 1] = x.y * scale; qr[4 * e + 2] = x.z * scale; qr[4 * e + 3] = x.w * scale;
-        }
+// ---- dense causal attention forward: the kernels of attn_gqa128.hpp over these rows -------------------------------------------------------
+// grid (b, K/V head, query tile REVERSED out of `tiles`).  Query position p >= q_from is row b Sq + p - q_from of q / out / lse
+// (Sq = S - q_from); a tile that lies wholly below q_from or past S is empty.
+struct DenseRows {
+    const float *q, *k, *v;
+    int ldq, ldkv, S, q_from, tiles;
+    float* lse;
+    struct Tile {
+        const float *q, *k, *v;
+        int ldq, ldkv, t0, from, S;
+        size_t row0;
+        float* lse;
+        bool empty;
+    };
+    __device__ __forceinline__ Tile tile(int) const {
+        const int b = blockIdx.x, kvh = blockIdx.y, t0 = (tiles - 1 - (int)blockIdx.z) * QT;
+        return Tile{q, k + (size_t)b * S * ldkv + kvh * HD, v + (size_t)b * S * ldkv + kvh * HD, ldq, ldkv, t0, q_from, S,
+                    (size_t)b * (S - q_from), lse, t0 >= S || t0 + QT <= q_from};
     }
-#pragma unroll
-    for (int e = 0; e < HD / 2; ++e) acc[e] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    const int kend = min(t0 + QT, S);
-    for (int j0 = 0; j0 < kend; j0 += KT) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < KT * HD / 4 / (64 * G); ++i) {
-            const int idx = tid + 64 * G * i, kk = idx >> 5, part = idx & 31, j = j0 + kk;
-            float4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
-            if (j < kend) {
-                a = reinterpret_cast<const float4*>(kb + (size_t)j * ldkv)[part];
-                c = reinterpret_cast<const float4*>(vb + (size_t)j * ldkv)[part];
-            }
-            Ks[idx] = a;
-            Vs[idx] = c;
-        }
-        __syncthreads();
-#pragma unroll 1
-        for (int c4 = 0; c4 < KT && j0 + c4 < kend; c4 += KC) {
-            float sc[KC];
-            float cmax = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < KC; ++c) {
-                float a = 0.f;
-#pragma unroll
-                for (int e = 0; e < HD / 8; ++e) {
-                    const float4 kk = Ks[(c4 + c) * (HD / 4) + (HD / 8) * hf + e];
-                    a += qr[4 * e] * kk.x + qr[4 * e + 1] * kk.y + qr[4 * e + 2] * kk.z + qr[4 * e + 3] * kk.w;
-                }
-                a += IMMTSF_DPP(a, 0xB1);                   // the other half of the head
-                sc[c] = (j0 + c4 + c <= pn) ? a : -INFINITY;
-                cmax = fmaxf(cmax, sc[c]);
-            }
-            if (cmax > m) {                                 // (finite from the first chunk on: key 0 is visible to every query)
-                const float corr = __expf(m - cmax);
-                m = cmax;
-                l *= corr;
-#pragma unroll
-                for (int e = 0; e < HD / 2; ++e) acc[e] *= corr;
-            }
-#pragma unroll
-            for (int c = 0; c < KC; ++c) {
-                const float p = __expf(sc[c] - m);
-                l += p;
-#pragma unroll
-                for (int e = 0; e < HD / 8; ++e) {
-                    const float4 vv = Vs[(c4 + c) * (HD / 4) + (HD / 8) * hf + e];
-                    acc[4 * e] += p * vv.x; acc[4 * e + 1] += p * vv.y; acc[4 * e + 2] += p * vv.z; acc[4 * e + 3] += p * vv.w;
-                }
-            }
-        }
-    }
-    if (!live) return;
-    const float inv = 1.f / l;
-    const size_t orow = qrow * dq + h * HD + (HD / 2) * hf;
-    if (o32) {
-#pragma unroll
-        for (int e = 0; e < HD / 8; ++e)
-            reinterpret_cast<float4*>(o32 + orow)[e] = float4{acc[4 * e] * inv, acc[4 * e + 1] * inv, acc[4 * e + 2] * inv, acc[4 * e + 3] * inv};
-    }
-    if (o16) {
-#pragma unroll
-        for (int e = 0; e < HD / 8; ++e)
-            reinterpret_cast<bf16x4*>(o16 + orow)[e] = bf16x4{(bf16_t)(acc[4 * e] * inv), (bf16_t)(acc[4 * e + 1] * inv),
-                                                             (bf16_t)(acc[4 * e + 2] * inv), (bf16_t)(acc[4 * e + 3] * inv)};
-    }
-    if (lse && hf == 0) lse[qrow * H + h] = m + __logf(l);
-}
-
-// ---- dense causal attention forward, bf16 MFMA: llama_embed.hip's transposed form (S^T = K Q^T, O^T += V^T P^T) with the query offset ------
-__device__ __forceinline__ f32x4 lb_mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
-template <int G>
-__global__ void __launch_bounds__(64 * G) llama_body_attn_mfma_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ k,
-                                                                      const float* __restrict__ v, int ldkv, int S, int H, int q_from,
-                                                                      int tiles, float scale, float* __restrict__ o32,
-                                                                      bf16_t* __restrict__ o16, float* __restrict__ lse) {
-    __shared__ __attribute__((aligned(16))) bf16_t Ks[KT * KS_LD];
-    __shared__ __attribute__((aligned(16))) bf16_t Vt[HD * VT_LD];
-    const int tid = threadIdx.x, lane = tid & 63, fr = lane & 15, g = lane >> 4;
-    const int b = blockIdx.x, kvh = blockIdx.y, h = kvh * G + (tid >> 6);
-    const int t0 = (tiles - 1 - (int)blockIdx.z) * QT;
-    if (t0 >= S || t0 + QT <= q_from) return;
-    const int Sq = S - q_from, dq = H * HD;
-    const float* kb = k + (size_t)b * S * ldkv + kvh * HD;
-    const float* vb = v + (size_t)b * S * ldkv + kvh * HD;
-    bf16x8 qf[2][4];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const int pn = t0 + 16 * mt + fr;
-        const int pc = pn < q_from ? q_from : pn >= S ? S - 1 : pn;      // an idle query repeats a live one and is not written
-        const float4* qp = reinterpret_cast<const float4*>(q + ((size_t)b * Sq + (pc - q_from)) * ldq + h * HD);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const float4 a = qp[8 * ks + 2 * g], c = qp[8 * ks + 2 * g + 1];
-            qf[mt][ks] = bf16x8{(bf16_t)a.x, (bf16_t)a.y, (bf16_t)a.z, (bf16_t)a.w, (bf16_t)c.x, (bf16_t)c.y, (bf16_t)c.z, (bf16_t)c.w};
-        }
-    }
-    f32x4 O[2][8];
-    float m[2], ls[2];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        m[mt] = -INFINITY;
-        ls[mt] = 0.f;
-#pragma unroll
-        for (int et = 0; et < 8; ++et) O[mt][et] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const int kend = min(t0 + QT, S);
-    for (int j0 = 0; j0 < kend; j0 += KT) {
-        __syncthreads();
-#pragma unroll 4
-        for (int i = 0; i < KT * HD / 4 / (64 * G); ++i) {
-            const int idx = tid + 64 * G * i, kk = idx >> 5, part = idx & 31, j = j0 + kk;
-            float4 a = {0.f, 0.f, 0.f, 0.f}, c = a;
-            if (j < kend) {
-                a = reinterpret_cast<const float4*>(kb + (size_t)j * ldkv)[part];
-                c = reinterpret_cast<const float4*>(vb + (size_t)j * ldkv)[part];
-            }
-            *reinterpret_cast<bf16x4*>(&Ks[kk * KS_LD + 4 * part]) = bf16x4{(bf16_t)a.x, (bf16_t)a.y, (bf16_t)a.z, (bf16_t)a.w};
-            Vt[(4 * part + 0) * VT_LD + kk] = (bf16_t)c.x;
-            Vt[(4 * part + 1) * VT_LD + kk] = (bf16_t)c.y;
-            Vt[(4 * part + 2) * VT_LD + kk] = (bf16_t)c.z;
-            Vt[(4 * part + 3) * VT_LD + kk] = (bf16_t)c.w;
-        }
-        __syncthreads();
-        bf16x8 kf[2][4], vf[8];
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) kf[nt][ks] = *reinterpret_cast<const bf16x8*>(&Ks[(16 * nt + fr) * KS_LD + 32 * ks + 8 * g]);
-#pragma unroll
-        for (int et = 0; et < 8; ++et) {
-            const bf16x4 lo = *reinterpret_cast<const bf16x4*>(&Vt[(16 * et + fr) * VT_LD + 4 * g]);
-            const bf16x4 hi = *reinterpret_cast<const bf16x4*>(&Vt[(16 * et + fr) * VT_LD + 16 + 4 * g]);
-            vf[et] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            const int qi = t0 + 16 * mt + fr;               // the last key this lane's query sees (>= j0: the tiles are aligned)
-            float s[2][4];
-            float cmax = -INFINITY;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                f32x4 Sc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) Sc = lb_mfma(kf[nt][ks], qf[mt][ks], Sc);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    s[nt][i] = (j0 + 16 * nt + 4 * g + i <= qi) ? Sc[i] * scale : -INFINITY;
-                    cmax = fmaxf(cmax, s[nt][i]);
-                }
-            }
-            cmax = xor32_max(xor16_max(cmax));
-            const float mn = fmaxf(m[mt], cmax);
-            const float corr = __expf(m[mt] - mn);
-            m[mt] = mn;
-            float psum = 0.f;
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    s[nt][i] = __expf(s[nt][i] - mn);
-                    psum += s[nt][i];
-                }
-            ls[mt] = ls[mt] * corr + psum;
-            const bf16x8 pf = bf16x8{(bf16_t)s[0][0], (bf16_t)s[0][1], (bf16_t)s[0][2], (bf16_t)s[0][3],
-                                     (bf16_t)s[1][0], (bf16_t)s[1][1], (bf16_t)s[1][2], (bf16_t)s[1][3]};
-#pragma unroll
-            for (int et = 0; et < 8; ++et) {
-                f32x4 o = O[mt][et];
-                o[0] *= corr; o[1] *= corr; o[2] *= corr; o[3] *= corr;
-                O[mt][et] = lb_mfma(vf[et], pf, o);
-            }
-        }
-    }
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-        const float l = xor32_sum(xor16_sum(ls[mt]));        // shares of lanes fr, fr + 16, fr + 32, fr + 48 in one fixed order
-        const int pn = t0 + 16 * mt + fr;
-        if (pn < q_from || pn >= S) continue;
-        const float inv = 1.f / l;
-        const size_t qrow = (size_t)b * Sq + (pn - q_from);
-        const size_t orow = qrow * dq + h * HD + 4 * g;
-#pragma unroll
-        for (int et = 0; et < 8; ++et) {
-            const f32x4 o = O[mt][et];
-            if (o32) *reinterpret_cast<float4*>(o32 + orow + 16 * et) = float4{o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv};
-            if (o16)
-                *reinterpret_cast<bf16x4*>(o16 + orow + 16 * et) =
-                    bf16x4{(bf16_t)(o[0] * inv), (bf16_t)(o[1] * inv), (bf16_t)(o[2] * inv), (bf16_t)(o[3] * inv)};
-        }
-        if (lse && g == 0) lse[qrow * H + h] = m[mt] + __logf(l);
-    }
-}
+};
 
 // ---- backward, tail queries: dQ against all keys --------------------------------------------------------------------------------------------
 // grid (b, head, query tile), one wave: 32 aligned positions, two lanes a query (head columns 64 hf .. 64 hf + 63 of q, dout and dq in
@@ -570,12 +362,6 @@ __global__ void __launch_bounds__(256) llama_body_swiglu_bwd_kernel(const float*
     }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool al8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-inline unsigned grid_for(size_t n, int per) {
-    const size_t g = (n + per - 1) / per;
-    return (unsigned)(g < 1 ? 1 : g > 65536 ? 65536 : g);
-}
 inline bool group_ok(int H, int Hkv) {
     if (H <= 0 || Hkv <= 0 || H % Hkv) return false;
     const int G = H / Hkv;
@@ -593,12 +379,11 @@ int attn_args_ok(const float* q, int32_t ldq, const float* k, const float* v, in
 template <int G>
 void launch_fwd(dim3 grid, hipStream_t s, int32_t precision, const float* q, int32_t ldq, const float* k, const float* v, int32_t ldkv, int32_t S,
                 int32_t H, int32_t q_from, int32_t tiles, float scale, float* out32, void* out16, float* lse) {
+    const DenseRows rows = {q, k, v, ldq, ldkv, S, q_from, tiles, lse};
     if (precision == 1)
-        hipLaunchKernelGGL(llama_body_attn_mfma_kernel<G>, grid, dim3(64 * G), 0, s, q, ldq, k, v, ldkv, S, H, q_from, tiles, scale, out32,
-                           static_cast<bf16_t*>(out16), lse);
+        hipLaunchKernelGGL((gqa128::attn_mfma_kernel<G, DenseRows>), grid, dim3(64 * G), 0, s, rows, H, scale, out32, static_cast<bf16_t*>(out16));
     else
-        hipLaunchKernelGGL(llama_body_attn_valu_kernel<G>, grid, dim3(64 * G), 0, s, q, ldq, k, v, ldkv, S, H, q_from, tiles, scale, out32,
-                           static_cast<bf16_t*>(out16), lse);
+        hipLaunchKernelGGL((gqa128::attn_valu_kernel<G, DenseRows>), grid, dim3(64 * G), 0, s, rows, H, scale, out32, static_cast<bf16_t*>(out16));
 }
 
 }  // namespace

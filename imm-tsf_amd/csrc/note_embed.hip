@@ -6,7 +6,7 @@
 // one sequence, B = 1):
 //   * token embedding: row r of note n at position p = wte[ids[r]] + wpe[p]
 //   * causal attention forward over ragged sequences, Q / K / V read in c_attn's output layout (row pitch 3 d, head h at columns 64 h),
-//     output in the layout c_proj reads.  fp32 mode: one query per thread, keys through LDS (the form of gpt2_attn_fwd_kernel with the
+//     output in the layout c_proj reads.  fp32 mode: one query per thread, keys through LDS (the form of attn_dense64.hpp with the
 //     key range taken from cu).  bf16 mode: both products on bf16 MFMA with fp32 accumulation, fp32 online softmax.
 //   * ln_f + mean-pool: LayerNorm of each row of a note, summed in position order, / max(L, 1); a note of no tokens gives an exact 0 row
 // Forward only, no dropout, no atomics, one writer per output element, every sum in a fixed order: two runs give the same bits.
@@ -327,7 +327,6 @@ __global__ void __launch_bounds__(256) note_pool_kernel(const float* __restrict_
     }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 template <bool CAUSAL>
@@ -336,7 +335,7 @@ int launch_attention(const float* qkv, int32_t ld, const int32_t* cu, int32_t N,
     if (!qkv || !cu || (!out32 && !out16) || N <= 0 || rows <= 0 || H <= 0 || max_len <= 0) return IMMTSF_EINVAL;
     if (precision < 0 || precision > 1) return IMMTSF_EINVAL;
     if (H > 65535 || max_len > MAXL || ld < 3 * H * HD || (ld & 3) || !al16(qkv) || (out32 && !al16(out32)) ||
-        (out16 && (reinterpret_cast<uintptr_t>(out16) & 7)))
+        (out16 && !al8(out16)))
         return IMMTSF_EUNSUPPORTED;
     const dim3 grid((unsigned)N, (unsigned)H, (unsigned)((max_len + QT - 1) / QT));
     hipStream_t s = static_cast<hipStream_t>(stream);

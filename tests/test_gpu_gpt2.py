@@ -18,7 +18,7 @@ import gpt2_ref as R  # noqa: E402
 pytestmark = pytest.mark.gpu
 OUT_BAR, GRAD_BAR = 1e-4, 3e-4
 D, H = 128, 2
-SHAPES = [(3, 37, 5), (2, 0, 9), (1, 1, 1), (2, 60, 4), (2, 17, 40)]
+SHAPES = [(3, 37, 5), (2, 0, 9), (1, 1, 1), (2, 60, 4), (2, 17, 40), (1, 31, 65)]
 CASES = [(s, 2) for s in SHAPES] + [((3, 37, 5), 1)]       # (B, S_p, S_t), n_layer
 IDS = [f"B{s[0]}_Sp{s[1]}_St{s[2]}_L{n}" for s, n in CASES]
 
@@ -44,6 +44,11 @@ def _body(n_layer, p_drop, **kw):
     return m.to(_dev()).train()
 
 
+def _positions(shape):
+    """the default body has 64 positions (test_supported_limits reads that bound); a longer sequence gets a body with a longer table"""
+    return {"n_positions": 128} if shape[1] + shape[2] > 64 else {}
+
+
 @functools.lru_cache(maxsize=None)
 def _inputs(shape):
     B, S_p, S_t = shape
@@ -55,7 +60,7 @@ def _inputs(shape):
 def _reference(shape, n_layer):
     """float64, no dropout: computed once, shared"""
     prefix, tail, up = _inputs(shape)
-    m = _body(n_layer, 0.0)
+    m = _body(n_layer, 0.0, **_positions(shape))
     return R.tail_forward_backward(R.weights64(m), prefix, tail, up, n_layer, H, m.config.layer_norm_epsilon)
 
 
@@ -78,7 +83,7 @@ def _fused(m, shape, training=False, seed=None, prefix_grad=False):
 def test_fp32_against_float64(shape, n_layer):
     from immtsf import config
     config.precision = "fp32"
-    out, grad, _ = _fused(_body(n_layer, 0.0), shape)
+    out, grad, _ = _fused(_body(n_layer, 0.0, **_positions(shape)), shape)
     want_out, want_grad = _reference(shape, n_layer)
     eo, eg = _rel(out, want_out), _rel(grad, want_grad)
     print(f"{shape} L{n_layer}: out {eo:.2e} (bar {OUT_BAR:.0e})  d tail {eg:.2e} (bar {GRAD_BAR:.0e})")
@@ -96,7 +101,7 @@ def test_fp32_dropout_masks_reproduced(shape, n_layer):
     p, seed = 0.3, 0x5EED1234
     B, S_p, S_t = shape
     S = S_p + S_t
-    m = _body(n_layer, p)
+    m = _body(n_layer, p, **_positions(shape))
     out, grad, _ = _fused(m, shape, training=True, seed=seed)
     km = lambda site, n: ops.dropout_keep_mask(seed, site, n, p, dev).cpu()      # noqa: E731
     masks = {"p": (p, p, p), "embd": km(ops.GPT2_SITE_EMBD, B * S * D).view(B, S, D), "attn": [], "resid1": [], "resid2": []}
@@ -121,7 +126,7 @@ def test_fp32_dropout_masks_reproduced(shape, n_layer):
 def test_bf16_within_4x_of_autocast(shape, n_layer):
     from immtsf import config
     dev = _dev()
-    m = _body(n_layer, 0.0)
+    m = _body(n_layer, 0.0, **_positions(shape))
     want_out, want_grad = _reference(shape, n_layer)
     prefix, tail, up = (t.to(dev) for t in _inputs(shape))
     t2 = tail.clone().requires_grad_(True)
@@ -153,7 +158,7 @@ def test_fused_equals_the_stock_body(shape, n_layer):
     from immtsf import config
     config.precision = "fp32"
     dev = _dev()
-    m = _body(n_layer, 0.0)
+    m = _body(n_layer, 0.0, **_positions(shape))
     prefix, tail, up = (t.to(dev) for t in _inputs(shape))
     t2 = tail.clone().requires_grad_(True)
     hf = m(inputs_embeds=torch.cat([prefix, t2], 1)).last_hidden_state[:, -shape[2]:]
