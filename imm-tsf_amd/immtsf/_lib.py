@@ -190,6 +190,10 @@ _PROTOS = {
     "immtsf_gpt2_supported": (C.c_int, [C.c_int32] * 4),
     "immtsf_gpt2_gemm": (C.c_int, [C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_int32, c_f32p, C.c_void_p, C.c_int32, c_f32p, C.c_int32, c_f32p,
                                    C.c_int32, C.c_int32, C.c_int32, c_stream]),
+    "immtsf_split_bf16": (C.c_int, [c_f32p, C.c_uint64, C.c_void_p, C.c_void_p, c_stream]),
+    "immtsf_gemm_split_supported": (C.c_int, [C.c_int32] * 7),
+    "immtsf_gemm_split": (C.c_int, [C.c_int32, c_f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32,
+                                    C.c_int32, C.c_int32, c_stream]),
     "immtsf_gpt2_embed": (C.c_int, [c_f32p, c_f32p, c_f32p] + [C.c_int32] * 4 + [C.c_float, C.c_uint64, C.c_uint64, c_f32p, c_stream]),
     "immtsf_gpt2_layernorm": (C.c_int, [c_f32p] + [C.c_int32] * 4 + [c_f32p, c_f32p, C.c_float, c_f32p, C.c_void_p, c_f32p, c_f32p, c_stream]),
     "immtsf_gpt2_layernorm_backward": (C.c_int, [c_f32p] * 6 + [C.c_int64, C.c_int32, c_f32p, c_stream]),

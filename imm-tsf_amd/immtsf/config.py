@@ -146,6 +146,19 @@ timellm_fused = os.environ.get("IMMTSF_TIMELLM_FUSED", "1") != "0"
 # stock call (178 vs 72 ms), so fp32 mode keeps the stock call unless IMMTSF_TIMELLM_BERT_FP32=1 asks for the operator (the
 # cross-check of the two paths at fp32 accuracy; less saved memory).  Under timellm_fused either way
 timellm_bert_fp32 = os.environ.get("IMMTSF_TIMELLM_BERT_FP32", "0") == "1"
+# How the frozen GPT-2 / Llama / BERT bodies and the three note-embedding operators form their weight products in fp32 mode (bf16 mode
+# never reads this).  "fp32": fp32 operands on the f32 MFMA, as ever.  "split": every product that immtsf_gemm_split_supported allows
+# runs on the bf16 MFMA over two cached bf16 images of the frozen weight and the activation cut in registers (csrc/gemm_split.hip,
+# 16 - 17 significant bits per operand, three MFMA passes); the rest of the body stays the fp32-mode one
+frozen_products = os.environ.get("IMMTSF_FROZEN_PRODUCTS", "fp32")
+_FROZEN_PRODUCTS = ("fp32", "split")
+
+
+def frozen_split(precision_code_: int) -> bool:
+    """whether a frozen body at this precision code forms its products on the split-bf16 kernel"""
+    if frozen_products not in _FROZEN_PRODUCTS:
+        raise ValueError(f"frozen_products must be one of {sorted(_FROZEN_PRODUCTS)}, got {frozen_products!r}")
+    return precision_code_ == 0 and frozen_products == "split"
 # TimeLLM's prompt statistics (min, max, median, trend, top lags of every window) in ONE launch and ONE device-to-host copy per
 # forecasting() call (immtsf.ops.timellm_prompt_stats, csrc/timellm_prompt.hip) wherever timellm_prompt_supported allows;
 # IMMTSF_TIMELLM_PROMPT_FUSED=0: the torch expressions with rfft / irfft and five host reads per window -- the cross-check.  The text is

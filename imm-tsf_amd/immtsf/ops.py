@@ -3123,6 +3123,55 @@ def _gpt2_w16(model, W):
     return hit[1]
 
 
+split_product_calls = 0          # products of the frozen bodies / note-embedding operators that ran on immtsf_gemm_split
+
+
+def _split_images(W):
+    """(hi, lo) bf16 images of a contiguous fp32 tensor: hi = bf16(W), lo = bf16(W - hi), the operands of csrc/gemm_split.hip"""
+    hi = torch.empty(W.shape, dtype=torch.bfloat16, device=W.device)
+    lo = torch.empty_like(hi)
+    check(_lib.load().immtsf_split_bf16(ptr(W), W.numel(), ptr(hi), ptr(lo), stream_ptr()), "split_bf16")
+    return hi, lo
+
+
+def _gpt2_w_split(model, W):
+    """(hi, lo) bf16 images of a frozen weight, same layout, cached on the model and keyed exactly as _gpt2_w16 keys its image: by the
+    parameter's storage address and version, so load_state_dict(), .to() or any in-place write makes a new pair"""
+    cache = model.__dict__.setdefault("_immtsf_gpt2_w_split", {})
+    key = (W.data_ptr(), W._version, tuple(W.shape))
+    hit = cache.get(id(W))
+    if hit is None or hit[0] != key:
+        hit = cache[id(W)] = (key, _split_images(W.detach().contiguous()))
+    return hit[1]
+
+
+def _w_img(model, W, bf, sp):
+    """what a frozen product reads beside the fp32 weight: its bf16 image in bf16 mode, its (hi, lo) pair under
+    config.frozen_products == "split" in fp32 mode, else nothing"""
+    return _gpt2_w16(model, W) if bf else _gpt2_w_split(model, W) if sp else None
+
+
+def _frozen_gemm(lib, layout, precision, pa32, pa16, lda, W, img, w_off, ldb, out, c_off, ldc, bias, M, N, K, st, what="gpt2_gemm"):
+    """out[.. c_off ..] (M, N; pitch ldc) = a (M, K; pitch lda) op(W[.. w_off ..]) + bias: one product of a frozen body.  pa32 / pa16
+    and bias: pointers as the caller made them (bias already at its offset, or None); W the fp32 weight and `img` what _w_img gave for
+    it, both read from element offset w_off at pitch ldb; out written from element offset c_off.  An (hi, lo) pair goes to
+    immtsf_gemm_split when that supports the shape; anything else is immtsf_gpt2_gemm's call as it always was."""
+    global split_product_calls
+
+    def off(t, o):
+        return None if t is None else C.c_void_p(t.data_ptr() + o * t.element_size())
+
+    if isinstance(img, tuple):
+        if lib.immtsf_gemm_split_supported(layout, M, N, K, lda, ldb, ldc):
+            check(lib.immtsf_gemm_split(layout, pa32, lda, off(img[0], w_off), off(img[1], w_off), ldb, off(out, c_off), ldc, bias, M, N, K, st),
+                  what + " (split)")
+            split_product_calls += 1
+            return
+        img = None
+    check(lib.immtsf_gpt2_gemm(layout, precision, pa32, pa16, lda, off(W, w_off), off(img, w_off), ldb, off(out, c_off), ldc, bias, M, N, K, st),
+          what)
+
+
 class GPT2BodyFn(torch.autograd.Function):
     """transformers' GPT2Model(inputs_embeds=cat([prefix, tail], 1)).last_hidden_state[:, -S_t:] on csrc/gpt2.hip + the GEMM family.  The
     body is frozen and only `tail` takes a gradient; attention is causal without a padding mask, so no prefix row depends on a tail row
@@ -3140,6 +3189,7 @@ class GPT2BodyFn(torch.autograd.Function):
         S, H, inner, L = S_p + S_t, int(cfg.n_head), _gpt2_inner(cfg), len(model.h)
         dev = tail.device
         bf = precision == 1
+        sp = config.frozen_split(precision)
         p_e, p_a, p_r = p_drops
         eps = float(cfg.layer_norm_epsilon)
         scale = 1.0 / float(d // H) ** 0.5
@@ -3149,10 +3199,8 @@ class GPT2BodyFn(torch.autograd.Function):
 
         def mm(a32, a16, W, bias, M, N, K, out, ldc, w_off=0, c_off=0):
             """out[:, c_off:c_off+N] = a (M, K) W[:, w_off:w_off+N] + bias[w_off:...]; W is the Conv1D weight (in, out)"""
-            ldb = W.shape[1]
-            w16 = adr(_gpt2_w16(model, W), w_off) if bf else None
-            check(lib.immtsf_gpt2_gemm(1, precision, ptr(a32), ptr(a16), K, adr(W, w_off), w16, ldb, adr(out, c_off), ldc, adr(bias, w_off),
-                                       M, N, K, st), "gpt2_gemm")
+            _frozen_gemm(lib, 1, precision, ptr(a32), ptr(a16), K, W, _w_img(model, W, bf, sp), w_off, W.shape[1], out, c_off, ldc,
+                         adr(bias, w_off), M, N, K, st)
 
         def ln(x, rows_per_b, s_from, norm, stats):
             n = B * (rows_per_b - s_from)
@@ -3228,6 +3276,7 @@ class GPT2BodyFn(torch.autograd.Function):
         S, M = S_p + S_t, B * S_t
         p_e, p_a, p_r = ctx.drops
         seed, prec = ctx.seed, ctx.precision
+        sp = config.frozen_split(prec)
         dev = dout.device
         scale = 1.0 / float(d // H) ** 0.5
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
@@ -3235,7 +3284,7 @@ class GPT2BodyFn(torch.autograd.Function):
 
         def mm_t(g, W, N, K):          # g (M, K) W^T: W is the Conv1D weight (in = N, out = K), read as it is stored
             o = f32(M, N)
-            check(lib.immtsf_gpt2_gemm(0, prec, ptr(g), None, K, ptr(W), None, K, ptr(o), N, None, M, N, K, st), "gpt2_gemm (backward)")
+            _frozen_gemm(lib, 0, prec, ptr(g), None, K, W, _w_img(model, W, False, sp), 0, K, o, 0, N, None, M, N, K, st, "gpt2_gemm (backward)")
             return o
 
         def ln_bwd(g, x, mean, rstd, norm, resid):
@@ -3336,6 +3385,7 @@ def gpt2_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         st = stream_ptr()
         precision = config.precision_code(precision)
         bf = precision == 1
+        sp = config.frozen_split(precision)
         H, inner = int(cfg.n_head), _gpt2_inner(cfg)
         eps = float(cfg.layer_norm_epsilon)
         scale = 1.0 / float(d // H) ** 0.5
@@ -3361,8 +3411,8 @@ def gpt2_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
 
         def mm(a, conv, N_out, K, out):
             W = conv.weight
-            check(lib.immtsf_gpt2_gemm(1, precision, a32(a), a16(a), K, ptr(W), ptr(_gpt2_w16(llm_model, W)) if bf else None, W.shape[1],
-                                       ptr(out), N_out, ptr(conv.bias), T, N_out, K, st), "gpt2_gemm")
+            _frozen_gemm(lib, 1, precision, a32(a), a16(a), K, W, _w_img(llm_model, W, bf, sp), 0, W.shape[1], out, 0, N_out, ptr(conv.bias),
+                         T, N_out, K, st)
 
         def ln(src, norm, dst):
             check(lib.immtsf_gpt2_layernorm(ptr(src), 1, T, 0, d, ptr(norm.weight), ptr(norm.bias), eps, a32(dst), a16(dst), None, None, st),
@@ -3409,9 +3459,10 @@ def bert_embed_notes_supported(llm_model, max_len):
     return bool(_lib.load().immtsf_bert_embed_supported(d, H, int(max_len), int(cfg.max_position_embeddings)))
 
 
-def _bert_qkv(model, att, bf):
+def _bert_qkv(model, att, bf, sp=False):
     """(W (3d, d), bias (3d), bf16 image of W or None) of one layer's query | key | value Linears, concatenated once and cached on the model,
-    keyed by the six parameters' storage address and version: load_state_dict(), .to() or any in-place write makes a new one"""
+    keyed by the six parameters' storage address and version: load_state_dict(), .to() or any in-place write makes a new one.  sp (fp32
+    mode under config.frozen_products == "split"): the third item is W's (hi, lo) pair, cached in the same entry"""
     cache = model.__dict__.setdefault("_immtsf_bert_qkv", {})
     params = (att.query.weight, att.key.weight, att.value.weight, att.query.bias, att.key.bias, att.value.bias)
     key = tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in params)
@@ -3422,6 +3473,10 @@ def _bert_qkv(model, att, bf):
     if bf and hit[3] is None:
         hit[3] = torch.empty(hit[1].shape, dtype=torch.bfloat16, device=hit[1].device)
         check(_lib.load().immtsf_f32_to_bf16(ptr(hit[1]), ptr(hit[3]), hit[1].numel(), stream_ptr()), "f32_to_bf16")
+    if sp and not bf:
+        if len(hit) == 4:
+            hit.append(_split_images(hit[1]))
+        return hit[1], hit[2], hit[4]
     return hit[1], hit[2], hit[3]
 
 
@@ -3456,6 +3511,7 @@ def bert_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         st = stream_ptr()
         precision = config.precision_code(precision)
         bf = precision == 1
+        sp = config.frozen_split(precision)
         H = int(cfg.num_attention_heads)
         eps = float(cfg.layer_norm_eps)
         scale = 1.0 / float(d // H) ** 0.5
@@ -3481,11 +3537,11 @@ def bert_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         def mm(a32, a16, W, W16, bias, out):
             """out (T, N_out) = a (T, K) W^T + bias: W (N_out, K) is the nn.Linear weight as stored (layout 0)"""
             N_out, K = W.shape
-            check(lib.immtsf_gpt2_gemm(0, precision, None if bf else ptr(a32), ptr(a16) if bf else None, K, ptr(W), ptr(W16) if bf else None, K,
-                                       ptr(out), N_out, ptr(bias), T, N_out, K, st), "gpt2_gemm")
+            _frozen_gemm(lib, 0, precision, None if bf else ptr(a32), ptr(a16) if bf else None, K, W, W16, 0, K, out, 0, N_out, ptr(bias),
+                         T, N_out, K, st)
 
         def lin(a32, a16, dense, out):
-            mm(a32, a16, dense.weight, _gpt2_w16(llm_model, dense.weight) if bf else None, dense.bias, out)
+            mm(a32, a16, dense.weight, _w_img(llm_model, dense.weight, bf, sp), dense.bias, out)
 
         def add_ln(y, base, norm, dst):
             check(lib.immtsf_bert_embed_add_layernorm(ptr(y), ptr(base), T, d, ptr(norm.weight), ptr(norm.bias), eps, ptr(dst), ptr(h), st),
@@ -3498,7 +3554,7 @@ def bert_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
                                          ptr(x), ptr(h), st), "bert_embed_rows")
         for layer in llm_model.encoder.layer:
             att = layer.attention
-            Wqkv, bqkv, Wqkv16 = _bert_qkv(llm_model, att.self, bf)
+            Wqkv, bqkv, Wqkv16 = _bert_qkv(llm_model, att.self, bf, sp)
             mm(x, h, Wqkv, Wqkv16, bqkv, qkv)
             check(lib.immtsf_bert_embed_attention(ptr(qkv), 3 * d, ptr(cu), N, T, H, max_len, scale, precision, None if bf else ptr(ao),
                                                   ptr(ao) if bf else None, st), "bert_embed_attention")
@@ -3542,9 +3598,10 @@ def llama_embed_notes_supported(llm_model, max_len):
     return bool(_lib.load().immtsf_llama_embed_supported(d, H, H_kv, inner, int(max_len), int(cfg.max_position_embeddings)))
 
 
-def _llama_cat(model, owner, slot, linears, bf):
+def _llama_cat(model, owner, slot, linears, bf, sp=False):
     """(W, bf16 image of W or None): the weights of `linears` concatenated along the output axis, once, cached on the model under
-    (owner, slot) and keyed by the parameters' storage address and version: load_state_dict(), .to() or any in-place write makes a new one"""
+    (owner, slot) and keyed by the parameters' storage address and version: load_state_dict(), .to() or any in-place write makes a new one.
+    sp (fp32 mode under config.frozen_products == "split"): the second item is W's (hi, lo) pair, cached in the same entry"""
     cache = model.__dict__.setdefault("_immtsf_llama_cat", {})
     params = tuple(lin.weight for lin in linears)
     key = tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in params)
@@ -3554,6 +3611,10 @@ def _llama_cat(model, owner, slot, linears, bf):
     if bf and hit[2] is None:
         hit[2] = torch.empty(hit[1].shape, dtype=torch.bfloat16, device=hit[1].device)
         check(_lib.load().immtsf_f32_to_bf16(ptr(hit[1]), ptr(hit[2]), hit[1].numel(), stream_ptr()), "f32_to_bf16")
+    if sp and not bf:
+        if len(hit) == 3:
+            hit.append(_split_images(hit[1]))
+        return hit[1], hit[3]
     return hit[1], hit[2]
 
 
@@ -3589,6 +3650,7 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         st = stream_ptr()
         precision = config.precision_code(precision)
         bf = precision == 1
+        sp = config.frozen_split(precision)
         eps = float(cfg.rms_norm_eps)
         scale = 1.0 / float(hd) ** 0.5
         pooled = torch.empty(N, d, dtype=torch.float32, device=dev)
@@ -3615,11 +3677,10 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         def mm(a, W, W16, out):
             """out (T, N_out) = a (T, K) W^T: W (N_out, K) is the nn.Linear weight as stored (layout 0); Llama's Linears have no bias"""
             N_out, K = W.shape
-            check(lib.immtsf_gpt2_gemm(0, precision, o32(a), o16(a), K, ptr(W), ptr(W16) if bf else None, K, ptr(out), N_out, None, T, N_out, K,
-                                       st), "gpt2_gemm")
+            _frozen_gemm(lib, 0, precision, o32(a), o16(a), K, W, W16, 0, K, out, 0, N_out, None, T, N_out, K, st)
 
         def lin(a, dense, out):
-            mm(a, dense.weight, _gpt2_w16(llm_model, dense.weight) if bf else None, out)
+            mm(a, dense.weight, _w_img(llm_model, dense.weight, bf, sp), out)
 
         rope = llm_model.rotary_emb
         inv_freq = rope.inv_freq.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -3634,14 +3695,14 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
                 check(lib.immtsf_llama_embed_rmsnorm(ptr(x), T, d, ptr(w_in), eps, o32(h), o16(h), st), "llama_embed_rmsnorm")
             else:      # the residual add of the layer before rides on this norm
                 check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(w_in), eps, o32(h), o16(h), st), "llama_embed_add_rmsnorm")
-            mm(h, *_llama_cat(llm_model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf), qkv)
+            mm(h, *_llama_cat(llm_model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf, sp), qkv)
             check(lib.immtsf_llama_embed_rope(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, ptr(cos_t), ptr(sin_t), st), "llama_embed_rope")
             check(lib.immtsf_llama_embed_attention(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, scale, precision, o32(ao), o16(ao), st),
                   "llama_embed_attention")
             lin(ao, att.o_proj, pr)
             check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(layer.post_attention_layernorm.weight), eps, o32(h), o16(h), st),
                   "llama_embed_add_rmsnorm")
-            mm(h, *_llama_cat(llm_model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf), gu)
+            mm(h, *_llama_cat(llm_model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf, sp), gu)
             check(lib.immtsf_llama_embed_swiglu(ptr(gu), T, inner, o32(act), o16(act), st), "llama_embed_swiglu")
             lin(act, mlp.down_proj, pr)
         check(lib.immtsf_llama_embed_pool(ptr(x), ptr(pr), ptr(cu), N, T, d, ptr(llm_model.norm.weight), eps, ptr(rstd), ptr(pooled), st),
@@ -3682,6 +3743,7 @@ class LlamaBodyFn(torch.autograd.Function):
         dqkv = dq + 2 * dkv
         dev = tail.device
         bf = precision == 1
+        sp = config.frozen_split(precision)
         eps = float(cfg.rms_norm_eps)
         scale = 1.0 / float(hd) ** 0.5
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
@@ -3692,11 +3754,11 @@ class LlamaBodyFn(torch.autograd.Function):
             """out[:, c_off:c_off + n_out] = a (M, K) W[w_row:w_row + n_out]^T: W (N, K) is the nn.Linear weight as stored (layout 0)"""
             K = W.shape[1]
             n_out = W.shape[0] if n_out is None else n_out
-            check(lib.immtsf_gpt2_gemm(0, precision, None if bf else ptr(a), ptr(a) if bf else None, K, adr(W, w_row * K),
-                                       adr(W16, w_row * K) if bf else None, K, adr(out, c_off), ldc, None, M, n_out, K, st), "gpt2_gemm")
+            _frozen_gemm(lib, 0, precision, None if bf else ptr(a), ptr(a) if bf else None, K, W, W16, w_row * K, K, out, c_off, ldc, None,
+                         M, n_out, K, st)
 
         def lin(a, dense, M, out):
-            mm(a, dense.weight, _gpt2_w16(model, dense.weight) if bf else None, M, out, dense.weight.shape[0])
+            mm(a, dense.weight, _w_img(model, dense.weight, bf, sp), M, out, dense.weight.shape[0])
 
         def rms(xin, S_in, s_from, y, w, stats):
             """(row sums xin + y or xin itself, normed operand, rstd) of the rows s_from .. S_in - 1, compact"""
@@ -3730,7 +3792,7 @@ class LlamaBodyFn(torch.autograd.Function):
             qf = S_p if li == L - 1 else 0
             Sq = S - qf
             x, h, rstd1 = rms(x, Sx, 0, y, layer.input_layernorm.weight, need_bwd)
-            W, W16 = _llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf)
+            W, W16 = _llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf, sp)
             if qf == 0:
                 qkv = f32(B * S, dqkv)
                 mm(h, W, W16, B * S, qkv, dqkv)
@@ -3754,7 +3816,7 @@ class LlamaBodyFn(torch.autograd.Function):
             lin(ao16 if bf else ao32, att.o_proj, B * Sq, pr)
             x1, g, rstd2 = rms(x, S, qf, pr, layer.post_attention_layernorm.weight, need_bwd)
             gu = f32(B * Sq, 2 * inner)
-            mm(g, *_llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf), B * Sq, gu, 2 * inner)
+            mm(g, *_llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf, sp), B * Sq, gu, 2 * inner)
             act = b16(B * Sq, inner) if bf else f32(B * Sq, inner)
             check(lib.immtsf_llama_embed_swiglu(ptr(gu), B * Sq, inner, None if bf else ptr(act), ptr(act) if bf else None, st),
                   "llama_embed_swiglu")
@@ -3790,6 +3852,7 @@ class LlamaBodyFn(torch.autograd.Function):
         dq, dkv = H * hd, H_kv * hd
         dqkv = dq + 2 * dkv
         bf = prec == 1
+        sp = config.frozen_split(prec)
         dev = dout.device
         scale = 1.0 / float(hd) ** 0.5
         cos_t, sin_t = ctx.rope
@@ -3800,12 +3863,12 @@ class LlamaBodyFn(torch.autograd.Function):
         def mm_t(g32, g16, W, W16):       # g (M, N) W: W (N, K) is the nn.Linear weight as stored, read as it is (layout 1)
             N, K = W.shape
             o = f32(M, K)
-            check(lib.immtsf_gpt2_gemm(1, prec, None if bf else ptr(g32), ptr(g16) if bf else None, N, ptr(W), ptr(W16) if bf else None, K,
-                                       ptr(o), K, None, M, K, N, st), "gpt2_gemm (backward)")
+            _frozen_gemm(lib, 1, prec, None if bf else ptr(g32), ptr(g16) if bf else None, N, W, W16, 0, K, o, 0, K, None, M, K, N, st,
+                         "gpt2_gemm (backward)")
             return o
 
         def lin_t(g32, g16, dense):
-            return mm_t(g32, g16, dense.weight, _gpt2_w16(model, dense.weight) if bf else None)
+            return mm_t(g32, g16, dense.weight, _w_img(model, dense.weight, bf, sp))
 
         def rms_bwd(g, x, rstd, w, resid):
             o, o16 = f32(M, d), b16(M, d)
@@ -3823,7 +3886,7 @@ class LlamaBodyFn(torch.autograd.Function):
             dgu, dgu16 = (None, b16(M, 2 * inner)) if bf else (f32(M, 2 * inner), None)
             check(lib.immtsf_llama_body_swiglu_backward(ptr(gu_t), ptr(dact), M, inner, ptr(dgu), ptr(dgu16), st),
                   "llama_body_swiglu_backward")
-            dg = mm_t(dgu, dgu16, *_llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf))
+            dg = mm_t(dgu, dgu16, *_llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf, sp))
             dx1, dx1_16 = rms_bwd(dg, x1_t, rstd2, layer.post_attention_layernorm.weight, dx)
             dao = lin_t(dx1, dx1_16, att.o_proj)
             dbuf, dbuf16 = f32(M, dqkv), b16(M, dqkv)
@@ -3833,7 +3896,7 @@ class LlamaBodyFn(torch.autograd.Function):
                                                            adr(dbuf, dq + dkv), dqkv, st), "llama_body_attention_backward")
             check(lib.immtsf_llama_body_rope(ptr(dbuf), dqkv, M, S_t, S_p, H + H_kv, S, ptr(cos_t), ptr(sin_t), 1, ptr(dbuf16), st),
                   "llama_body_rope (backward)")
-            dh = mm_t(dbuf, dbuf16, *_llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf))
+            dh = mm_t(dbuf, dbuf16, *_llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf, sp))
             dx, dx16 = rms_bwd(dh, x_t, rstd1, layer.input_layernorm.weight, dx1)
         return dx.view(B, S_t, d), None, None, None, None
 
@@ -3898,6 +3961,7 @@ class BertBodyFn(torch.autograd.Function):
         M = B * S_t
         dev = tail.device
         bf = precision == 1
+        sp = config.frozen_split(precision)
         p_h, p_a = p_drops
         eps = float(cfg.layer_norm_eps)
         scale = 1.0 / float(d // H) ** 0.5
@@ -3910,12 +3974,11 @@ class BertBodyFn(torch.autograd.Function):
             stored (layout 0)"""
             K = W.shape[1]
             n_out = W.shape[0] if n_out is None else n_out
-            check(lib.immtsf_gpt2_gemm(0, precision, None if bf else ptr(a32), ptr(a16) if bf else None, K, adr(W, w_row * K),
-                                       adr(W16, w_row * K) if bf else None, K, adr(out, c_off), ldc, adr(bias, w_row), rows, n_out, K, st),
-                  "gpt2_gemm")
+            _frozen_gemm(lib, 0, precision, None if bf else ptr(a32), ptr(a16) if bf else None, K, W, W16, w_row * K, K, out, c_off, ldc,
+                         adr(bias, w_row), rows, n_out, K, st)
 
         def lin(a32, a16, dense, rows, out):
-            mm(a32, a16, dense.weight, _gpt2_w16(model, dense.weight) if bf else None, dense.bias, rows, out, dense.weight.shape[0])
+            mm(a32, a16, dense.weight, _w_img(model, dense.weight, bf, sp), dense.bias, rows, out, dense.weight.shape[0])
 
         def add_ln(xin, S_in, s_from, y, q_from, norm, site, out32, keep16):
             """LayerNorm(xin rows + dropout(y)) -> (out32, bf16 image or None, pre-norm sum, mean, rstd)"""
@@ -3947,7 +4010,7 @@ class BertBodyFn(torch.autograd.Function):
             Mq = B * Sq
             s_attn, s_h1, s_h2 = bert_sites(li)
             att = layer.attention
-            W, bias, W16 = _bert_qkv(model, att.self, bf)
+            W, bias, W16 = _bert_qkv(model, att.self, bf, sp)
             qkv = f32(B * S, 3 * d)
             if qf == 0:
                 mm(x, x16, W, W16, bias, B * S, qkv, 3 * d)
@@ -3990,6 +4053,7 @@ class BertBodyFn(torch.autograd.Function):
         S, M, L = S_p + S_t, B * S_t, len(model.encoder.layer)
         p_h, p_a = ctx.drops
         bf = prec == 1
+        sp = config.frozen_split(prec)
         dev = dout.device
         scale = 1.0 / float(d // H) ** 0.5
         f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
@@ -3999,12 +4063,12 @@ class BertBodyFn(torch.autograd.Function):
         def mm_t(g32, g16, W, W16, rows):       # g (rows, N) W: W (N, K) is the nn.Linear weight as stored, read as it is (layout 1)
             N, K = W.shape
             o = f32(rows, K)
-            check(lib.immtsf_gpt2_gemm(1, prec, None if bf else ptr(g32), ptr(g16) if bf else None, N, ptr(W), ptr(W16) if bf else None, K,
-                                       ptr(o), K, None, rows, K, N, st), "gpt2_gemm (backward)")
+            _frozen_gemm(lib, 1, prec, None if bf else ptr(g32), ptr(g16) if bf else None, N, W, W16, 0, K, o, 0, K, None, rows, K, N, st,
+                         "gpt2_gemm (backward)")
             return o
 
         def lin_t(g32, g16, dense, rows):
-            return mm_t(g32, g16, dense.weight, _gpt2_w16(model, dense.weight) if bf else None, rows)
+            return mm_t(g32, g16, dense.weight, _w_img(model, dense.weight, bf, sp), rows)
 
         def ln_bwd(dy, Sn, sm, mean, rstd, norm, q_from, site):
             """dy = (dy_a, Sa, sa_from, dy_b, tb_from) -> (d_sum fp32, the branch's gradient as the next product reads it: fp32, bf16)"""
@@ -4053,7 +4117,7 @@ class BertBodyFn(torch.autograd.Function):
             dqkv16 = b16(B * rows_b, 3 * d)
             if bf:
                 check(lib.immtsf_f32_to_bf16(ptr(dqkv), ptr(dqkv16), dqkv.numel(), st), "f32_to_bf16")
-            W, _, W16 = _bert_qkv(model, att.self, bf)
+            W, _, W16 = _bert_qkv(model, att.self, bf, sp)
             gq = mm_t(dqkv, dqkv16, W, W16, B * rows_b)
             if first:
                 dy = (dsum1, Sq, S_p - qf, gq, 0)

@@ -1030,6 +1030,26 @@ int immtsf_timellm_prototypes_backward(int32_t precision, const float* E, const 
                                        int32_t d_llm, int32_t D, float* dW_map, float* db_map, float* dWk, float* dbk, float* dWv,
                                        float* dbv, void* scratch, size_t scratch_bytes, immtsf_stream_t stream);
 
+/* ---- Frozen-weight products at fp32 grade on the bf16 MFMA (added within ABI 7: new functions only; csrc/gemm_split.hip): what the frozen
+ * GPT-2 / Llama / BERT bodies and the note-embedding operators run instead of immtsf_gpt2_gemm at precision 0 when
+ * immtsf.config.frozen_products is "split" (DESIGN 4u).
+ * ..._split_bf16: hi[i] = bf16(src[i]), lo[i] = bf16(src[i] - hi[i]) (round to nearest even; the subtraction is exact), n elements each:
+ *   the two images of a frozen weight, made once.  Any alignment (four elements a thread where src is 16- and hi / lo are 8-byte aligned).
+ * ..._gemm_split: C (M, N; pitch ldc) = op(A) op(B) + bias, A (M, K; pitch lda) fp32, B given as its two images Bhi / Blo with B's own
+ *   shape and pitch ldb; layout 0: B is (N, K), an nn.Linear weight as stored, C = A B^T; layout 1: B is (K, N).  Sub-blocks are pointer
+ *   offsets (a row block of a layout-0 weight, a column block of a layout-1 weight or of C).  A is cut in registers the same way and
+ *   every 32-deep step of an output fragment is a_lo b_hi + a_hi b_lo + a_hi b_hi, in that order, on v_mfma_f32_16x16x32_bf16 with fp32
+ *   sums; a_lo b_lo is dropped.  The tests hold |C - exact| to (2^-16 + 3 K 2^-24) (|A| |B|) per element (worst case of the cut 2^-15:
+ *   DESIGN 4u).  bias (N) may be null.  No split-K, no
+ *   atomics, one writer per element, one summation order: the same inputs give the same bits.  Nothing allocates or synchronises.
+ * ..._gemm_split_supported: layout 0 | 1; M, N, K >= 1; K and N multiples of 8; lda a multiple of 4 and >= K; ldb a multiple of 8 and
+ *   >= K (layout 0) / N (layout 1); ldc >= N.  Outside this set, or with A / Bhi / Blo not 16-byte aligned, ..._gemm_split returns
+ *   IMMTSF_EUNSUPPORTED before anything is launched and C is untouched. */
+int immtsf_split_bf16(const float* src, uint64_t n, void* hi, void* lo, immtsf_stream_t stream);
+int immtsf_gemm_split_supported(int32_t layout, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc);
+int immtsf_gemm_split(int32_t layout, const float* A, int32_t lda, const void* Bhi, const void* Blo, int32_t ldb, float* C, int32_t ldc,
+                      const float* bias, int32_t M, int32_t N, int32_t K, immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

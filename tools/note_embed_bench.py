@@ -16,7 +16,11 @@ right-padded) -> immtsf.ops.bert_embed_notes; token counts from a few to 512.
 weights) cut to `--layers` layers (default 2: the whole body is 32 of them and every layer costs the same, so the times scale and the
 ratios stand), max_length 1024, the GPT-2 note mix behind a begin-of-text token -> immtsf.ops.llama_embed_notes.
 
-usage: python tools/note_embed_bench.py [--model gpt2|bert|llama] [--layers 2] [--notes 32] [--passes 3] [--single 8] [--out FILE]
+--products split: config.frozen_products = "split" for the whole run -- in fp32 mode the fused operator forms its weight products on
+the split-bf16 kernel (csrc/gemm_split.hip); bf16 mode and the stock side do not read it.  The same lines, with "products".
+
+usage: python tools/note_embed_bench.py [--model gpt2|bert|llama] [--products fp32|split] [--layers 2] [--notes 32] [--passes 3]
+                                        [--single 8] [--out FILE]
 """
 import argparse
 import json
@@ -64,6 +68,7 @@ def note_lengths(n, cap=MAX_LENGTH):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("gpt2", "bert", "llama"), default="gpt2")
+    ap.add_argument("--products", choices=("fp32", "split"), default="fp32", help="config.frozen_products for the run (read in fp32 mode)")
     ap.add_argument("--layers", type=int, default=2, help="layers of the --model llama body")
     ap.add_argument("--notes", type=int, default=32)
     ap.add_argument("--single", type=int, default=8, help="notes of the one-call-per-note workload (the first ones of the mix)")
@@ -77,6 +82,7 @@ def main():
     from fusions import load_llm as L
     from immtsf import config
     dev = torch.device("cuda:0")
+    config.frozen_products = args.products
     torch.manual_seed(0)
     if args.model == "bert":
         max_length, layers = 512, 6
@@ -131,7 +137,7 @@ def main():
     lines = []
     for prec in ("fp32", "bf16"):
         config.precision = prec
-        line = {"tool": "note_embed_bench", "model": args.model, "precision": prec, "layers": layers, "d": int(getattr(model.config, "hidden_size", 768)), "max_length": max_length,
+        line = {"tool": "note_embed_bench", "model": args.model, "precision": prec, "products": args.products, "layers": layers, "d": int(getattr(model.config, "hidden_size", 768)), "max_length": max_length,
                 "notes": len(notes), "row_ratio": round(ratio, 4), "single_notes": args.single, "single_row_ratio":
                 round(sum(lengths[:args.single]) / (args.single * max_length), 4), "passes": args.passes}
         for what, fn in (("batch", batch), ("single", single)):

@@ -28,7 +28,11 @@ sides: the stage alone, forward + backward (V 50257, S 1000, d_llm 768, H 8, d_k
 forecasting() + backward, the same alternating passes; one JSON line per precision mode with the best pass, all passes and their range
 (lo, hi) per side, whether every pass with the knob on lies below every pass with it off, and the operator's launches per direction.
 
-usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--prompt | --reprogram] [--iters 5] [--passes 5] [--batch 64] [--out FILE]
+--products split: config.frozen_products = "split" for the whole run -- in fp32 mode the fused body forms its weight products on the
+split-bf16 kernel (csrc/gemm_split.hip); bf16 mode and the stock side do not read it.  The same lines, with "products" in them.
+
+usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--products fp32|split] [--prompt | --reprogram] [--iters 5] [--passes 5]
+                                     [--batch 64] [--out FILE]
 """
 import argparse
 import json
@@ -52,6 +56,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--llm", choices=("GPT2", "LLAMA", "BERT"), default="GPT2")
+    ap.add_argument("--products", choices=("fp32", "split"), default="fp32", help="config.frozen_products for the run (read in fp32 mode)")
     ap.add_argument("--prompt", action="store_true", help="time the prompt statistics, knob on against knob off (GPT-2 body)")
     ap.add_argument("--reprogram", action="store_true", help="time the folded word prototypes, knob on against knob off (GPT-2 body)")
     args = ap.parse_args()
@@ -65,6 +70,7 @@ def main():
     from immtsf import config, ops
     from models.TimeLLM import TimeLLM
     dev = torch.device("cuda:0")
+    config.frozen_products = args.products
     B = args.batch
     torch.manual_seed(0)
     m = TimeLLM(types.SimpleNamespace(
@@ -189,7 +195,7 @@ def main():
         config.timellm_reprogram_fused = default
     for prec in (() if (args.prompt or args.reprogram) else ("fp32", "bf16")):
         config.precision = prec
-        line = {"tool": "timellm_bench", "precision": prec, "B": B, "layers": layers, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
+        line = {"tool": "timellm_bench", "precision": prec, "products": args.products, "B": B, "layers": layers, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
                 "passes": args.passes}
         if llama:       # the fused plan: 9 launches a layer + 3 for the last layer's tail queries + table and final norm;
             #             10 a layer backward (the attention backward is two) + the final norm's
@@ -211,6 +217,7 @@ def main():
                 line[f"{what}_{name}_ms_passes"] = [round(v, 3) for v in t[fused]]
             line[f"{what}_speedup"] = round(min(t[False]) / min(t[True]), 2)
         config.timellm_fused = True
+        line["split_product_calls"] = ops.split_product_calls
         print(json.dumps(line), flush=True)
         lines.append(json.dumps(line))
     if args.out:
