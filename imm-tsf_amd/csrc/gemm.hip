@@ -670,6 +670,7 @@ __global__ __launch_bounds__((SPEC ? 2 : 1) * WM * WN * 64) void gemm_kernel(con
 }
 
 thread_local long g_last_grid_threads = 0;   // for the timing tap: lets bench.py match a launch with rocprof's Grid_Size
+thread_local int g_last_kernel = 0;          // immtsf_debug_last_gemm_launch: which kernel the launchers of gemm*.hip chose last
 
 template <bool BF16, int BM, int BN, int BK, int WM, int WN, bool SPEC = false, bool BBF = false>
 int launch_cfg(int layout, const GemmArgs& g, int Mmax, int splits, hipStream_t stream) {
@@ -698,6 +699,11 @@ int g_variant = 0, g_splitk = 0, g_xcd = 1, g_dbg = 0, g_tn_spec = 1, g_xcd2d = 
 }  // namespace
 
 void immtsf_gemm_note_grid(long threads) { g_last_grid_threads = threads; }
+void immtsf_gemm_note_kernel(int code) { g_last_kernel = code; }
+extern "C" int immtsf_debug_last_gemm_launch(int64_t* grid_threads) {
+    if (grid_threads) *grid_threads = g_last_grid_threads;
+    return g_last_kernel;
+}
 
 extern int g_immtsf_ttcn_fused;      // ttcn.hip
 extern int g_immtsf_ttcn_bwd_grid;   // ttcn_full.hip
@@ -981,6 +987,8 @@ static int launch_gemm_impl(int layout, int precision, GemmArgs& g, hipStream_t 
             const long thr = (long)g.M * (g.N / 4);
             const dim3 grid((unsigned)((thr + 255) / 256));
             const int fd = g.row_flag_div > 0 ? g.row_flag_div : 1;
+            g_last_grid_threads = (long)grid.x * 256;
+            g_last_kernel = 1800;
 #define IMMTSF_SKINNY_K(TB, KB)                                                                                                      \
     hipLaunchKernelGGL((skinny_k_kernel<TB, KB>), grid, dim3(256), 0, stream, g.p[0].A, g.lda, g.p[0].B, g.ldb, g.p[0].C, g.ldc, g.p[0].bias, \
                        g.M, g.N, g.alpha, g.row_flag, fd)
@@ -991,6 +999,8 @@ static int launch_gemm_impl(int layout, int precision, GemmArgs& g, hipStream_t 
             return IMMTSF_OK;
         }
         if (al16 && layout == GEMM_NN && (g.N == 8 || g.N == 16) && g.K >= 64 && !g.p[0].bias && !g.row_flag) {
+            g_last_grid_threads = (long)cdiv(g.M, 4) * 256;
+            g_last_kernel = 1801;
             if (g.N == 8)
                 hipLaunchKernelGGL(skinny_n_kernel<8>, dim3(cdiv(g.M, 4)), dim3(256), 0, stream, g.p[0].A, g.lda, g.p[0].B, g.ldb, g.p[0].C, g.ldc,
                                    g.M, g.K, g.alpha, g.accumulate);
@@ -1121,6 +1131,7 @@ static int launch_gemm_impl(int layout, int precision, GemmArgs& g, hipStream_t 
             // tile on the straight-line loader
             if (!dyn_k && (g.K % 64) != 0 && (g.K % 32) == 0 && g.K <= 512) v = 7;
         }
+        g_last_kernel = 1000 + v + (bbf ? 100 : 0);
         switch (v) {
             case 1: return launch_cfg<true, 64, 64, 64, 2, 2>(layout, g, Mmax, splits, stream);
             case 2: return launch_cfg<true, 64, 64, 128, 2, 2>(layout, g, Mmax, splits, stream);
@@ -1149,6 +1160,7 @@ static int launch_gemm_impl(int layout, int precision, GemmArgs& g, hipStream_t 
     }
     if (precision == 0) {
         const long tiles128 = (long)cdiv(Mmax, 128) * cdiv(g.N, 128) * nbz;
+        g_last_kernel = tiles128 >= 512 ? 1901 : 1900;
         if (tiles128 >= 512) return launch_cfg<false, 128, 128, 16, 2, 2>(layout, g, Mmax, splits, stream);
         return launch_cfg<false, 64, 64, 16, 2, 2>(layout, g, Mmax, splits, stream);
     }

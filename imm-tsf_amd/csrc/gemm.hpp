@@ -93,6 +93,10 @@ const void* immtsf_twin_lookup(const float* p, size_t min_elems);
 // does not implement (batched form, TN with a row map, unaligned operands): the caller then uses immtsf_launch_gemm.
 bool immtsf_gemm2_supported(int layout, const GemmArgs& g);
 void immtsf_gemm_note_grid(long threads);      // timing tap: threads of the launch just made
+// immtsf_debug_last_gemm_launch: the kernel the launcher chose.  gemm.hip 1000 + variant (+ 100: B from its bf16 twin), 1900 / 1901 the fp32
+// 64 / 128 tile, 1800 / 1801 skinny_k / skinny_n; gemm2.hip 2000 + variant, 2900 / 2901 grouped 64 / 128; gemm3.hip 3000 / 3001 / 3002 the
+// 128x256 / 256x256 / 256x192 tile, 3010 the split TN
+void immtsf_gemm_note_kernel(int code);
 int immtsf_launch_gemm2(int layout, GemmArgs& g, hipStream_t stream);
 // several TN products of different shapes in one launch (64 x 64 K-group tiles); IMMTSF_EUNSUPPORTED: launch them one by one
 int immtsf_launch_gemm2_group_tn(GemmArgs* list, int n, hipStream_t stream);

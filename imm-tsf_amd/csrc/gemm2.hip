@@ -616,6 +616,7 @@ int immtsf_launch_gemm2(int layout, GemmArgs& g, hipStream_t stream) {
         // 9.7 on 64x64w8, 17.5 in the step with the device-side row count -- and is a tool-only variant now)
         else v = 9;                                               // 64x64, 8 waves, 4 stages, two workgroups per CU
     }
+    immtsf_gemm_note_kernel(2000 + v);
     switch (v) {
         case 1: return launch2<64, 64, 2, 2, 4>(layout, g, Mmax, splits, stream);
         case 2: return launch2<64, 96, 2, 2, 4>(layout, g, Mmax, splits, stream);
@@ -702,6 +703,7 @@ int immtsf_launch_gemm2_group_tn(GemmArgs* list, int n, hipStream_t stream) {
     for (int i = n + 1; i <= G2_GROUP_MAX; ++i) gg.tile0[i] = tiles;
     gg.n = n;
     immtsf_gemm_note_grid((long)tiles * (gt == 128 ? 512 : 1024));
+    immtsf_gemm_note_kernel(gt == 128 ? 2901 : 2900);
     if (gt == 128)
         hipLaunchKernelGGL((gemm2_group_kernel<true, true, 128, 128, 2, 2, 2, 2>), dim3(tiles), dim3(512), 0, stream, gg);
     else

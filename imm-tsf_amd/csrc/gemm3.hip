@@ -739,6 +739,7 @@ int immtsf_launch_gemm3(int layout, const void* A, int lda, const void* B, int l
     if (!dyn_rows && nt < grid) grid = (int)((nt + 7) / 8 * 8);
     grid = (grid + 7) / 8 * 8;
     immtsf_gemm_note_grid((long)grid * 512);
+    immtsf_gemm_note_kernel(bn == 192 ? 3002 : bm == 256 ? 3001 : 3000);
 #define G3_LAUNCH(TA_, TB_) (bn == 192 ? launch3_out<TA_, TB_, 256, 192>(g, grid, stream) \
                             : bm == 256 ? launch3_out<TA_, TB_, 256>(g, grid, stream) : launch3_out<TA_, TB_, 128>(g, grid, stream))
     switch (layout) {
@@ -808,6 +809,7 @@ int immtsf_launch_gemm3_tn(const void* A, int lda, const void* B, int ldb, float
     int grid = g3_grid > 0 ? g3_grid : 256;
     if (items < grid) grid = (int)((items + 7) / 8 * 8);
     immtsf_gemm_note_grid((long)grid * 512);
+    immtsf_gemm_note_kernel(3010);
     hipLaunchKernelGGL((gemm3_kernel<true, true, 256, 1, 0, 0, true>), dim3(grid), dim3(512), 0, stream, g);
     IMMTSF_LAUNCH_CHECK();
     const long threads = (long)M * (N / 4) + (bias_grad ? M : 0);

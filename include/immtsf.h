@@ -1556,7 +1556,10 @@ int immtsf_embed_backward(int32_t mode, const float* x, int32_t R, int32_t L, in
  * ldch).  layout 0 NT: C = A(M,K) B(N,K)^T (a linear layer's forward, layers/<module>.py nn.Linear call sites and
  * fusions/<module>.py projections); 1 NN: C = A(M,K) B(K,N) (its data gradient); 2 TN: C = A(K,M)^T B(K,N) (its weight
  * gradient; bias_grad (M) = column sums of A when given).  dyn: optional device int32 overriding M (dyn_which 0, NT/NN)
- * or K (dyn_which 1, TN) -- the ragged note count; a_rowmap: optional source row per logical row of A (NT/NN).
+ * or K (dyn_which 1, TN) -- the ragged note count; a_rowmap: optional source row per logical row of A (NT/NN).  With a device-side
+ * M, rows m >= *dyn of C / Ch are NOT written (they keep what they held) and rows of A that no logical row below *dyn names are not
+ * read into any result; with a device-side K, rows k >= *dyn of A and B are not.  Columns n >= N of a pitched C / Ch (ldc, ldch > N)
+ * are never written.  bias_grad carries the factor alpha, like C.  Ch is the round-to-nearest-even bf16 image of the fp32 result.
  * IMMTSF_EUNSUPPORTED: operands not 16-byte aligned / leading dimensions not multiples of 8 / K (NT, NN) or M, N (TN)
  * not multiples of 8. */
 int immtsf_gemm_bf16(int32_t layout, const void* A, int32_t lda, const void* B, int32_t ldb, float* C, int32_t ldc, void* Ch,
@@ -1577,7 +1580,9 @@ int immtsf_debug_gemm2_config(int32_t variant, int32_t splitk, int32_t xcd);
  * attn in-proj, fusions/MMF_XAttn_Add.py:36-47).  One 512-thread workgroup per CU walks 256 x 256 (or 128 x 256) tiles;
  * results as fp32 (C, may be NULL) and/or bf16 (Ch, may be NULL), x = rowflag(alpha * acc + bias) + add_vec, where
  * row_flag is int32 per group of row_flag_div rows (zero: the rows are zeroed before add_vec).  dyn_rows: optional device
- * int32 overriding M (NT / NN).  IMMTSF_EUNSUPPORTED (use immtsf_gemm_bf16): K <= 64, act != 0, misaligned operands. */
+ * int32 overriding M (NT / NN): rows m >= *dyn_rows of C / Ch keep what they held, rows of A from *dyn_rows on reach no result, and
+ * row_flag needs (*dyn_rows - 1) / row_flag_div + 1 entries.  IMMTSF_EUNSUPPORTED (use immtsf_gemm_bf16): K <= 64, act != 0,
+ * misaligned operands. */
 int immtsf_gemm3_bf16(int32_t layout, const void* A, int32_t lda, const void* B, int32_t ldb, float* C, int32_t ldc, void* Ch,
                       int32_t ldch, const float* bias, const float* add_vec, const int32_t* row_flag, int32_t row_flag_div,
                       int32_t M, int32_t N, int32_t K, float alpha, int32_t act, const int32_t* dyn_rows, immtsf_stream_t stream);
@@ -1591,6 +1596,12 @@ int immtsf_gemm3_tn_bf16(const void* A, int32_t lda, const void* B, int32_t ldb,
                          immtsf_stream_t stream);
 /* tuning aid for tools/gemm3_bench.py: force the tile height (256 / 128, 0 = heuristic) and the grid (0 = 256 workgroups) */
 int immtsf_debug_gemm3_config(int32_t bm, int32_t grid);
+/* test aid (tests/test_gpu_gemm_paths.py): which kernel the GEMM launchers chose for the calling thread's last product -- the entries
+ * above that do not pass through the timing tap included -- and, in *grid_threads (may be NULL), the threads of its grid.  Codes:
+ * csrc/gemm.hip 1000 + tile variant (+ 100 when B came from its bf16 twin), 1900 / 1901 the fp32 64 / 128 tile, 1800 / 1801 the skinny-K /
+ * skinny-N kernels; csrc/gemm2.hip 2000 + tile variant, 2900 / 2901 the grouped launch on 64 / 128 tiles; csrc/gemm3.hip 3000 / 3001 /
+ * 3002 the 128 x 256 / 256 x 256 / 256 x 192 tile, 3010 the split TN.  0: none yet.  linear_small.hip is not a GEMM launcher. */
+int immtsf_debug_last_gemm_launch(int64_t* grid_threads);
 
 #ifdef __cplusplus
 }
