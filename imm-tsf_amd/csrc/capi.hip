@@ -332,6 +332,31 @@ int immtsf_adam_range(float* param, float* grad, const void* grad_h, float* exp_
                              static_cast<hipStream_t>(stream));
 }
 
+int immtsf_adam_prepare_scaled(const float* grad, const void* grad_h, uint64_t n, float* norm_scratch, int64_t* step_dev,
+                               uint64_t* dropout_step_dev, int32_t* pending, const int32_t* err, const void* guard_h, const float* guard_f,
+                               int32_t* skip_out, const float* grad_scale, const float* found_inf_in, float* found_inf_out, float max_norm,
+                               immtsf_stream_t stream) {
+    if ((!grad && !grad_h) || !norm_scratch) return IMMTSF_EINVAL;
+    return launch_adam_prepare_scaled(grad, grad_h, (size_t)n, norm_scratch, reinterpret_cast<long long*>(step_dev),
+                                      reinterpret_cast<unsigned long long*>(dropout_step_dev), pending, err, guard_h, guard_f, skip_out,
+                                      grad_scale, found_inf_in, found_inf_out, max_norm, static_cast<hipStream_t>(stream));
+}
+
+int immtsf_adam_range_scaled(float* param, float* grad, const void* grad_h, float* exp_avg, float* exp_avg_sq, uint64_t n, uint64_t lo,
+                             uint64_t hi, float lr, float beta1, float beta2, float eps, float weight_decay, const int64_t* step_dev,
+                             const float* norm_scratch, int32_t zero_grad, const int32_t* skip, immtsf_stream_t stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || !norm_scratch || !step_dev || hi > n || lo > hi || (lo & 7)) return IMMTSF_EINVAL;
+    return launch_adam_range(param, grad, grad_h, exp_avg, exp_avg_sq, (size_t)n, (size_t)lo, (size_t)hi, lr, beta1, beta2, eps,
+                             weight_decay, reinterpret_cast<const long long*>(step_dev), 0.f, norm_scratch, zero_grad ? 1 : 0, skip,
+                             static_cast<hipStream_t>(stream), true);
+}
+
+int immtsf_loss_scale_update(float* scale, int32_t* growth_tracker, const float* found_inf, float growth, float backoff, int32_t interval,
+                             immtsf_stream_t stream) {
+    if (!scale || !growth_tracker || !found_inf || interval < 1) return IMMTSF_EINVAL;
+    return launch_loss_scale_update(scale, growth_tracker, found_inf, growth, backoff, interval, static_cast<hipStream_t>(stream));
+}
+
 int immtsf_guard_pack(const int32_t* err, void* slot, int32_t is_bf16, immtsf_stream_t stream) {
     if (!err || !slot) return IMMTSF_EINVAL;
     return launch_guard_pack(err, slot, is_bf16 ? 1 : 0, static_cast<hipStream_t>(stream));

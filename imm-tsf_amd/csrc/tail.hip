@@ -339,7 +339,113 @@ __global__ void guard_pack_kernel(const int* err, void* slot, int is_bf16) {
     else *static_cast<float*>(slot) = v;
 }
 
+// ---- the same step on a gradient stored TIMES A LOSS SCALE (torch.amp.GradScaler around main.py:1080-1091) ----------------------
+// norm_scratch of the loss-scaled entry points (immtsf_adam_prepare_scaled / _range_scaled), in floats: the 1024 partial sums, one
+// non-finite word per workgroup of the prepare pass, then what its last workgroup leaves for the range updates -- the clip coefficient,
+// the reciprocal of the loss scale, the step decision -- and the ticket that finds that last workgroup (zero between calls)
+constexpr int AMP_FLAGS = 1024, AMP_COEF = 2048, AMP_INV = 2049, AMP_SKIP = 2050, AMP_TICKET = 2051;    // < IMMTSF_AMP_SCRATCH_FLOATS
+
+// magnitude bits of a float: >= 0x7f800000 <=> inf or NaN.  One v_and + one v_max per element on a pass that waits for memory
+__device__ __forceinline__ unsigned int mag_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+// a word another workgroup of this launch wrote before it drew its ticket
+__device__ __forceinline__ float peer_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// adam_prepare_kernel for a scaled gradient: the same 1024 partial sums in the same order over the gradient AS STORED, every element
+// tested for inf / NaN on the way (the sum cannot tell: finite elements may overflow it), one non-finite word per workgroup beside
+// its partial.  The workgroup that finishes last (ticket counter, as mse_counted_kernel) folds both -- the partials exactly as the
+// head of adam_kernel does, so that coef has the same bits -- and takes the step decision: adam_prepare_kernel's conditions, or
+// *found_inf_in != 0, or a non-finite element (then *found_inf_out = 1).  It leaves coef = min(1, max_norm / (norm + 1e-6)), the
+// float-rounded double reciprocal of *grad_scale (torch's _unscale_grads_) and the decision behind the partials
+__global__ __launch_bounds__(256) void adam_prepare_scaled_kernel(const float* __restrict__ g, const bf16_t* __restrict__ gh, size_t n, int vec,
+                                                                   float* scratch, long long* step_dev, unsigned long long* drop_dev,
+                                                                   int* pending, const int* err, const bf16_t* guard_h, const float* guard_f,
+                                                                   int* skip_out, const float* grad_scale, const float* found_inf_in,
+                                                                   float* found_inf_out, float max_norm) {
+    __shared__ float red[17];                  // [16]: this workgroup drew the last ticket
+    float a = 0.f;
+    unsigned int mx = 0u;
+    const size_t stride = (size_t)gridDim.x * 256, t0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (gh) {
+        const size_t n8 = vec ? n >> 3 : 0;
+        for (size_t i = t0; i < n8; i += stride) {
+            const bf16x8 x = reinterpret_cast<const bf16x8*>(gh)[i];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { const float f = (float)x[k]; a = fmaf(f, f, a); mx = max(mx, mag_bits(f)); }
+        }
+        for (size_t i = (n8 << 3) + t0; i < n; i += stride) { const float f = (float)gh[i]; a = fmaf(f, f, a); mx = max(mx, mag_bits(f)); }
+    } else {
+        const size_t n4 = vec ? n >> 2 : 0;
+        for (size_t i = t0; i < n4; i += stride) {
+            const float4 x = reinterpret_cast<const float4*>(g)[i];
+            a = fmaf(x.x, x.x, fmaf(x.y, x.y, fmaf(x.z, x.z, fmaf(x.w, x.w, a))));
+            mx = max(max(mx, mag_bits(x.x)), max(max(mag_bits(x.y), mag_bits(x.z)), mag_bits(x.w)));
+        }
+        for (size_t i = (n4 << 2) + t0; i < n; i += stride) { a = fmaf(g[i], g[i], a); mx = max(mx, mag_bits(g[i])); }
+    }
+    a = block_sum(a, red);
+    const float bad = block_sum(mx >= 0x7f800000u ? 1.f : 0.f, red);        // a count of at most 256: exact
+    if (threadIdx.x == 0) {
+        scratch[blockIdx.x] = a;
+        scratch[AMP_FLAGS + blockIdx.x] = bad != 0.f ? 1.f : 0.f;
+        __threadfence();
+        red[16] = atomicAdd(reinterpret_cast<unsigned int*>(scratch) + AMP_TICKET, 1u) == gridDim.x - 1 ? 1.f : 0.f;
+    }
+    __syncthreads();
+    if (red[16] == 0.f) return;
+    if (threadIdx.x == 0) __threadfence();
+    __syncthreads();
+    float s = 0.f, f = 0.f;
+    for (int i = threadIdx.x; i < 1024; i += 256) {
+        s += peer_load(scratch + i);
+        f += peer_load(scratch + AMP_FLAGS + i);
+    }
+    const float total = sqrtf(block_sum(s, red));
+    const float nbad = block_sum(f, red);
+    if (threadIdx.x == 0) {
+        int skip = 0;
+        if (pending) { if (*pending == 0) skip = 1; *pending = 0; }
+        if (err && *err) skip = 1;
+        if (guard_h && (float)guard_h[0] != 0.f) skip = 1;
+        if (guard_f && guard_f[0] != 0.f) skip = 1;
+        if ((found_inf_in && found_inf_in[0] != 0.f) || nbad != 0.f) {
+            skip = 1;
+            if (found_inf_out) found_inf_out[0] = 1.f;
+        }
+        float coef = 1.f;
+        if (max_norm > 0.f) coef = fminf(1.f, max_norm / (total + 1e-6f));
+        scratch[AMP_COEF] = coef;
+        scratch[AMP_INV] = grad_scale ? (float)(1.0 / (double)grad_scale[0]) : 1.f;
+        reinterpret_cast<int*>(scratch)[AMP_SKIP] = skip;
+        if (skip_out) *skip_out = skip;
+        if (step_dev && !skip) step_dev[0] += 1;
+        if (drop_dev) drop_dev[0] += 1;
+        reinterpret_cast<unsigned int*>(scratch)[AMP_TICKET] = 0u;
+    }
+}
+
+// torch's _amp_update_scale_ for callers of the C ABI that have no GradScaler: back off on a skipped step, grow after `interval`
+// clean ones in a row (never to inf)
+__global__ void loss_scale_update_kernel(float* scale, int* growth_tracker, const float* found_inf, float growth, float backoff, int interval) {
+    if (found_inf[0] != 0.f) {
+        scale[0] *= backoff;
+        growth_tracker[0] = 0;
+        return;
+    }
+    const int ok = growth_tracker[0] + 1;
+    if (ok == interval) {
+        const float grown = scale[0] * growth;
+        if (isfinite(grown)) scale[0] = grown;
+        growth_tracker[0] = 0;
+    } else {
+        growth_tracker[0] = ok;
+    }
+}
+
 // (g and gz may be the same buffer -- read, then zeroed: neither is declared __restrict__)
+// SCALED: the gradient is stored times a loss scale: clip coefficient, 1 / scale and the step decision are read from behind the
+// partials (adam_prepare_scaled_kernel left them there) and the effective gradient is fl(fl(g coef) / scale) -- torch's order, clip
+// then unscale
+template <bool SCALED>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* g, float* __restrict__ m,
                                                     float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
                                                     float wd, float bc1, float bc2s, float max_norm,
@@ -349,7 +455,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     // gz != null (== g): the gradient is left zero behind the update -- the next step's zero-fill rides on this pass
     // gh != null: the gradient is read from its bf16 wire image (what a bf16 all-reduce left behind) instead of g
     __shared__ float red[16];
-    if (skip && *skip) {          // dropped step (see sqnorm_partial_kernel): only the zero-fill happens
+    bool drop = skip && *skip;
+    if constexpr (SCALED) drop = drop || reinterpret_cast<const int*>(part)[AMP_SKIP] != 0;
+    if (drop) {                   // dropped step (see sqnorm_partial_kernel): only the zero-fill happens
         if (gz) {
             const size_t stride = (size_t)gridDim.x * 256;
             for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) gz[i] = 0.f;
@@ -361,14 +469,20 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         bc1 = 1.f - powf(b1, st);
         bc2s = sqrtf(1.f - powf(b2, st));
     }
-    float a = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) a += part[i];
-    const float total = sqrtf(block_sum(a, red));
-    float coef = 1.f;
-    if (max_norm > 0.f) coef = fminf(1.f, max_norm / (total + 1e-6f));
+    float coef = 1.f, inv_scale = 1.f;
+    if constexpr (SCALED) {
+        coef = part[AMP_COEF];
+        inv_scale = part[AMP_INV];
+    } else {
+        float a = 0.f;
+        for (int i = threadIdx.x; i < nparts; i += 256) a += part[i];
+        const float total = sqrtf(block_sum(a, red));
+        if (max_norm > 0.f) coef = fminf(1.f, max_norm / (total + 1e-6f));
+    }
     const float step = lr / bc1;
     auto upd = [&](float gi, float pi, float& mi, float& vi) -> float {
         gi *= coef;
+        if constexpr (SCALED) gi *= inv_scale;
         if (wd != 0.f) gi = fmaf(wd, pi, gi);
         mi = fmaf(b1, mi, (1.f - b1) * gi);
         vi = fmaf(b2, vi, (1.f - b2) * gi * gi);
@@ -586,7 +700,7 @@ int launch_adam(float* param, const float* grad, float* m, float* v, size_t n, f
     IMMTSF_LAUNCH_CHECK();
     const float bc1 = 1.f - powf(b1, (float)step), bc2s = sqrtf(1.f - powf(b2, (float)step));
     const unsigned blocks = (unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, param, grad, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, max_norm,
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, s, param, grad, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, max_norm,
                        norm_scratch, nparts, (const long long*)nullptr, reinterpret_cast<bf16_t*>(twin), vec, (float*)nullptr, (const int*)nullptr);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
@@ -609,7 +723,7 @@ int launch_adam_apply(float* param, const float* grad, float* m, float* v, size_
     const int vec = adam_vec_ok(param, grad, m, v, twin);
     const float bc1 = step_dev ? 1.f : 1.f - powf(b1, (float)step), bc2s = step_dev ? 1.f : sqrtf(1.f - powf(b2, (float)step));
     const unsigned blocks = (unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, param, grad, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, max_norm,
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, s, param, grad, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s, max_norm,
                        norm_scratch, 1024, step_dev, reinterpret_cast<bf16_t*>(twin), vec, (float*)nullptr, (const int*)nullptr);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
@@ -625,7 +739,7 @@ int launch_adam_dev(float* param, const float* grad, float* m, float* v, size_t 
     hipLaunchKernelGGL(sqnorm_partial_kernel, dim3(nparts), dim3(256), 0, s, grad, n, vec, norm_scratch, step_dev, drop_dev, skip);
     IMMTSF_LAUNCH_CHECK();
     const unsigned blocks = (unsigned)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, param, grad, m, v, n, lr, b1, b2, eps, wd, 1.f, 1.f, max_norm,
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, s, param, grad, m, v, n, lr, b1, b2, eps, wd, 1.f, 1.f, max_norm,
                        norm_scratch, nparts, (const long long*)step_dev, reinterpret_cast<bf16_t*>(twin), vec,
                        zero_grad ? const_cast<float*>(grad) : nullptr, skip);
     IMMTSF_LAUNCH_CHECK();
@@ -643,7 +757,7 @@ int launch_adam_prepare(const float* grad, const void* grad_h, size_t n, float* 
 }
 int launch_adam_range(float* param, float* grad, const void* grad_h, float* m, float* v, size_t n, size_t lo, size_t hi, float lr, float b1,
                       float b2, float eps, float wd, const long long* step_dev, float max_norm, const float* norm_scratch, int zero_grad,
-                      const int* skip, hipStream_t s) {
+                      const int* skip, hipStream_t s, bool scaled) {
     if (hi <= lo) return IMMTSF_OK;
     const bf16_t* twin0 = static_cast<const bf16_t*>(immtsf_twin_lookup(param, n));
     bf16_t* twin = twin0 ? const_cast<bf16_t*>(twin0) + lo : nullptr;
@@ -651,8 +765,30 @@ int launch_adam_range(float* param, float* grad, const void* grad_h, float* m, f
     const size_t k = hi - lo;
     const int vec = adam_vec_ok(param + lo, grad + lo, m + lo, v + lo, twin) && (reinterpret_cast<uintptr_t>(gh) & 7) == 0;
     const unsigned blocks = (unsigned)((k / 4 + 255) / 256 > 2048 ? 2048 : (k / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, s, param + lo, grad + lo, m + lo, v + lo, k, lr, b1, b2, eps, wd, 1.f, 1.f,
-                       max_norm, norm_scratch, 1024, step_dev, twin, vec, zero_grad ? grad + lo : nullptr, skip, gh);
+    if (scaled)
+        hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, s, param + lo, grad + lo, m + lo, v + lo, k, lr, b1, b2, eps, wd, 1.f, 1.f,
+                           max_norm, norm_scratch, 1024, step_dev, twin, vec, zero_grad ? grad + lo : nullptr, skip, gh);
+    else
+        hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, s, param + lo, grad + lo, m + lo, v + lo, k, lr, b1, b2, eps, wd, 1.f, 1.f,
+                           max_norm, norm_scratch, 1024, step_dev, twin, vec, zero_grad ? grad + lo : nullptr, skip, gh);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+int launch_adam_prepare_scaled(const float* grad, const void* grad_h, size_t n, float* norm_scratch, long long* step_dev,
+                               unsigned long long* drop_dev, int* pending, const int* err, const void* guard_h, const float* guard_f,
+                               int* skip_out, const float* grad_scale, const float* found_inf_in, float* found_inf_out, float max_norm,
+                               hipStream_t s) {
+    const uintptr_t a = grad_h ? reinterpret_cast<uintptr_t>(grad_h) : reinterpret_cast<uintptr_t>(grad);
+    const int vec = (a & 15) == 0;
+    hipLaunchKernelGGL(adam_prepare_scaled_kernel, dim3(1024), dim3(256), 0, s, grad, static_cast<const bf16_t*>(grad_h), n, vec, norm_scratch,
+                       step_dev, drop_dev, pending, err, static_cast<const bf16_t*>(guard_h), guard_f, skip_out, grad_scale, found_inf_in,
+                       found_inf_out, max_norm);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+int launch_loss_scale_update(float* scale, int* growth_tracker, const float* found_inf, float growth, float backoff, int interval,
+                             hipStream_t s) {
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(1), 0, s, scale, growth_tracker, found_inf, growth, backoff, interval);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
 }

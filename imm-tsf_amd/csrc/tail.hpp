@@ -51,7 +51,15 @@ int launch_adam_prepare(const float* grad, const void* grad_h, size_t n, float* 
                         int* pending, const int* err, const void* guard_h, const float* guard_f, int* skip_out, hipStream_t s);
 int launch_adam_range(float* param, float* grad, const void* grad_h, float* m, float* v, size_t n, size_t lo, size_t hi, float lr, float b1,
                       float b2, float eps, float wd, const long long* step_dev, float max_norm, const float* norm_scratch, int zero_grad,
-                      const int* skip, hipStream_t s);
+                      const int* skip, hipStream_t s,
+                      bool scaled = false);      // scaled: clip coefficient, 1 / loss scale and the decision come from launch_adam_prepare_scaled
+// ... on a gradient stored times a loss scale (include/immtsf.h immtsf_adam_prepare_scaled / _range_scaled / immtsf_loss_scale_update)
+int launch_adam_prepare_scaled(const float* grad, const void* grad_h, size_t n, float* norm_scratch, long long* step_dev,
+                               unsigned long long* drop_dev, int* pending, const int* err, const void* guard_h, const float* guard_f,
+                               int* skip_out, const float* grad_scale, const float* found_inf_in, float* found_inf_out, float max_norm,
+                               hipStream_t s);
+int launch_loss_scale_update(float* scale, int* growth_tracker, const float* found_inf, float growth, float backoff, int interval,
+                             hipStream_t s);
 int launch_guard_pack(const int* err, void* slot, int is_bf16, hipStream_t s);
 
 // dst[i] = bf16(src[i]) (round to nearest even): refresh of a bf16 twin

@@ -14,6 +14,7 @@ from fusions.MMF_XAttn_Add import MMF_XAttn_Add
 from fusions.TTF_RecAvg import TTF_RecAvg
 from fusions.TTF_T2V_XAttn import TTF_T2V_XAttn
 from immtsf import config
+from immtsf.dropin import fp32_entry as _fp32_entry
 
 _TTF_CLASSES = {"TTF_RecAvg": TTF_RecAvg, "TTF_T2V_XAttn": TTF_T2V_XAttn}
 _MMF_CLASSES = {"MMF_GR_Add": MMF_GR_Add, "MMF_XAttn_Add": MMF_XAttn_Add}
@@ -87,6 +88,7 @@ class FusionModel(nn.Module):
         E_txt, M_txt = self.ttf(notes_input, tau, t_hat)
         return E_txt, M_txt, (self.mmf.project_kv(E_txt) if hasattr(self.mmf, "project_kv") else None)
 
+    @_fp32_entry
     def forward(self, notes_input, tau, t_hat, Y_ts):
         sync = config.nan_check == "sync"
         if sync and torch.isnan(Y_ts).any():

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libimmtsf_hip.so")
 
 ABI_VERSION = 7
+AMP_SCRATCH_FLOATS = 2056  # IMMTSF_AMP_SCRATCH_FLOATS: norm_scratch of immtsf_adam_prepare_scaled / _range_scaled (zero-initialised)
 FORM_NO_PROJ = 16        # immtsf_fusion_cfg.form bit (IMMTSF_FORM_NO_PROJ)
 FORM_HALF_OUT = 32       # ... IMMTSF_FORM_HALF_OUT: the fp32 output is not written, its bf16 image is all the consumer reads
 FORM_LOWRANK_OUT = 64    # ... IMMTSF_FORM_LOWRANK_OUT: dZ = dP Wc is not written, the producer's backward takes (dP, Wc)
@@ -490,6 +491,11 @@ _PROTOS = {
     "immtsf_flag_wait_ge_multi": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_stream]),
     "immtsf_adam_range": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
                                     C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_float, c_f32p, C.c_int32, C.c_void_p, c_stream]),
+    "immtsf_adam_prepare_scaled": (C.c_int, [c_f32p, C.c_void_p, C.c_uint64, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_float, c_stream]),
+    "immtsf_adam_range_scaled": (C.c_int, [c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_float,
+                                           C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, c_f32p, C.c_int32, C.c_void_p, c_stream]),
+    "immtsf_loss_scale_update": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_float, C.c_float, C.c_int32, c_stream]),
     "immtsf_guard_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_stream]),
     "immtsf_seam_route": (C.c_int, [C.c_int32] * 3),
     "immtsf_seam_p_bf16": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, c_stream]),

@@ -200,3 +200,7 @@ neuralflow_fused = os.environ.get("IMMTSF_NEURALFLOW_FUSED", "1") != "0"
 # built on the device, one id upload per epoch); IMMTSF_RESIDENT_LOADER=0: the reference module's own host loaders, when a
 # reference tree is on the path (NotImplementedError otherwise)
 resident_loader = os.environ.get("IMMTSF_RESIDENT_LOADER", "1") != "0"
+# immtsf.optim.FusedAdam under torch.amp.GradScaler takes the loss scale inside its two launches (the clip on the gradient as stored, the
+# unscale and the skip decision on the device: no foreach unscale, no host read of found_inf); IMMTSF_OPTIM_AMP=0: GradScaler's generic
+# route (it unscales every .grad, reads found_inf on the host, then calls step()) -- read when the optimizer is built
+optim_amp = os.environ.get("IMMTSF_OPTIM_AMP", "1") != "0"

@@ -112,3 +112,36 @@ class _Overlay(importlib.abc.MetaPathFinder):
 def overlay_module(fullname: str, target: str) -> None:
     if not any(isinstance(f, _Overlay) and f.fullname == fullname for f in sys.meta_path):
         sys.meta_path.insert(0, _Overlay(fullname, target))
+
+
+# ---- torch.autocast around the drop-in entry points -------------------------------------------------------------------------------
+# main.py --use_amp runs the step inside `autocast()` (main.py:1080-1091).  This build's precision is immtsf.config.precision's: its
+# kernels take fp32 tensors and choose their own MFMA operands, and it has no fp16 path.  Autocast would only reach the torch ops
+# BETWEEN the kernels (an fp16 linear here, a bf16 matmul there) and feed half tensors into autograd Functions that expect fp32, so the
+# entry points compute under autocast exactly what they compute outside it.
+
+def _to_fp32(x):
+    import torch
+    if torch.is_tensor(x):
+        return x.float() if x.dtype in (torch.float16, torch.bfloat16) else x
+    if isinstance(x, dict):
+        return {k: _to_fp32(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_to_fp32(v) for v in x)
+    return x
+
+
+def fp32_entry(fn):
+    """decorator of a drop-in entry point (lib.evaluation.compute_all_losses / evaluation, FusionModel.forward, <backbone>.forecasting):
+    inside torch.autocast the call runs with autocast disabled and half tensors among its arguments widened to fp32; outside it the
+    call is fn's own, untouched"""
+    import functools
+
+    @functools.wraps(fn)
+    def entry(*args, **kwargs):
+        import torch
+        if not torch.is_autocast_enabled("cuda"):
+            return fn(*args, **kwargs)
+        with torch.autocast("cuda", enabled=False):
+            return fn(*_to_fp32(args), **_to_fp32(kwargs))
+    return entry

@@ -12,20 +12,28 @@ leaves the clipping to that optimizer's next `step()`; any other call goes to to
 
 `install()` puts the two in torch's namespaces (`torch.optim.Adam`, `torch.nn.utils.clip_grad_norm_`) so that an unmodified script gets
 them; the drop-in `lib.evaluation` calls it on import unless IMMTSF_OPTIM_SHIM=0.  Same arithmetic as torch.optim.Adam (L2-style
-weight decay, bias corrections, eps outside the square root) -- tests/test_gpu_train.py::test_optim_shim_trains_like_torch_adam."""
+weight decay, bias corrections, eps outside the square root) -- tests/test_gpu_train.py::test_optim_shim_trains_like_torch_adam.
+
+Under `torch.amp.GradScaler` (main.py:1052, 1080-1091 with --use_amp) FusedAdam takes the loss scale itself (`_step_supports_amp_scaling`:
+`GradScaler.step` hands it `grad_scale` / `found_inf` instead of unscaling every `.grad` and reading found_inf back on the host): still two
+launches (immtsf_adam_prepare_scaled + immtsf_adam_range_scaled), the skip decided on the device.  A pending clip is taken on the gradient
+as stored -- scaled in main.py's order, unscaled when the caller ran `scaler.unscale_(opt)` first.  IMMTSF_OPTIM_AMP=0 (config.optim_amp)
+leaves the scale to torch's generic route -- tests/test_gpu_amp.py."""
 from __future__ import annotations
 
 import os
 
 import torch
 
-from . import _lib
+from . import _lib, config
 
 _torch_adam = torch.optim.Adam
 _torch_clip = torch.nn.utils.clip_grad_norm_
 
 
 class FusedAdam(torch.optim.Optimizer):
+    _step_supports_amp_scaling = True           # GradScaler.step(): hand grad_scale / found_inf to step() (not with config.optim_amp off)
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
         params = list(params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -37,8 +45,10 @@ class FusedAdam(torch.optim.Optimizer):
         self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.norm_scratch = torch.zeros(1024, dtype=torch.float32, device=dev)
+        self.norm_scratch = torch.zeros(_lib.AMP_SCRATCH_FLOATS, dtype=torch.float32, device=dev)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        if not config.optim_amp:
+            self._step_supports_amp_scaling = False
         self._views, self._gviews, off = [], [], 0
         for p in ps:
             k = p.numel()
@@ -89,12 +99,27 @@ class FusedAdam(torch.optim.Optimizer):
         lib = _lib.load()
         n = self.flat_param.numel()
         st = _lib.stream_ptr()
-        _lib.check(lib.immtsf_adam_prepare(_lib.ptr(self.flat_grad), None, n, _lib.ptr(self.norm_scratch), _lib.ptr(self.step_dev), None,
-                                           None, None, None, None, None, st), "adam_prepare")
-        _lib.check(lib.immtsf_adam_range(_lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), None, _lib.ptr(self.exp_avg),
-                                         _lib.ptr(self.exp_avg_sq), n, 0, n, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
-                                         float(g["eps"]), float(g["weight_decay"]), _lib.ptr(self.step_dev), float(self._pending_clip),
-                                         _lib.ptr(self.norm_scratch), 1, None, st), "adam_range")
+        # GradScaler.step() leaves these on the optimizer for the call: the scale the gradient is stored times (None behind the caller's
+        # own unscale_()) and torch's found_inf (either may also be the caller's own)
+        scale, found = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        if scale is None and found is None:
+            _lib.check(lib.immtsf_adam_prepare(_lib.ptr(self.flat_grad), None, n, _lib.ptr(self.norm_scratch), _lib.ptr(self.step_dev), None,
+                                               None, None, None, None, None, st), "adam_prepare")
+            _lib.check(lib.immtsf_adam_range(_lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), None, _lib.ptr(self.exp_avg),
+                                             _lib.ptr(self.exp_avg_sq), n, 0, n, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]),
+                                             float(g["eps"]), float(g["weight_decay"]), _lib.ptr(self.step_dev), float(self._pending_clip),
+                                             _lib.ptr(self.norm_scratch), 1, None, st), "adam_range")
+        else:
+            # the clip is taken on the gradient as stored (still scaled in main.py's order), the unscale follows it, a step with a
+            # non-finite gradient changes nothing but the zero-fill: all decided on the device (include/immtsf.h)
+            scale, found = (None if t is None else t.to(device=self.flat_grad.device, dtype=torch.float32) for t in (scale, found))
+            _lib.check(lib.immtsf_adam_prepare_scaled(_lib.ptr(self.flat_grad), None, n, _lib.ptr(self.norm_scratch), _lib.ptr(self.step_dev),
+                                                      None, None, None, None, None, None, _lib.ptr(scale), _lib.ptr(found), None,
+                                                      float(self._pending_clip), st), "adam_prepare_scaled")
+            _lib.check(lib.immtsf_adam_range_scaled(_lib.ptr(self.flat_param), _lib.ptr(self.flat_grad), None, _lib.ptr(self.exp_avg),
+                                                    _lib.ptr(self.exp_avg_sq), n, 0, n, float(g["lr"]), float(g["betas"][0]),
+                                                    float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), _lib.ptr(self.step_dev),
+                                                    _lib.ptr(self.norm_scratch), 1, None, st), "adam_range_scaled")
         self._pending_clip = 0.0
         self._zeroed = True
         return loss

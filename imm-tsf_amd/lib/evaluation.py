@@ -9,6 +9,7 @@ import os
 import torch
 
 from immtsf import config, step_plan
+from immtsf.dropin import fp32_entry as _fp32_entry
 from immtsf.ops import masked_mse
 
 
@@ -309,6 +310,7 @@ def check_deferred_nan(fusion=None):
             raise ValueError("MSE is NaN")
 
 
+@_fp32_entry
 def compute_all_losses(model, fusion, batch_dict, enable_text=True, use_text_embeddings=True, group=None):
     """One training-step forward: backbone forecast -> fusion -> masked MSE (lib/evaluation.py:72-164).
     The reference's per-step host syncs (NaN checks, per-row mask loop, .item()) follow immtsf.config.nan_check:
@@ -367,6 +369,7 @@ def _eval_step(model, fusion, enable_text):
     return ev
 
 
+@_fp32_entry
 def evaluation(model, fusion, dataloader, enable_text=True, use_text_embeddings=True):
     """Test/validation metrics with the reference's definitions (lib/evaluation.py:192-283): per-variable sums of the
     squared / absolute / relative errors and of the observation counts over the whole loader, then mean over the

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from immtsf import config
 from immtsf.ops import cru_scan, cru_supported, layer_norm, linear
+from immtsf.dropin import fp32_entry as _fp32_entry
 
 
 def _variance(x, kind, soft="elup1"):
@@ -324,6 +325,7 @@ class CRU(nn.Module):
         # the module itself: a .half() / .bfloat16() model, one left on another device -> composed
         return all(q.device == data.device and q.dtype == torch.float32 for q in self._scan_params())
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         core = self.cru_model_core
         cell = core._cru_layer._cell

@@ -12,6 +12,7 @@ import torch.nn as nn
 
 from immtsf import config
 from immtsf.ops import dlinear_forecast, dlinear_supported, linear
+from immtsf.dropin import fp32_entry as _fp32_entry
 from layers.Autoformer_EncDec import series_decomp
 from models._common import masked_instance_norm
 
@@ -54,6 +55,7 @@ class DLinear(nn.Module):
                 tuple(mask.shape) == (B, L, C) and tuple(tp.shape) == (B, L) and
                 dlinear_supported(self.seq_len, self.pred_len, C, self.moving_avg, self.individual))
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         B, L, C = observed_data.shape
         assert C == self.C

@@ -30,6 +30,7 @@ import torch.nn as nn
 
 from immtsf import _lib, config
 from immtsf.ops import latent_ode, latent_ode_supported
+from immtsf.dropin import fp32_entry as _fp32_entry
 
 MAX_FUSED_STEPS = 256      # LO_MAX_SUB of csrc/latent_ode.hip
 
@@ -254,6 +255,7 @@ class LatentODE(nn.Module):
         # the module itself: a .half() / .bfloat16() model, one left on another device -> composed
         return all(q.device == data.device and q.dtype == torch.float32 for q in self.latent_ode_model_core.parameters())
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         observed_data = observed_data.to(self.device).float()
         observed_tp = observed_tp.to(self.device).float()

@@ -41,6 +41,7 @@ import torch.nn.functional as F
 
 from immtsf import _lib, config
 from immtsf.ops import neural_flow, neural_flow_supported
+from immtsf.dropin import fp32_entry as _fp32_entry
 
 TIME_NETS = ("TimeLinear", "TimeTanh")
 
@@ -275,6 +276,7 @@ class NeuralFlow(nn.Module):
         # the module itself: a .half() / .bfloat16() model, one left on another device -> composed
         return all(q.device == data.device and q.dtype == torch.float32 for q in self.nf_model_core.parameters())
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         """tp_to_predict (B, Lp), observed_data (B, L, C), observed_tp (B, L), observed_mask (B, L, C) -> (B, Lp, C)"""
         observed_data = observed_data.to(self.device).float()

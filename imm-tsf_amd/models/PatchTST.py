@@ -9,6 +9,7 @@ from layers.Embed import PatchEmbedding
 from layers.SelfAttention_Family import AttentionLayer, FullAttention
 from layers.Transformer_EncDec import Encoder, EncoderLayer
 from immtsf.ops import linear
+from immtsf.dropin import fp32_entry as _fp32_entry
 from models._common import pad_history, plain_instance_norm
 
 
@@ -57,6 +58,7 @@ class PatchTST(nn.Module):
                                 head_dropout=configs.dropout)
         self.zeros_pad = torch.zeros(configs.batch_size, max(configs.input_len, configs.pred_len), configs.enc_in).to(configs.device)
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         """tp_to_predict (B,Lp); observed_data/mask (B,L,K); observed_tp (B,L) -> (B,Lp,K)"""
         tp_to_predict, data, tp, mask, Lp = pad_history(self.zeros_pad, self.input_len, self.pred_len, tp_to_predict,

@@ -15,6 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from immtsf.ops import linear
+from immtsf.dropin import fp32_entry as _fp32_entry
 from layers.MLP import TTMLayer, TTMMixerBlock
 
 
@@ -131,6 +132,7 @@ class TTM(Model):
     def mixer_blocks(self):
         return [m for m in self.modules() if isinstance(m, TTMMixerBlock)]
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         B, L, C = observed_data.shape
         assert C == self.orig_vars, f"expected {self.orig_vars} channels, got {C}"

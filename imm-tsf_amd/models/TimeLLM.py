@@ -33,6 +33,7 @@ from immtsf import config
 from immtsf.ops import (bert_body, bert_body_supported, gpt2_body, gpt2_body_supported, linear, llama_body, llama_body_supported,
                         shared_kv_attention, timellm_prompt_packed, timellm_prompt_split, timellm_prompt_supported, timellm_prototypes,
                         timellm_prototypes_pays, timellm_prototypes_supported)
+from immtsf.dropin import fp32_entry as _fp32_entry
 from layers.Embed import PatchEmbedding
 from models._common import masked_instance_norm
 
@@ -225,6 +226,7 @@ class TimeLLM(nn.Module):
             prompts.append(self._prompt_text(mins[b].tolist(), maxs[b].tolist(), meds[b].tolist(), trend[b].item() > 0, lags[b].tolist()))
         return prompts
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         B, L, N = observed_data.shape
         if L < self.input_len:

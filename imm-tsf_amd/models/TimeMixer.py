@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 from immtsf import config
 from immtsf.ops import linear, timemixer_forecast, timemixer_params, timemixer_supported
+from immtsf.dropin import fp32_entry as _fp32_entry
 from layers.Autoformer_EncDec import series_decomp
 from layers.Embed import DataEmbedding
 from layers.StandardNorm import Normalize
@@ -187,6 +188,7 @@ class TimeMixer(nn.Module):
         # the module itself: a .half() / .bfloat16() model, one left on another device, a non-contiguous parameter -> composed
         return all(q.device == data.device and q.dtype == torch.float32 and q.is_contiguous() for q in timemixer_params(self))
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         B, L, C = observed_data.shape
         assert C == self.C

@@ -13,6 +13,7 @@ import torch.nn.functional as F
 
 from immtsf.ops import (INCEPTION_MAX, conv2d_periods, conv2d_same_cl, inception_merge, inception_periods, inception_periods_ok, layer_norm, linear,
                         period_aggregate, period_rows)
+from immtsf.dropin import fp32_entry as _fp32_entry
 from layers.Conv_Blocks import Inception_Block_V1
 from layers.Embed import DataEmbedding
 from models._common import pad_history, plain_instance_norm
@@ -119,6 +120,7 @@ class TimesNet(nn.Module):
         self.projection = nn.Linear(configs.d_model, configs.c_out, bias=True)
         self.zeros_pad = torch.zeros(configs.batch_size, max(configs.input_len, configs.pred_len), configs.enc_in).to(configs.device)
 
+    @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
         tp_to_predict, data, tp, mask, Lp = pad_history(self.zeros_pad, self.input_len, self.pred_len, tp_to_predict,
                                                         observed_data, observed_tp, observed_mask)

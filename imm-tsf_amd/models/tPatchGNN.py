@@ -12,6 +12,7 @@ import math
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from immtsf.dropin import fp32_entry as _fp32_entry
 
 
 class nconv(nn.Module):
@@ -216,6 +217,7 @@ class tPatchGNN(nn.Module):
             x = self._mlp(self.temporal_agg, x.reshape(B, N, -1))
         return x
 
+    @_fp32_entry
     def forecasting(self, time_steps_to_predict, X, truth_time_steps, mask=None):
         """time_steps_to_predict (B,Lp); X, truth_time_steps, mask (B,M,L,N) -> (B,Lp,N)"""
         B, M, L, N = X.shape

@@ -1331,6 +1331,32 @@ int immtsf_adam_prepare(const float* grad, const void* grad_h, uint64_t n, float
 int immtsf_adam_range(float* param, float* grad, const void* grad_h, float* exp_avg, float* exp_avg_sq, uint64_t n, uint64_t lo,
                       uint64_t hi, float lr, float beta1, float beta2, float eps, float weight_decay, const int64_t* step_dev,
                       float max_norm, const float* norm_scratch, int32_t zero_grad, const int32_t* skip, immtsf_stream_t stream);
+/* The same two launches on a gradient that is stored TIMES A LOSS SCALE S (torch.amp.GradScaler around main.py:1080-1091, which clips
+ * before anything unscales: the norm is ||S g||).  norm_scratch: >= IMMTSF_AMP_SCRATCH_FLOATS floats, of which the word at index 2051
+ * (a ticket) must be ZERO before the first call; every call leaves it zero.  The plain entry points above use the first 1024 only.
+ *   adam_prepare_scaled: adam_prepare's pass over the gradient AS STORED -- the same 1024 partials in the same order, no atomics on
+ *     floats -- that also tests EVERY ELEMENT for inf / NaN (not the norm: finite elements can overflow the sum).  The step is dropped
+ *     under adam_prepare's conditions, or when *found_inf_in != 0, or when an element is not finite; in the latter two cases
+ *     *found_inf_out = 1.0f (it is not written otherwise: it accumulates like torch's found_inf, and may be found_inf_in itself).
+ *     Behind the partials it leaves, for adam_range_scaled: coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6f)) : 1 (torch's
+ *     clip_grad_norm_), inv_scale = (float)(1.0 / (double)*grad_scale) (torch's _unscale_grads_; grad_scale NULL: 1) and the decision.
+ *     grad_scale, found_inf_in: one device float each; all three may be NULL.
+ *   adam_range_scaled: adam_range with the effective gradient fl(fl(g coef) inv_scale) -- two fp32 roundings in torch's order, clip
+ *     then unscale -- and the decision of adam_prepare_scaled (ORed with *skip when given).  After a prepare with grad_scale NULL and a
+ *     finite gradient it equals adam_range(max_norm) bit for bit.
+ *   loss_scale_update: torch's _amp_update_scale_ as one launch, for callers without a GradScaler: *found_inf != 0: *scale *= backoff,
+ *     *growth_tracker = 0; else the tracker counts up and at `interval` clean steps in a row *scale *= growth (unless that is inf)
+ *     and the tracker restarts.  scale, found_inf: device floats; growth_tracker: device int32. */
+#define IMMTSF_AMP_SCRATCH_FLOATS 2056
+int immtsf_adam_prepare_scaled(const float* grad, const void* grad_h, uint64_t n, float* norm_scratch, int64_t* step_dev,
+                               uint64_t* dropout_step_dev, int32_t* pending, const int32_t* err, const void* guard_h, const float* guard_f,
+                               int32_t* skip_out, const float* grad_scale, const float* found_inf_in, float* found_inf_out, float max_norm,
+                               immtsf_stream_t stream);
+int immtsf_adam_range_scaled(float* param, float* grad, const void* grad_h, float* exp_avg, float* exp_avg_sq, uint64_t n, uint64_t lo,
+                             uint64_t hi, float lr, float beta1, float beta2, float eps, float weight_decay, const int64_t* step_dev,
+                             const float* norm_scratch, int32_t zero_grad, const int32_t* skip, immtsf_stream_t stream);
+int immtsf_loss_scale_update(float* scale, int32_t* growth_tracker, const float* found_inf, float growth, float backoff, int32_t interval,
+                             immtsf_stream_t stream);
 /* *slot = (*err != 0) in the gradient wire's element type (is_bf16 != 0: one bf16, else one float): the guard word of this rank,
  * written into the slot behind the last bucket so that the step's last all-reduce sums it over the ranks (see adam_prepare) */
 int immtsf_guard_pack(const int32_t* err, void* slot, int32_t is_bf16, immtsf_stream_t stream);
