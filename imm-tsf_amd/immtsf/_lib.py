@@ -366,6 +366,12 @@ _PROTOS = {
                                                                                                                c_f32p, c_f32p, c_f32p, c_f32p,
                                                                                                                c_stream]),
     "immtsf_period_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, c_stream]),
+    "immtsf_timesnet_spectrum_ok": (C.c_int, [C.c_int32] * 3),
+    "immtsf_timesnet_spectrum_fwd": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, c_f32p, c_stream]),
+    "immtsf_timesnet_spectrum_select": (C.c_int, [c_f32p, C.c_int32, C.c_int32, C.c_int32, c_f32p, C.c_void_p, c_i32p, c_i32p, c_f32p, c_f32p,
+                                                  c_stream]),
+    "immtsf_timesnet_spectrum_bwd": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_f32p,
+                                               c_stream]),
     "immtsf_conv2d_period_forward": (C.c_int, [C.c_int32, c_f32p, C.c_int32, C.c_int32, c_i32p, c_i32p, C.c_int32, C.c_int32, c_f32p, c_f32p,
                                                C.c_int32, C.c_int32, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int32, c_stream]),
     "immtsf_conv2d_periods_forward": (C.c_int, [C.c_int32, c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_i32p, c_i32p, C.c_int32, C.c_int32,

@@ -204,3 +204,8 @@ resident_loader = os.environ.get("IMMTSF_RESIDENT_LOADER", "1") != "0"
 # unscale and the skip decision on the device: no foreach unscale, no host read of found_inf); IMMTSF_OPTIM_AMP=0: GradScaler's generic
 # route (it unscales every .grad, reads found_inf on the host, then calls step()) -- read when the optimizer is built
 optim_amp = os.environ.get("IMMTSF_OPTIM_AMP", "1") != "0"
+# TimesBlock's period selection (the amplitude spectrum, the top-k, the periods and image row counts, the softmaxed weights, the
+# position-major copy of the series) as two HIP launches forward and one backward (immtsf.ops.timesnet_spectrum: csrc/timesnet_spectrum.hip,
+# a direct DFT -- no FFT library in the step) on the device-period branch wherever immtsf_timesnet_spectrum_ok allows;
+# IMMTSF_TIMESNET_SPECTRUM_FUSED=0: torch.fft.rfft / topk / softmax / pad as before -- the cross-check.  fp32 in either precision mode
+timesnet_spectrum_fused = os.environ.get("IMMTSF_TIMESNET_SPECTRUM_FUSED", "1") != "0"

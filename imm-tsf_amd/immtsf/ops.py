@@ -1665,6 +1665,81 @@ def period_rows(top, total, B):
     return period, rows
 
 
+# ---- TimesNet's period selection without an FFT library (csrc/timesnet_spectrum.hip) ----------------------------------------------------
+def timesnet_spectrum_ok(T, N, k):
+    """the shapes the spectrum kernels take (immtsf_timesnet_spectrum_ok): 2 <= T <= 512, 1 <= N <= 256, T N <= 16384, 1 <= k <=
+    min(16, T // 2)"""
+    return bool(_lib.load().immtsf_timesnet_spectrum_ok(int(T), int(N), int(k)))
+
+
+def _spectrum_forward(x, k):
+    """the two forward launches on x (B, T, N): -> (amp_mean (B, F), freq (F), top (k) int64, period (k) int32, rows (k) int32, weight (B, k),
+    w (B, k), xl (2T B, N))"""
+    if x.dim() != 3:
+        raise _lib.ImmtsfError(f"timesnet_spectrum: x (B, T, N), got {tuple(x.shape)}")
+    _need_gpu(x)
+    if x.dtype != torch.float32:
+        raise _lib.ImmtsfError(f"timesnet_spectrum: x is {x.dtype}; the kernels are fp32 in every precision mode")
+    B, T, N = x.shape
+    k = int(k)
+    if B < 1 or not timesnet_spectrum_ok(T, N, k):
+        raise _lib.ImmtsfError(f"timesnet_spectrum: B {B}, T {T}, N {N}, k {k} is outside timesnet_spectrum_ok")
+    lib = _lib.load()
+    dev, F = x.device, T // 2 + 1
+    amp_mean = torch.empty(B, F, dtype=torch.float32, device=dev)
+    freq = torch.empty(F, dtype=torch.float32, device=dev)
+    xl = torch.empty(2 * T * B, N, dtype=torch.float32, device=dev)
+    top = torch.empty(k, dtype=torch.int64, device=dev)
+    period = torch.empty(k, dtype=torch.int32, device=dev)
+    rows = torch.empty(k, dtype=torch.int32, device=dev)
+    weight = torch.empty(B, k, dtype=torch.float32, device=dev)
+    w = torch.empty(B, k, dtype=torch.float32, device=dev)
+    check(lib.immtsf_timesnet_spectrum_fwd(ptr(x), B, T, N, ptr(amp_mean), ptr(xl), stream_ptr()), "timesnet_spectrum_fwd")
+    check(lib.immtsf_timesnet_spectrum_select(ptr(amp_mean), B, T, k, ptr(freq), ptr(top), ptr(period), ptr(rows), ptr(weight), ptr(w),
+                                              stream_ptr()), "timesnet_spectrum_select")
+    return amp_mean, freq, top, period, rows, weight, w, xl
+
+
+class TimesNetSpectrumFn(torch.autograd.Function):
+    """TimesBlock's period selection as two launches forward, one backward: x (B, T, N) -> (top, period, rows, w, xl) -- the k selected
+    frequency indices (int64), their periods and image row counts (int32; ops.period_rows' values), the softmaxed per-window weights (B, k)
+    and the position-major image (2T B, N).  Differentiable in x through w and xl; top / period / rows carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, k):
+        x = _c(x)
+        _, _, top, period, rows, _, w, xl = _spectrum_forward(x, k)
+        ctx.save_for_backward(x, top, w)
+        ctx.mark_non_differentiable(top, period, rows)
+        ctx.set_materialize_grads(False)
+        return top, period, rows, w, xl
+
+    @staticmethod
+    def backward(ctx, g_top, g_period, g_rows, g_w, g_xl):
+        x, top, w = ctx.saved_tensors
+        B, T, N = x.shape
+        g_w = None if g_w is None else _c(g_w.float())
+        g_xl = None if g_xl is None else _c(g_xl.float())
+        dx = torch.empty_like(x)
+        check(_lib.load().immtsf_timesnet_spectrum_bwd(ptr(x), ptr(top), ptr(w), ptr(g_w), ptr(g_xl), B, T, N, top.numel(), ptr(dx), stream_ptr()),
+              "timesnet_spectrum_bwd")
+        return dx, None
+
+
+def timesnet_spectrum(x, k):
+    """x (B, T, N) fp32 -> (top (k) int64, period (k) int32, rows (k) int32, w (B, k), xl (2T B, N)), everything on the device: what
+    fft_for_period_device + period_rows + softmax + the padded transpose of models/TimesNet.py TimesBlock.forward compute, by a direct DFT
+    (include/immtsf.h immtsf_timesnet_spectrum_*).  Outside timesnet_spectrum_ok this raises: callers check."""
+    return TimesNetSpectrumFn.apply(x, int(k))
+
+
+def timesnet_spectrum_stats(x, k):
+    """the forward's intermediate values, for tests and tools: (amp_mean (B, F) the per-window mean amplitude over the channels, freq (F) its
+    mean over the windows with freq[0] = 0, weight (B, k) = amp_mean[:, top] before the softmax).  No gradient."""
+    amp_mean, freq, _, _, _, weight, _, _ = _spectrum_forward(_c(x.detach()), k)
+    return amp_mean, freq, weight
+
+
 def conv2d_period(x, period, rows, Weff, beff, KS, B, Lmax, act=None, precision=None, w16=None):
     return Conv2dPeriodFn.apply(x.float(), period, rows, Weff, beff, int(KS), 2 if act == "gelu" else 0, config.precision_code(precision),
                                 int(B), int(Lmax), w16)

@@ -11,8 +11,9 @@ import torch.fft
 import torch.nn as nn
 import torch.nn.functional as F
 
+from immtsf import config
 from immtsf.ops import (INCEPTION_MAX, conv2d_periods, conv2d_same_cl, inception_merge, inception_periods, inception_periods_ok, layer_norm, linear,
-                        period_aggregate, period_rows)
+                        period_aggregate, period_rows, timesnet_spectrum, timesnet_spectrum_ok)
 from immtsf.dropin import fp32_entry as _fp32_entry
 from layers.Conv_Blocks import Inception_Block_V1
 from layers.Embed import DataEmbedding
@@ -45,6 +46,7 @@ class TimesBlock(nn.Module):
         self.conv = nn.Sequential(Inception_Block_V1(configs.d_model, configs.d_ff, num_kernels=configs.num_kernels),
                                   nn.GELU(),
                                   Inception_Block_V1(configs.d_ff, configs.d_model, num_kernels=configs.num_kernels))
+        self.spectrum_calls = 0      # forwards whose period selection ran as immtsf.ops.timesnet_spectrum (no FFT library)
 
     def forward(self, x):
         B, T, N = x.size()
@@ -62,9 +64,15 @@ class TimesBlock(nn.Module):
             # a host sync per TimesBlock and a step no hipGraph can hold.  Here the series is laid out position-major, (Lmax B, N) with
             # row l B + b, so an image of ANY length is a prefix of one static buffer, and the period reaches the kernels as a device
             # number (csrc/conv.hip conv2d_period_*): every host-side shape is static.
-            top, weight = fft_for_period_device(x, self.k)
-            period, rows = period_rows(top, total, B)
-            xl = F.pad(x.transpose(0, 1), (0, 0, 0, 0, 0, Lmax - total)).reshape(Lmax * B, N)
+            if config.timesnet_spectrum_fused and x.dtype == torch.float32 and timesnet_spectrum_ok(T, N, self.k):
+                # the selection, the periods, the softmaxed weights and the position-major copy in two launches (a direct DFT: ops.timesnet_spectrum)
+                top, period, rows, w, xl = timesnet_spectrum(x, self.k)
+                self.spectrum_calls += 1
+            else:
+                top, weight = fft_for_period_device(x, self.k)
+                period, rows = period_rows(top, total, B)
+                xl = F.pad(x.transpose(0, 1), (0, 0, 0, 0, 0, Lmax - total)).reshape(Lmax * B, N)
+                w = F.softmax(weight, dim=1)
             # the k period images in ONE call per convolution (the same merged kernel for each), then the aggregation + residual as one launch
             if implicit:
                 # bf16 mode: no im2col image -- a workgroup holds a (window, period) image in LDS (ops.InceptionPeriodsFn)
@@ -73,7 +81,7 @@ class TimesBlock(nn.Module):
             else:
                 img = conv2d_periods(xl, period, rows, W1, b1, K1, B, Lmax, act="gelu")
                 out = conv2d_periods(img, period, rows, W2, b2, K2, B, Lmax)
-            return period_aggregate(out, F.softmax(weight, dim=1), x, B, total, Lmax)
+            return period_aggregate(out, w, x, B, total, Lmax)
         periods, weight = FFT_for_Period(x, self.k)
         res = []
         for period in periods:

@@ -1520,6 +1520,27 @@ int immtsf_period_aggregate_forward(const float* Y, const float* w, const float*
                                     float* out, immtsf_stream_t stream);
 int immtsf_period_aggregate_backward(const float* Y, const float* w, const float* dout, int32_t B, int32_t total, int32_t Lmax, int32_t N, int32_t k,
                                      float* dY, float* dw, immtsf_stream_t stream);
+/* TimesBlock's period selection (reference models/TimesNet.py:9-18 FFT_for_Period + the softmax of :83 + the padded copy that becomes the
+ * position-major image) as launches of the library's own: a direct DFT per window, no FFT library (csrc/timesnet_spectrum.hip).  All fp32
+ * in every precision mode; no atomics; two runs give the same bits.  x (B, T, N), F = T / 2 + 1, Lmax = 2 T.
+ *   timesnet_spectrum_ok:     1 when the kernels take the shape: 2 <= T <= 512, 1 <= N <= 256, T N <= 16384 (the window's tile, the
+ *                             amplitudes and the T-entry cos / sin table in at most 101 KB of LDS), 1 <= k <= min(16, F - 1).
+ *   timesnet_spectrum_fwd:    amp_mean[b, f] = mean_n |sum_t x[b, t, n] exp(-2 pi i f t / T)| (B, F), and xl (Lmax B, N): row t B + b =
+ *                             x[b, t, :], rows t >= T zero.
+ *   timesnet_spectrum_select: freq[f] = mean_b amp_mean[b, f], freq[0] = 0 (F floats, may be NULL); top (k int64): the k largest of freq,
+ *                             descending, equal values to the lower index, NaN ranked above everything; period / rows (k int32 each):
+ *                             immtsf_period_rows' values for top, period = T where top == 0; weight[b, j] = amp_mean[b, top_j] and
+ *                             w = softmax(weight) over j (B, k each).
+ *   timesnet_spectrum_bwd:    dx (B, T, N) = g_xl transposed back + the gradient through w: gs = w (g_w - sum_j g_w w), dx[b, t, n] +=
+ *                             (1 / N) sum_j gs[b, j] (Re_j cos th_jt - Im_j sin th_jt) / amp_j with Re, Im recomputed at the k selected
+ *                             frequencies; a term with amp_j == 0 is 0.  g_w (B, k) and g_xl (Lmax B, N) may each be NULL (zero).
+ * A shape outside timesnet_spectrum_ok: IMMTSF_EUNSUPPORTED, nothing launched.  (ABI 7, functions only) */
+int immtsf_timesnet_spectrum_ok(int32_t T, int32_t N, int32_t k);
+int immtsf_timesnet_spectrum_fwd(const float* x, int32_t B, int32_t T, int32_t N, float* amp_mean, float* xl, immtsf_stream_t stream);
+int immtsf_timesnet_spectrum_select(const float* amp_mean, int32_t B, int32_t T, int32_t k, float* freq, int64_t* top, int32_t* period,
+                                    int32_t* rows, float* weight, float* w, immtsf_stream_t stream);
+int immtsf_timesnet_spectrum_bwd(const float* x, const int64_t* top, const float* w, const float* g_w, const float* g_xl, int32_t B, int32_t T,
+                                 int32_t N, int32_t k, float* dx, immtsf_stream_t stream);
 
 /* ---- measurement aid (bench.py roofline leg): when enabled, every GEMM launch is bracketed by hipEvents on the
  * stream it is launched on.  collect() synchronises those events and fills HOST arrays meta[10*max] = (layout,
