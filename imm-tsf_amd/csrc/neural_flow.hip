@@ -5,7 +5,8 @@
 //
 // A coupling flow of width D at time t (one t per row), for layer i = 0 .. NF-1 with the mask m = ordered_{i % 2} (m_j = 1 for
 // j < D / 2 where i is even, for j >= D / 2 where i is odd; all zero where D == 1):
-//   (s, b) = MLP([x m, t])  (HL hidden Linears with Tanh, a last Linear to 2D),  phi = scale t  (TimeLinear, scale 2D wide),
+//   (s, b) = MLP([x m, t])  (HL hidden Linears with Tanh, a last Linear to 2D),  phi = scale t  (TimeLinear, scale 2D wide) or
+//   tanhf(scale t)  (TimeTanh; the time net is the template argument TN of the four kernels that form phi, one instance each),
 //   x_j <- x_j exp(s_j phi_j) + b_j phi_{D+j}  where m_j = 0,  x_j  where m_j = 1.   exp() takes its argument as written: no clamp.
 // Encoder, a tile of NF_WT = 8 windows per workgroup, h = c = 0, for i = L-1 .. 0:
 //   h <- flow_enc(h, t_i - prev_t)   with prev_t = t_{L-1} + 0.01 at first, then the point before (every window reads its own times);
@@ -24,7 +25,9 @@
 // (the flow rebuilt from z0 with every layer's activations kept in LDS, pulled back; the cotangent of z0 per row goes to the
 // workspace); launch 2, the encoder: transform_z0, then the observed points i = 0 .. L-1, each rebuilt from its saved (h, c) and xg;
 // launch 3 adds the per-workgroup parameter-gradient slabs in index order.  Every slab entry has one owner thread: no atomics, the
-// same inputs give the same bits.  Data, mask, times and eps take no gradient.
+// same inputs give the same bits.  Data, mask, times and eps take no gradient.  phi is not saved: the backward forms it again with
+// nf_phi<TN> from the scale and the t it has in LDS, the forward's expression, so d scale += d phi (1 - phi^2) t (TimeTanh) uses the
+// forward's phi bit for bit and the LDS plan is the same for both time nets.  The fold kernel never sees phi and is shared.
 #include "../../include/immtsf.h"
 #include "common.hpp"
 
@@ -36,6 +39,7 @@ constexpr int NF_THREADS = 256;
 constexpr int NF_MAX_FL = 4, NF_MAX_HL = 4, NF_MAX_RZ = 64, NF_MAX_HD = 128, NF_MAX_C = 64, NF_MAX_T = 1 << 20;
 constexpr int NF_DEC_WG = 256;             // most workgroups of the decode kernels (a workgroup walks tiles grid-stride)
 constexpr size_t NF_LDS_MAX = 160 * 1024;
+constexpr int NF_LINEAR = IMMTSF_NF_TIME_LINEAR, NF_TANH = IMMTSF_NF_TIME_TANH;      // the time net of a kernel instance (TN)
 
 // a Linear: weight (N, K) at goff of its section of the flat parameters, bias (hb) behind it; in LDS at loff, rows ld apart
 struct NfLin { int N, K, ld, goff, loff, hb; };
@@ -206,6 +210,14 @@ __device__ inline bool nf_masked(int D, int layer, int j) {
     return (layer & 1) ? !low : low;
 }
 
+// phi = time_net(t) of one coordinate: scale t (TimeLinear), tanhf(scale t) (TimeTanh).  The one definition the forward and the backward of
+// an instance share: the backward rebuilds phi from the same scale and t in LDS, so it sees the forward's bits.
+template <int TN>
+__device__ inline float nf_phi(float sc, float t) {
+    const float a = sc * t;
+    return TN == NF_TANH ? tanhf(a) : a;
+}
+
 struct NfSlot { float *xin, *zin, *hid, *sb; };
 __device__ inline NfSlot nf_slot(const NfPlan& p, const NfBuf& s, int i) {
     NfSlot t;
@@ -218,6 +230,7 @@ __device__ inline NfSlot nf_slot(const NfPlan& p, const NfBuf& s, int i) {
 
 // x (pitch ldd) <- flow(x, tt), in place.  keep: layer i leaves its input, net input, hidden activations and (s, b) in slot i.
 // Expects a barrier behind the writes of x and tt; ends with a barrier.
+template <int TN>
 __device__ void nf_flow_fwd(const NfPlan& p, const NfFlow& f, const NfBuf& s, float* x, bool keep) {
     const int T = NF_WT, D = f.D;
     for (int i = 0; i < p.NF; ++i) {
@@ -246,13 +259,14 @@ __device__ void nf_flow_fwd(const NfPlan& p, const NfFlow& f, const NfBuf& s, fl
             const int w = idx / D, j = idx - w * D;
             if (nf_masked(D, i, j)) continue;
             const float t = s.tt[w], sv = q.sb[w * p.ld2 + j], bv = q.sb[w * p.ld2 + D + j];
-            x[w * p.ldd + j] = x[w * p.ldd + j] * expf(sv * (sc[j] * t)) + bv * (sc[D + j] * t);
+            x[w * p.ldd + j] = x[w * p.ldd + j] * expf(sv * nf_phi<TN>(sc[j], t)) + bv * nf_phi<TN>(sc[D + j], t);
         }
         __syncthreads();
     }
 }
 
 // the flow that nf_flow_fwd(keep) just rebuilt, backwards: s.g holds the cotangent of its result on entry and of its input on exit
+template <int TN>
 __device__ void nf_flow_bwd(const NfPlan& p, const NfFlow& f, const NfBuf& s, float* slab) {
     const int T = NF_WT, D = f.D;
     for (int i = p.NF - 1; i >= 0; --i) {
@@ -264,13 +278,18 @@ __device__ void nf_flow_bwd(const NfPlan& p, const NfFlow& f, const NfBuf& s, fl
                 s.gsb[o + j] = 0.f; s.gsb[o + D + j] = 0.f; s.gsc[o + j] = 0.f; s.gsc[o + D + j] = 0.f;
                 continue;
             }
-            const float t = s.tt[w], sv = q.sb[o + j], bv = q.sb[o + D + j], ps = sc[j] * t, pb = sc[D + j] * t;
+            const float t = s.tt[w], sv = q.sb[o + j], bv = q.sb[o + D + j], ps = nf_phi<TN>(sc[j], t), pb = nf_phi<TN>(sc[D + j], t);
             const float e = expf(sv * ps), xv = q.xin[w * p.ldd + j], gy = s.g[w * p.ldd + j];
             s.g[w * p.ldd + j] = gy * e;
             s.gsb[o + j] = gy * xv * e * ps;
             s.gsb[o + D + j] = gy * pb;
-            s.gsc[o + j] = gy * xv * e * sv * t;
-            s.gsc[o + D + j] = gy * bv * t;
+            if (TN == NF_TANH) {                                            // d phi / d scale = (1 - phi^2) t
+                s.gsc[o + j] = gy * xv * e * sv * ((1.f - ps * ps) * t);
+                s.gsc[o + D + j] = gy * bv * ((1.f - pb * pb) * t);
+            } else {
+                s.gsc[o + j] = gy * xv * e * sv * t;
+                s.gsc[o + D + j] = gy * bv * t;
+            }
         }
         __syncthreads();
         for (int j = threadIdx.x; j < 2 * D; j += NF_THREADS) {
@@ -331,6 +350,7 @@ __device__ void nf_gates(const NfPlan& p, const NfBuf& s, const float* xg, int b
     __syncthreads();
 }
 
+template <int TN>
 __global__ __launch_bounds__(NF_THREADS) void nf_enc_fwd_kernel(NfPlan p, const float* __restrict__ data, const float* __restrict__ mask,
                                                                const float* __restrict__ tp, const float* __restrict__ prm,
                                                                const float* __restrict__ eps, float* xg, float* __restrict__ states,
@@ -366,7 +386,7 @@ __global__ __launch_bounds__(NF_THREADS) void nf_enc_fwd_kernel(NfPlan p, const 
         const int i = L - 1 - q;
         nf_point(p, s, mask, tp, b0, i);
         __syncthreads();
-        nf_flow_fwd(p, p.enc, s, s.x, false);
+        nf_flow_fwd<TN>(p, p.enc, s, s.x, false);
         nf_gates(p, s, xg, b0, i);
         for (int idx = threadIdx.x; idx < T * R; idx += NF_THREADS) {
             const int w = idx / R, j = idx - w * R;
@@ -408,6 +428,7 @@ __device__ void nf_dec_rows(const NfPlan& p, const NfBuf& s, const float* __rest
     __syncthreads();
 }
 
+template <int TN>
 __global__ __launch_bounds__(NF_THREADS) void nf_dec_fwd_kernel(NfPlan p, const float* __restrict__ zs, const float* __restrict__ tpp,
                                                                const float* __restrict__ prm, float* __restrict__ out) {
     extern __shared__ __align__(16) float nf_lds[];
@@ -419,7 +440,7 @@ __global__ __launch_bounds__(NF_THREADS) void nf_dec_fwd_kernel(NfPlan p, const 
     __syncthreads();
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         nf_dec_rows(p, s, zs, tpp, tile);
-        nf_flow_fwd(p, p.dec, s, s.x, false);
+        nf_flow_fwd<TN>(p, p.dec, s, s.x, false);
         nf_lin<0>(s.W, p.dcd, s.x, p.ldd, s.co, p.ldo);
         for (int idx = threadIdx.x; idx < T * C; idx += NF_THREADS) {
             const int w = idx / C, c = idx - w * C, r = tile * T + w;
@@ -429,6 +450,7 @@ __global__ __launch_bounds__(NF_THREADS) void nf_dec_fwd_kernel(NfPlan p, const 
     }
 }
 
+template <int TN>
 __global__ __launch_bounds__(NF_THREADS) void nf_dec_bwd_kernel(NfPlan p, const float* __restrict__ zs, const float* __restrict__ tpp,
                                                                const float* __restrict__ prm, const float* __restrict__ dout,
                                                                float* __restrict__ slabs, float* __restrict__ gzr) {
@@ -447,10 +469,10 @@ __global__ __launch_bounds__(NF_THREADS) void nf_dec_bwd_kernel(NfPlan p, const 
             s.co[w * p.ldo + c] = r < rows ? dout[(size_t)r * C + c] : 0.f;
         }
         nf_dec_rows(p, s, zs, tpp, tile);
-        nf_flow_fwd(p, p.dec, s, s.x, true);
+        nf_flow_fwd<TN>(p, p.dec, s, s.x, true);
         nf_wgrad(slab, p.dcd, s.co, p.ldo, s.x, p.ldd);
         nf_lin_t(s.W, p.dcd, s.co, p.ldo, s.g, p.ldd, Z, nullptr, 0);
-        nf_flow_bwd(p, p.dec, s, slab);
+        nf_flow_bwd<TN>(p, p.dec, s, slab);
         for (int idx = threadIdx.x; idx < T * Z; idx += NF_THREADS) {
             const int w = idx / Z, j = idx - w * Z, r = tile * T + w;
             if (r < rows) gzr[(size_t)r * Z + j] = s.g[w * p.ldd + j];
@@ -459,6 +481,7 @@ __global__ __launch_bounds__(NF_THREADS) void nf_dec_bwd_kernel(NfPlan p, const 
     }
 }
 
+template <int TN>
 __global__ __launch_bounds__(NF_THREADS) void nf_enc_bwd_kernel(NfPlan p, const float* __restrict__ data, const float* __restrict__ mask,
                                                                const float* __restrict__ tp, const float* __restrict__ prm,
                                                                const float* __restrict__ eps, const float* __restrict__ xg,
@@ -517,7 +540,7 @@ __global__ __launch_bounds__(NF_THREADS) void nf_enc_bwd_kernel(NfPlan p, const 
         }
         nf_point(p, s, mask, tp, b0, i);
         __syncthreads();
-        nf_flow_fwd(p, p.enc, s, s.x, true);
+        nf_flow_fwd<TN>(p, p.enc, s, s.x, true);
         nf_gates(p, s, xg, b0, i);
         for (int idx = threadIdx.x; idx < T * R; idx += NF_THREADS) {
             const int w = idx / R, j = idx - w * R, o = w * p.ldd + j;
@@ -560,7 +583,7 @@ __global__ __launch_bounds__(NF_THREADS) void nf_enc_bwd_kernel(NfPlan p, const 
             s.g[w * p.ldd + k] += a;
         }
         __syncthreads();
-        nf_flow_bwd(p, p.enc, s, slab);
+        nf_flow_bwd<TN>(p, p.enc, s, slab);
     }
 }
 
@@ -590,6 +613,7 @@ int nf_dec_wgs(const NfPlan& p) {
     const int tiles = cdiv(p.B * p.Lp, NF_WT);
     return tiles < NF_DEC_WG ? tiles : NF_DEC_WG;
 }
+bool nf_kind_ok(int32_t tn) { return tn == NF_LINEAR || tn == NF_TANH; }
 bool nf_call_ok(const immtsf_neural_flow_dims* d) {
     if (!immtsf_neural_flow_supported(d) || d->B < 1) return false;
     const int64_t widest = nf_max(nf_max(4 * d->rec_dims, d->latents), d->C);
@@ -599,6 +623,40 @@ size_t nf_up64(size_t n) { return (n + 63) & ~size_t(63); }
 template <typename K>
 void nf_allow_lds(K kernel, size_t lds) {
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
+// the two forward launches / the three backward launches of one instance (TN fixed at compile time: no branch on it in a kernel)
+template <int TN>
+int nf_forward(const NfPlan& p, const float* data, const float* mask, const float* tp, const float* tp_pred, const float* params,
+               const float* eps, float* out, float* xg, float* states, float* zs, hipStream_t s) {
+    const size_t le = nf_lds_bytes(p, true, false), ld = nf_lds_bytes(p, false, false);
+    nf_allow_lds(nf_enc_fwd_kernel<TN>, le);
+    hipLaunchKernelGGL(nf_enc_fwd_kernel<TN>, dim3(nf_enc_wgs(p)), dim3(NF_THREADS), le, s, p, data, mask, tp, params, eps, xg, states, zs);
+    IMMTSF_LAUNCH_CHECK();
+    nf_allow_lds(nf_dec_fwd_kernel<TN>, ld);
+    hipLaunchKernelGGL(nf_dec_fwd_kernel<TN>, dim3(nf_dec_wgs(p)), dim3(NF_THREADS), ld, s, p, zs, tp_pred, params + p.NVe, out);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
+template <int TN>
+int nf_backward(const NfPlan& p, const float* data, const float* mask, const float* tp, const float* tp_pred, const float* params,
+                const float* eps, const float* xg, const float* states, const float* zs, const float* d_out, float* grads, void* workspace,
+                hipStream_t s) {
+    const int nwe = nf_enc_wgs(p), nwd = nf_dec_wgs(p);
+    float* se = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
+    float* sd = se + nf_up64((size_t)nwe * p.NVe);
+    float* gzr = sd + nf_up64((size_t)nwd * p.NVd);
+    const size_t le = nf_lds_bytes(p, true, true), ld = nf_lds_bytes(p, false, true);
+    nf_allow_lds(nf_dec_bwd_kernel<TN>, ld);
+    hipLaunchKernelGGL(nf_dec_bwd_kernel<TN>, dim3(nwd), dim3(NF_THREADS), ld, s, p, zs, tp_pred, params + p.NVe, d_out, sd, gzr);
+    IMMTSF_LAUNCH_CHECK();
+    nf_allow_lds(nf_enc_bwd_kernel<TN>, le);
+    hipLaunchKernelGGL(nf_enc_bwd_kernel<TN>, dim3(nwe), dim3(NF_THREADS), le, s, p, data, mask, tp, params, eps, xg, states, gzr, se);
+    IMMTSF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nf_fold_kernel, dim3(cdiv(p.NVe + p.NVd, NF_THREADS)), dim3(NF_THREADS), 0, s, p.NVe, p.NVd, nwe, nwd, se, sd, grads);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
 }
 
 }  // namespace
@@ -623,51 +681,63 @@ size_t immtsf_neural_flow_workspace_bytes(const immtsf_neural_flow_dims* dims) {
     return sizeof(float) * (nf_up64((size_t)nf_enc_wgs(p) * p.NVe) + nf_up64((size_t)nf_dec_wgs(p) * p.NVd) + (size_t)p.B * p.Lp * p.Z) + 256;
 }
 
-int immtsf_neural_flow_forward(const immtsf_neural_flow_dims* dims, const float* data, const float* mask, const float* tp,
-                               const float* tp_pred, const float* params, const float* eps, float* out, float* xg, float* states,
-                               float* zs, immtsf_stream_t stream) {
+// the TimeTanh instance keeps no phi tile (the backward rebuilds phi from scale and t, both already in LDS), so the LDS plan, the
+// parameter layout and the workspace are the TimeLinear instance's: the queries differ in the kind they accept only
+int immtsf_neural_flow_tn_supported(const immtsf_neural_flow_dims* dims, int32_t time_net) {
+    return nf_kind_ok(time_net) && immtsf_neural_flow_supported(dims);
+}
+
+int32_t immtsf_neural_flow_tn_param_count(const immtsf_neural_flow_dims* dims, int32_t time_net) {
+    return nf_kind_ok(time_net) ? immtsf_neural_flow_param_count(dims) : -1;
+}
+
+size_t immtsf_neural_flow_tn_workspace_bytes(const immtsf_neural_flow_dims* dims, int32_t time_net) {
+    return nf_kind_ok(time_net) ? immtsf_neural_flow_workspace_bytes(dims) : 0;
+}
+
+int immtsf_neural_flow_tn_forward(const immtsf_neural_flow_dims* dims, int32_t time_net, const float* data, const float* mask,
+                                  const float* tp, const float* tp_pred, const float* params, const float* eps, float* out, float* xg,
+                                  float* states, float* zs, immtsf_stream_t stream) {
     if (!dims || dims->B < 0) return IMMTSF_EINVAL;
-    if (!immtsf_neural_flow_supported(dims)) return IMMTSF_EUNSUPPORTED;
+    if (!immtsf_neural_flow_tn_supported(dims, time_net)) return IMMTSF_EUNSUPPORTED;
     if (dims->B == 0) return IMMTSF_OK;
     if (!nf_call_ok(dims)) return IMMTSF_EINVAL;
     if (!data || !mask || !tp || !tp_pred || !params || !eps || !out || !xg || !states || !zs) return IMMTSF_EINVAL;
     const NfPlan p = nf_plan_of(dims);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t le = nf_lds_bytes(p, true, false), ld = nf_lds_bytes(p, false, false);
-    nf_allow_lds(nf_enc_fwd_kernel, le);
-    hipLaunchKernelGGL(nf_enc_fwd_kernel, dim3(nf_enc_wgs(p)), dim3(NF_THREADS), le, s, p, data, mask, tp, params, eps, xg, states, zs);
-    IMMTSF_LAUNCH_CHECK();
-    nf_allow_lds(nf_dec_fwd_kernel, ld);
-    hipLaunchKernelGGL(nf_dec_fwd_kernel, dim3(nf_dec_wgs(p)), dim3(NF_THREADS), ld, s, p, zs, tp_pred, params + p.NVe, out);
-    IMMTSF_LAUNCH_CHECK();
-    return IMMTSF_OK;
+    return time_net == NF_TANH ? nf_forward<NF_TANH>(p, data, mask, tp, tp_pred, params, eps, out, xg, states, zs, s)
+                               : nf_forward<NF_LINEAR>(p, data, mask, tp, tp_pred, params, eps, out, xg, states, zs, s);
+}
+
+int immtsf_neural_flow_tn_backward(const immtsf_neural_flow_dims* dims, int32_t time_net, const float* data, const float* mask,
+                                   const float* tp, const float* tp_pred, const float* params, const float* eps, const float* xg,
+                                   const float* states, const float* zs, const float* d_out, float* grads, void* workspace,
+                                   size_t workspace_bytes, immtsf_stream_t stream) {
+    if (!dims || dims->B < 1) return IMMTSF_EINVAL;
+    if (!immtsf_neural_flow_tn_supported(dims, time_net)) return IMMTSF_EUNSUPPORTED;
+    if (!nf_call_ok(dims)) return IMMTSF_EINVAL;
+    if (!data || !mask || !tp || !tp_pred || !params || !eps || !xg || !states || !zs || !d_out || !grads || !workspace) return IMMTSF_EINVAL;
+    if (workspace_bytes < immtsf_neural_flow_workspace_bytes(dims)) return IMMTSF_EWORKSPACE;
+    const NfPlan p = nf_plan_of(dims);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return time_net == NF_TANH
+               ? nf_backward<NF_TANH>(p, data, mask, tp, tp_pred, params, eps, xg, states, zs, d_out, grads, workspace, s)
+               : nf_backward<NF_LINEAR>(p, data, mask, tp, tp_pred, params, eps, xg, states, zs, d_out, grads, workspace, s);
+}
+
+// the entry points from before the time-net kind: TimeLinear
+int immtsf_neural_flow_forward(const immtsf_neural_flow_dims* dims, const float* data, const float* mask, const float* tp,
+                               const float* tp_pred, const float* params, const float* eps, float* out, float* xg, float* states,
+                               float* zs, immtsf_stream_t stream) {
+    return immtsf_neural_flow_tn_forward(dims, IMMTSF_NF_TIME_LINEAR, data, mask, tp, tp_pred, params, eps, out, xg, states, zs, stream);
 }
 
 int immtsf_neural_flow_backward(const immtsf_neural_flow_dims* dims, const float* data, const float* mask, const float* tp,
                                 const float* tp_pred, const float* params, const float* eps, const float* xg, const float* states,
                                 const float* zs, const float* d_out, float* grads, void* workspace, size_t workspace_bytes,
                                 immtsf_stream_t stream) {
-    if (!dims || dims->B < 1) return IMMTSF_EINVAL;
-    if (!immtsf_neural_flow_supported(dims)) return IMMTSF_EUNSUPPORTED;
-    if (!nf_call_ok(dims)) return IMMTSF_EINVAL;
-    if (!data || !mask || !tp || !tp_pred || !params || !eps || !xg || !states || !zs || !d_out || !grads || !workspace) return IMMTSF_EINVAL;
-    if (workspace_bytes < immtsf_neural_flow_workspace_bytes(dims)) return IMMTSF_EWORKSPACE;
-    const NfPlan p = nf_plan_of(dims);
-    const int nwe = nf_enc_wgs(p), nwd = nf_dec_wgs(p);
-    float* se = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~uintptr_t(255));
-    float* sd = se + nf_up64((size_t)nwe * p.NVe);
-    float* gzr = sd + nf_up64((size_t)nwd * p.NVd);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t le = nf_lds_bytes(p, true, true), ld = nf_lds_bytes(p, false, true);
-    nf_allow_lds(nf_dec_bwd_kernel, ld);
-    hipLaunchKernelGGL(nf_dec_bwd_kernel, dim3(nwd), dim3(NF_THREADS), ld, s, p, zs, tp_pred, params + p.NVe, d_out, sd, gzr);
-    IMMTSF_LAUNCH_CHECK();
-    nf_allow_lds(nf_enc_bwd_kernel, le);
-    hipLaunchKernelGGL(nf_enc_bwd_kernel, dim3(nwe), dim3(NF_THREADS), le, s, p, data, mask, tp, params, eps, xg, states, gzr, se);
-    IMMTSF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(nf_fold_kernel, dim3(cdiv(p.NVe + p.NVd, NF_THREADS)), dim3(NF_THREADS), 0, s, p.NVe, p.NVd, nwe, nwd, se, sd, grads);
-    IMMTSF_LAUNCH_CHECK();
-    return IMMTSF_OK;
+    return immtsf_neural_flow_tn_backward(dims, IMMTSF_NF_TIME_LINEAR, data, mask, tp, tp_pred, params, eps, xg, states, zs, d_out, grads,
+                                          workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

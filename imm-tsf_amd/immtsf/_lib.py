@@ -215,6 +215,11 @@ _PROTOS = {
     "immtsf_neural_flow_workspace_bytes": (C.c_size_t, [_P(NeuralFlowDims)]),
     "immtsf_neural_flow_forward": (C.c_int, [_P(NeuralFlowDims)] + [c_f32p] * 10 + [c_stream]),
     "immtsf_neural_flow_backward": (C.c_int, [_P(NeuralFlowDims)] + [c_f32p] * 11 + [C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_neural_flow_tn_supported": (C.c_int, [_P(NeuralFlowDims), C.c_int32]),
+    "immtsf_neural_flow_tn_param_count": (C.c_int32, [_P(NeuralFlowDims), C.c_int32]),
+    "immtsf_neural_flow_tn_workspace_bytes": (C.c_size_t, [_P(NeuralFlowDims), C.c_int32]),
+    "immtsf_neural_flow_tn_forward": (C.c_int, [_P(NeuralFlowDims), C.c_int32] + [c_f32p] * 10 + [c_stream]),
+    "immtsf_neural_flow_tn_backward": (C.c_int, [_P(NeuralFlowDims), C.c_int32] + [c_f32p] * 11 + [C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_note_embed_supported": (C.c_int, [C.c_int32] * 4),
     "immtsf_note_embed_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "immtsf_note_embed_tokens": (C.c_int, [c_i32p, c_i32p, C.c_int32, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32, c_f32p,

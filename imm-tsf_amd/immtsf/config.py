@@ -196,6 +196,10 @@ latentode_fused = os.environ.get("IMMTSF_LATENTODE_FUSED", "1") != "0"
 # with the TimeLinear time net and immtsf_neural_flow_supported allows; IMMTSF_NEURALFLOW_FUSED=0: the composed path (the reference's
 # loop over the observed points on torch ops) -- the cross-check.  fp32 in either precision mode
 neuralflow_fused = os.environ.get("IMMTSF_NEURALFLOW_FUSED", "1") != "0"
+# ... and the same launches for nf_time_net='TimeTanh' (the TimeTanh instance of those kernels), under every condition above.  OFF unless
+# IMMTSF_NEURALFLOW_TANH_FUSED=1: tests/test_gpu_neuralflow.py pins that a TimeTanh model with nothing set takes the composed path, and
+# what ran before this instance existed keeps running as it did.  neuralflow_fused off turns both off
+neuralflow_tanh_fused = os.environ.get("IMMTSF_NEURALFLOW_TANH_FUSED", "0") == "1"
 # lib.parse_datasets.parse_datasets() returns immtsf.data.ResidentLoader objects over a ResidentStore (the dataset in HBM, every batch
 # built on the device, one id upload per epoch); IMMTSF_RESIDENT_LOADER=0: the reference module's own host loaders, when a
 # reference tree is on the path (NotImplementedError otherwise)

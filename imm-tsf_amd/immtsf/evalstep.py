@@ -120,7 +120,7 @@ class EvalStep:
         mods = [m for m in (self.model, self.fusion) if m is not None]
         sig = tuple(p.data_ptr() for m in mods for p in m.parameters())
         return (config.precision, config.t2v_form, config.fuse_tail, config.xattn_rank, config.attn_mid, config.note_index, config.gr_split,
-                config.dlinear_fused, config.timemixer_fused, config.ttm_fused, config.cru_fused, config.latentode_fused, config.neuralflow_fused, config.timesnet_spectrum_fused, sig, tuple((k, tuple(b[k].shape), b[k].dtype) for k in names))
+                config.dlinear_fused, config.timemixer_fused, config.ttm_fused, config.cru_fused, config.latentode_fused, config.neuralflow_fused, config.neuralflow_tanh_fused, config.timesnet_spectrum_fused, sig, tuple((k, tuple(b[k].shape), b[k].dtype) for k in names))
 
     def __call__(self, batch):
         model, fusion = self.model, self.fusion

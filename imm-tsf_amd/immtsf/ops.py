@@ -4444,22 +4444,34 @@ def _neural_flow_dims(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers,
                                int(flow_layers))
 
 
-def neural_flow_supported(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers, call=False):
-    """the limits of the fused NeuralFlow kernels (immtsf_neural_flow_supported: rec_dims, latents <= 64, hidden_dim <= 128, hidden_layers,
-    flow_layers <= 4, C <= 64, L, Lp <= 2^20, W_hh, the flow's nets and a tile's state within 160 KB of LDS), from the dims alone; call:
-    also what a compute call needs (B >= 1 and the saved state's index range, immtsf_neural_flow_workspace_bytes > 0)"""
+NEURAL_FLOW_TIME_NETS = {"TimeLinear": 0, "TimeTanh": 1}      # IMMTSF_NF_TIME_LINEAR / IMMTSF_NF_TIME_TANH
+neural_flow_launches = {name: 0 for name in NEURAL_FLOW_TIME_NETS}      # forward calls per kernel instance (tests assert which one ran)
+
+
+def _neural_flow_kind(time_net):
+    """the library's number of a time net; -1 (which the library refuses) for a name it has no instance of"""
+    return NEURAL_FLOW_TIME_NETS.get(time_net, -1)
+
+
+def neural_flow_supported(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers, call=False, time_net="TimeLinear"):
+    """the limits of the fused NeuralFlow kernels (immtsf_neural_flow_tn_supported: time_net TimeLinear or TimeTanh, rec_dims, latents <= 64,
+    hidden_dim <= 128, hidden_layers, flow_layers <= 4, C <= 64, L, Lp <= 2^20, W_hh, the flow's nets and a tile's state within 160 KB of
+    LDS), from the dims alone; call: also what a compute call needs (B >= 1 and the saved state's index range,
+    immtsf_neural_flow_tn_workspace_bytes > 0)"""
     lib = _lib.load()
-    return _dims_supported(lib.immtsf_neural_flow_supported, lib.immtsf_neural_flow_workspace_bytes,
+    kind = _neural_flow_kind(time_net)
+    return _dims_supported(lambda d: lib.immtsf_neural_flow_tn_supported(d, kind), lambda d: lib.immtsf_neural_flow_tn_workspace_bytes(d, kind),
                            _neural_flow_dims(B, L, Lp, C, rec_dims, latents, hidden_dim, hidden_layers, flow_layers), call)
 
 
 class NeuralFlowFn(torch.autograd.Function):
     """NeuralFlow's forecasting() (the encoder's reversed walk of coupling-flow step + LSTM cell, transform_z0, z0 = mu + eps sigma, the
-    coupling flow at every forecast time, the decoder) as TWO launches; backward = THREE (immtsf_neural_flow_forward / _backward,
-    csrc/neural_flow.hip).  The flat parameter buffer is the only input with a gradient.  fp32 in either precision mode."""
+    coupling flow at every forecast time, the decoder) as TWO launches; backward = THREE (immtsf_neural_flow_tn_forward / _tn_backward,
+    csrc/neural_flow.hip), on the kernel instance of `time_net` (kept on the node as .time_net).  The flat parameter buffer is the only
+    input with a gradient.  fp32 in either precision mode."""
 
     @staticmethod
-    def forward(ctx, data, mask, tp, tpp, flat, eps, widths):
+    def forward(ctx, data, mask, tp, tpp, flat, eps, widths, time_net="TimeLinear"):
         lib = _lib.load()
         data, mask, tp, tpp, flat, eps = (_c(t) for t in (data, mask, tp, tpp, flat, eps))
         _need_gpu(data, mask, tp, tpp, flat, eps)
@@ -4471,9 +4483,11 @@ class NeuralFlowFn(torch.autograd.Function):
         xg = torch.empty(B, L, 4 * R, dtype=torch.float32, device=data.device)
         states = torch.empty(B, L + 1, 2 * R, dtype=torch.float32, device=data.device)
         zs = torch.empty(B, 3, Z, dtype=torch.float32, device=data.device)
-        check(lib.immtsf_neural_flow_forward(C.byref(d), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(out), ptr(xg),
-                                             ptr(states), ptr(zs), stream_ptr()), "neural_flow_forward")
+        check(lib.immtsf_neural_flow_tn_forward(C.byref(d), _neural_flow_kind(time_net), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat),
+                                                ptr(eps), ptr(out), ptr(xg), ptr(states), ptr(zs), stream_ptr()), "neural_flow_forward")
+        neural_flow_launches[time_net] += 1
         ctx.dims = (B, L, Lp, Cc) + tuple(widths)
+        ctx.time_net = time_net
         ctx.save_for_backward(data, mask, tp, tpp, flat, eps, xg, states, zs)
         return out
 
@@ -4482,28 +4496,30 @@ class NeuralFlowFn(torch.autograd.Function):
         lib = _lib.load()
         data, mask, tp, tpp, flat, eps, xg, states, zs = ctx.saved_tensors
         d = _neural_flow_dims(*ctx.dims)
+        kind = _neural_flow_kind(ctx.time_net)
         grads = torch.empty_like(flat)      # every entry is written: no zero fill
-        ws = _bytes(lib.immtsf_neural_flow_workspace_bytes(C.byref(d)), data.device)
-        check(lib.immtsf_neural_flow_backward(C.byref(d), ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(xg),
-                                              ptr(states), ptr(zs), ptr(dout.contiguous()), ptr(grads), ptr(ws), ws.numel(), stream_ptr()),
-              "neural_flow_backward")
-        return None, None, None, None, grads, None, None
+        ws = _bytes(lib.immtsf_neural_flow_tn_workspace_bytes(C.byref(d), kind), data.device)
+        check(lib.immtsf_neural_flow_tn_backward(C.byref(d), kind, ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(flat), ptr(eps), ptr(xg),
+                                                 ptr(states), ptr(zs), ptr(dout.contiguous()), ptr(grads), ptr(ws), ws.numel(),
+                                                 stream_ptr()), "neural_flow_backward")
+        return None, None, None, None, grads, None, None, None
 
 
-def neural_flow(data, mask, tp, tp_pred, flat_params, eps, widths):
+def neural_flow(data, mask, tp, tp_pred, flat_params, eps, widths, time_net="TimeLinear"):
     """data, mask (B, L, C); tp (B, L), tp_pred (B, Lp): every window's own times; flat_params: every parameter in state_dict order,
-    flattened; eps (B, latents); widths = (rec_dims, latents, hidden_dim, hidden_layers, flow_layers) -> the forecast (B, Lp, C).
-    Gradients reach flat_params only."""
+    flattened; eps (B, latents); widths = (rec_dims, latents, hidden_dim, hidden_layers, flow_layers); time_net 'TimeLinear' or
+    'TimeTanh' -> the forecast (B, Lp, C).  Gradients reach flat_params only."""
     B, L, Cc = data.shape
     widths = tuple(int(w) for w in widths)
     if tp_pred.dim() != 2:
         raise _lib.ImmtsfError("neural_flow: tp_pred is (B, Lp)")
     Lp = tp_pred.shape[1]
-    if not neural_flow_supported(B, L, Lp, Cc, *widths, call=True):
-        raise _lib.ImmtsfError(f"neural_flow: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, C {Cc}, widths {widths})")
+    if not neural_flow_supported(B, L, Lp, Cc, *widths, call=True, time_net=time_net):
+        raise _lib.ImmtsfError(f"neural_flow: shapes outside the fused kernel (B {B}, L {L}, Lp {Lp}, C {Cc}, widths {widths}, "
+                               f"time_net {time_net!r})")
     d = _neural_flow_dims(B, L, Lp, Cc, *widths)
-    nv = int(_lib.load().immtsf_neural_flow_param_count(C.byref(d)))
+    nv = int(_lib.load().immtsf_neural_flow_tn_param_count(C.byref(d), _neural_flow_kind(time_net)))
     if tuple(mask.shape) != (B, L, Cc) or tuple(tp.shape) != (B, L) or tuple(tp_pred.shape) != (B, Lp) or tuple(eps.shape) != (B, widths[1]) or \
             flat_params.numel() != nv or any(q.dtype != torch.float32 for q in (data, mask, tp, tp_pred, flat_params, eps)):
         raise _lib.ImmtsfError("neural_flow: the tensors are not the fp32 tensors of these dimensions")
-    return NeuralFlowFn.apply(data, mask, tp, tp_pred, flat_params, eps, widths)
+    return NeuralFlowFn.apply(data, mask, tp, tp_pred, flat_params, eps, widths, time_net)

@@ -250,7 +250,7 @@ def _seam_key(model, fusion, batch_dict, names):
     sig = tuple((p.data_ptr(), p.requires_grad) for m in (model, fusion) for p in m.parameters())
     return (id(fusion), model.training, fusion.training, config.precision, config.t2v_form, config.fuse_tail, config.xattn_rank,
             config.xattn_fused_loss, config.attn_mid, config.note_index, config.dlinear_fused, config.timemixer_fused, config.ttm_fused,
-            config.cru_fused, config.latentode_fused, config.neuralflow_fused, config.timesnet_spectrum_fused, sig,
+            config.cru_fused, config.latentode_fused, config.neuralflow_fused, config.neuralflow_tanh_fused, config.timesnet_spectrum_fused, sig,
             tuple((k, tuple(batch_dict[k].shape), batch_dict[k].dtype) for k in names))
 
 

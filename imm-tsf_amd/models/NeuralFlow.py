@@ -30,7 +30,9 @@ which are not restated.  The options of the reference's ODE branch (nf_solver, n
 With the TimeLinear time net, fp32 tensors on the GPU, no gradient wanted for the data and immtsf_neural_flow_supported taking the
 widths, forecasting() is TWO HIP launches forward and THREE backward (immtsf.ops.neural_flow, csrc/neural_flow.hip) whenever
 config.neuralflow_fused is on; eps is one torch.randn launch, every window's times are read from device memory, nothing syncs with the
-host.  `fused_calls` counts those calls.  Anything else -- and IMMTSF_NEURALFLOW_FUSED=0 -- runs the composed path: the reference's
+host.  The TimeTanh time net takes the same launches (the kernels' TimeTanh instance) under the same conditions once
+config.neuralflow_tanh_fused is on as well (IMMTSF_NEURALFLOW_TANH_FUSED=1; off by default, see immtsf/config.py).  `fused_calls`
+counts the calls of either kind.  Anything else -- and IMMTSF_NEURALFLOW_FUSED=0 -- runs the composed path: the reference's
 loop on torch ops, which covers every option the reference's forecasting() reaches with the coupling flow (any nf_flow_layers,
 nf_hidden_layers, nf_hidden_dim, nf_rec_dims, nf_latents, TimeTanh) and does not sync either.
 
@@ -258,9 +260,13 @@ class NeuralFlow(nn.Module):
         a = self.nf_args
         return (a.rec_dims, a.latents, a.hidden_dim, a.hidden_layers, a.flow_layers)
 
+    def _time_net_fused(self):
+        """the knobs: TimeLinear under config.neuralflow_fused, TimeTanh under config.neuralflow_tanh_fused as well"""
+        tn = self.nf_args.time_net
+        return bool(config.neuralflow_fused and (tn == "TimeLinear" or (tn == "TimeTanh" and config.neuralflow_tanh_fused)))
+
     def _static_fused_ok(self):
-        return bool(config.neuralflow_fused and self.nf_args.time_net == "TimeLinear" and
-                    neural_flow_supported(1, 1, 1, self.enc_in, *self._widths()))
+        return self._time_net_fused() and neural_flow_supported(1, 1, 1, self.enc_in, *self._widths(), time_net=self.nf_args.time_net)
 
     @property
     def immtsf_graphable(self):
@@ -271,7 +277,7 @@ class NeuralFlow(nn.Module):
         B, L, C = data.shape
         if not (self._static_fused_ok() and B > 0 and C == self.enc_in and tpp.dim() == 2 and tp.dim() == 2 and
                 all(t.is_cuda and t.dtype == torch.float32 and not t.requires_grad for t in (tpp, data, tp, mask)) and
-                neural_flow_supported(B, L, tpp.shape[1], C, *self._widths(), call=True)):
+                neural_flow_supported(B, L, tpp.shape[1], C, *self._widths(), call=True, time_net=self.nf_args.time_net)):
             return False
         # the module itself: a .half() / .bfloat16() model, one left on another device -> composed
         return all(q.device == data.device and q.dtype == torch.float32 for q in self.nf_model_core.parameters())
@@ -294,7 +300,7 @@ class NeuralFlow(nn.Module):
         if self._fused_ok(tp_to_predict, observed_data, observed_tp, observed_mask):
             self.fused_calls += 1
             flat = torch.cat([p.reshape(-1) for p in core.parameters()])
-            return neural_flow(observed_data, observed_mask, observed_tp, tp_to_predict, flat, eps, self._widths())
+            return neural_flow(observed_data, observed_mask, observed_tp, tp_to_predict, flat, eps, self._widths(), self.nf_args.time_net)
         mu, sigma = core.encoder_z0(torch.cat((observed_data, observed_mask), -1), observed_tp)
         z0 = eps * sigma + mu
         Lp = tp_to_predict.shape[1]

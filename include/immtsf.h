@@ -773,6 +773,24 @@ int immtsf_neural_flow_backward(const immtsf_neural_flow_dims* dims, const float
                                 const float* tp_pred, const float* params, const float* eps, const float* xg, const float* states,
                                 const float* zs, const float* d_out, float* grads, void* workspace, size_t workspace_bytes,
                                 immtsf_stream_t stream);
+/* The same five with the time net as an argument (added within ABI 7: new functions only; the struct is unchanged).  time_net:
+ * IMMTSF_NF_TIME_LINEAR, phi = scale t -- exactly the calls above, the same kernels and bits -- or IMMTSF_NF_TIME_TANH,
+ * phi = tanhf(scale t), for both halves (phi_s, phi_b), a second compile-time instance of the four kernels that form phi; the backward
+ * forms phi again from the forward's expression and adds d phi (1 - phi^2) t into time_net.scale.  Parameter layout, saved state,
+ * workspace and limits are the same for both.  Any other time_net: ..._tn_supported 0, ..._tn_param_count -1, ..._tn_workspace_bytes 0,
+ * forward / backward IMMTSF_EUNSUPPORTED, and nothing is launched. */
+#define IMMTSF_NF_TIME_LINEAR 0
+#define IMMTSF_NF_TIME_TANH 1
+int immtsf_neural_flow_tn_supported(const immtsf_neural_flow_dims* dims, int32_t time_net);
+int32_t immtsf_neural_flow_tn_param_count(const immtsf_neural_flow_dims* dims, int32_t time_net);
+size_t immtsf_neural_flow_tn_workspace_bytes(const immtsf_neural_flow_dims* dims, int32_t time_net);
+int immtsf_neural_flow_tn_forward(const immtsf_neural_flow_dims* dims, int32_t time_net, const float* data, const float* mask,
+                                  const float* tp, const float* tp_pred, const float* params, const float* eps, float* out, float* xg,
+                                  float* states, float* zs, immtsf_stream_t stream);
+int immtsf_neural_flow_tn_backward(const immtsf_neural_flow_dims* dims, int32_t time_net, const float* data, const float* mask,
+                                   const float* tp, const float* tp_pred, const float* params, const float* eps, const float* xg,
+                                   const float* states, const float* zs, const float* d_out, float* grads, void* workspace,
+                                   size_t workspace_bytes, immtsf_stream_t stream);
 
 /* ---- Raw-text mode (added within ABI 7: new functions only; csrc/note_embed.hip): what immtsf.ops.gpt2_embed_notes composes with
  * immtsf_gpt2_gemm and the row kernels of the GPT-2 body (run with B = 1 over the packed rows, p_drop = 0) into reference

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """NeuralFlow.forecasting() forward + backward, fused (csrc/neural_flow.hip: two launches forward, three backward) against composed
 (IMMTSF_NEURALFLOW_FUSED=0: the reference's Python loop over the observed points on torch ops): the widths the reference's main.py forces
-for this model -- coupling flow, 2 flow layers, TimeLinear, hidden [32, 32, 32], rec_dims 40, latents 20, fp32 -- with C 5 and
+for this model -- coupling flow, 2 flow layers, hidden [32, 32, 32], rec_dims 40, latents 20, fp32, the time net of --time-net
+(TimeLinear, or TimeTanh: the kernels' TimeTanh instance, which the tool admits with config.neuralflow_tanh_fused) -- with C 5 and
 L = Lp = 24 (config 2's window), every window with its own times (observed times sorted uniform draws in [0, 0.6], forecast times in
 [0.62, 1]), at B = 64 windows, every parameter 0.1 randn off its init.  In ONE process, after warming both paths: alternating passes of
 `--iters` eager steps each, then passes of replays of each path's captured hipGraph (torch.cuda.graph over forward + backward; neither
@@ -11,7 +12,7 @@ path's graph (torch.profiler), all kernels and the backbone's own (nf_*).
 
 The driver (no --one) runs every B as a child process under its own time limit and stops at the first that fails.
 
-usage: python tools/neuralflow_bench.py [--iters 20] [--passes 3] [--limit 300] [--out FILE]
+usage: python tools/neuralflow_bench.py [--time-net TimeLinear|TimeTanh] [--iters 20] [--passes 3] [--limit 300] [--out FILE]
 """
 import argparse
 import json
@@ -41,15 +42,16 @@ def count_kernels(fn):
     return len(names), sum(1 for n in names if "nf_" in n)
 
 
-def one(B, iters, passes):
+def one(B, iters, passes, time_net):
     import torch
     from immtsf import config
     from models.NeuralFlow import NeuralFlow
     dev = torch.device("cuda:0")
+    config.neuralflow_tanh_fused = True      # only a TimeTanh model reads it
 
     def model():
         torch.manual_seed(0)
-        m = NeuralFlow(types.SimpleNamespace(input_len=S, pred_len=P, enc_in=C, device=dev))
+        m = NeuralFlow(types.SimpleNamespace(input_len=S, pred_len=P, enc_in=C, device=dev, nf_time_net=time_net))
         gp = torch.Generator().manual_seed(2)
         with torch.no_grad():
             for p in m.parameters():
@@ -134,13 +136,14 @@ def main():
     ap.add_argument("--limit", type=int, default=300, help="seconds a child process may take")
     ap.add_argument("--one", type=int, default=None, help="run this B in this process")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--time-net", default="TimeLinear", choices=("TimeLinear", "TimeTanh"))
     args = ap.parse_args()
     if args.one is not None:
-        return one(args.one, args.iters, args.passes)
+        return one(args.one, args.iters, args.passes, args.time_net)
     lines = []
     for B in BATCHES:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--one", str(B), "--iters", str(args.iters),
-               "--passes", str(args.passes)]
+               "--passes", str(args.passes), "--time-net", args.time_net]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(r.stdout)
         sys.stdout.flush()
