@@ -134,6 +134,13 @@ ttm_fused = os.environ.get("IMMTSF_TTM_FUSED", "1") != "0"
 # IMMTSF_INFORMER_FUSED=0: the composed path (torch gather / sort / scatter, nn.BatchNorm1d, nn.MaxPool1d) with the same tie rule -- the
 # cross-check.  The kernels are fp32 in either precision mode
 informer_fused = os.environ.get("IMMTSF_INFORMER_FUSED", "1") != "0"
+# Informer's model (models.Informer): everything around the layers -- padding, masked instance norm, the input concatenations and both
+# DataEmbeddings as one HIP launch forward and two backward, decoder.norm + decoder.projection + de-normalisation + the slice to the horizon
+# as one forward and two backward (csrc/informer.hip) -- wherever immtsf_informer_model_supported allows, c_out == C, the batch fits the
+# model lengths and wants no gradient; IMMTSF_INFORMER_MODEL_FUSED=0: the composed path (the reference's sequence on torch ops,
+# immtsf.ops.token_embed, layer_norm and linear) -- the cross-check.  Independent of informer_fused, which steers the layers.  fp32 in
+# either precision mode
+informer_model_fused = os.environ.get("IMMTSF_INFORMER_MODEL_FUSED", "1") != "0"
 # CRU's Kalman recurrence as one HIP launch forward and two backward (csrc/cru.hip) wherever the cell is the continuous CRUCell with the
 # single Linear + softmax coefficient net and immtsf_cru_supported allows; IMMTSF_CRU_FUSED=0: the composed path (a Python loop over the
 # time points around torch.matrix_exp) -- the cross-check.  The kernels are fp32 in either precision mode

@@ -2,7 +2,7 @@
 
 `imm-tsf_amd/` goes FIRST on sys.path and ships packages with the reference's names (`fusions`, `layers`, `models`,
 `lib`).  A regular package would hide the reference's directory of the same name, and with it every module this build
-does not mirror (`lib.utils`, `lib.parse_datasets`, `models.Informer`, ...), so:
+does not mirror (`lib.utils`, `lib.parse_datasets`, `layers.Attn_Bias`, ...), so:
 
   * `extend_package_path` (called from each package's __init__) appends the same-named directories found further along
     sys.path to the package's __path__: mirrored modules resolve here, everything else resolves to the reference;
@@ -14,7 +14,8 @@ does not mirror (`lib.utils`, `lib.parse_datasets`, `models.Informer`, ...), so:
     names -- while this build replaces some of its entry points: when `<package>.<leaf>` is imported, the reference's module further
     along the package's __path__ is executed as usual and then handed to `install(module)` of the module here that carries the
     replacements (`lib.parse_datasets`: the reference's module with `parse_datasets` / `get_input_and_pred_len` of
-    `lib.resident_datasets` installed).  With no such module on the path the name is an alias of the module here, so it imports
+    `lib.resident_datasets` installed; `models.Informer`: the reference's module with the `Informer` class of `models.informer_model`
+    installed when what it finds there is the reference's model).  With no such module on the path the name is an alias of the module here, so it imports
     standalone too.  Why not a mirrored file lib/parse_datasets.py ending in reexport_missing, like the others:
     tests/test_dropin_packages.py::test_reference_main_imports_resolve_with_this_tree_in_front pins `lib.parse_datasets.__file__` to the
     tree behind this one, and a file of that name here would always be found first.

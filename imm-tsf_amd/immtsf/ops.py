@@ -3080,6 +3080,125 @@ def conv_distil(x, conv, norm, training, precision=None):
                               float(norm.momentum), bool(training))
 
 
+# ---- Informer's model stages (csrc/informer.hip): everything of models/Informer.py that is not a layer
+SITE_INFORMER_ENC = SITE_LAYER_BASE + 46      # enc_embedding's dropout: element (b input_len + l) d_model + f
+SITE_INFORMER_DEC = SITE_LAYER_BASE + 47      # dec_embedding's dropout: element (b pred_len + t) d_model + f
+
+
+def informer_model_supported(input_len, pred_len, Cc, d_model):
+    """the limits of the fused Informer stages (immtsf_informer_model_supported): 1 <= input_len, pred_len <= 512, 1 <= C <= 32,
+    d_model % 4 == 0, 4 <= d_model <= 512 or a multiple of 64 up to 1024"""
+    return bool(_lib.load().immtsf_informer_model_supported(int(input_len), int(pred_len), int(Cc), int(d_model)))
+
+
+class InformerFrontFn(torch.autograd.Function):
+    """padding, masked instance norm, the two input concatenations and both DataEmbeddings as ONE launch; backward = the two token
+    weights' gradients in TWO (immtsf_informer_front_forward / _backward).  data / mask (B, L, C), tp (B, L), tpp (B, Lp) are data: no
+    gradient.  dims = (input_len, pred_len); drop = (p, seed, counter pointer).  -> enc (B, input_len, D), dec (B, pred_len, D), means,
+    stdev (B, 1, C)."""
+
+    @staticmethod
+    def forward(ctx, data, mask, tp, tpp, W_enc, W_dec, pe_enc, pe_dec, dims, drop):
+        lib = _lib.load()
+        data, mask, tp, tpp, W_enc, W_dec, pe_enc, pe_dec = (_c(t) for t in (data, mask, tp, tpp, W_enc, W_dec, pe_enc, pe_dec))
+        _need_gpu(data, mask, tp, tpp, W_enc, W_dec, pe_enc, pe_dec)
+        (B, L, Cc), Lp, (S, P), D = data.shape, tpp.shape[1], dims, W_enc.shape[0]
+        p, seed, cnt = drop
+        dev = data.device
+        stats = torch.empty(2, B, 1, Cc, dtype=torch.float32, device=dev)
+        enc = torch.empty(B, S, D, dtype=torch.float32, device=dev)
+        dec = torch.empty(B, P, D, dtype=torch.float32, device=dev)
+        check(lib.immtsf_informer_front_forward(B, L, S, Lp, P, Cc, D, ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(W_enc), ptr(W_dec),
+                                                ptr(pe_enc), ptr(pe_dec), ptr(stats[0]), ptr(stats[1]), ptr(enc), ptr(dec), p, seed,
+                                                SITE_INFORMER_ENC, SITE_INFORMER_DEC, cnt, stream_ptr()), "informer_front_forward")
+        ctx.cfg = (B, L, S, Lp, P, Cc, D, p, seed, cnt)
+        ctx.save_for_backward(data, mask, tp, tpp, stats)
+        ctx.mark_non_differentiable(stats)
+        return enc, dec, stats
+
+    @staticmethod
+    def backward(ctx, d_enc, d_dec, _d_stats):
+        lib = _lib.load()
+        data, mask, tp, tpp, stats = ctx.saved_tensors
+        B, L, S, Lp, P, Cc, D, p, seed, cnt = ctx.cfg
+        dev = data.device
+        d_enc = torch.zeros(B, S, D, dtype=torch.float32, device=dev) if d_enc is None else d_enc.contiguous()
+        d_dec = torch.zeros(B, P, D, dtype=torch.float32, device=dev) if d_dec is None else d_dec.contiguous()
+        dW = torch.empty(2, D, 2 * Cc + 1, 3, dtype=torch.float32, device=dev)      # every entry is written: no zero fill
+        ws = _bytes(lib.immtsf_informer_front_workspace_bytes(B, S, P, Cc, D), dev)
+        check(lib.immtsf_informer_front_backward(B, L, S, Lp, P, Cc, D, ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(stats[0]), ptr(stats[1]),
+                                                 ptr(d_enc), ptr(d_dec), ptr(dW[0]), ptr(dW[1]), p, seed, SITE_INFORMER_ENC,
+                                                 SITE_INFORMER_DEC, cnt, ptr(ws), ws.numel(), stream_ptr()), "informer_front_backward")
+        return (None,) * 4 + (dW[0] if ctx.needs_input_grad[4] else None, dW[1] if ctx.needs_input_grad[5] else None) + (None,) * 4
+
+
+def informer_front(data, mask, tp, tpp, input_len, pred_len, W_enc, W_dec, pe_enc, pe_dec, p_drop=0.0, training=False, seed=None):
+    """data, mask (B, L <= input_len, C), tp (B, L), tpp (B, Lp <= pred_len) -> (enc (B, input_len, D), dec (B, pred_len, D), means,
+    stdev (B, 1, C)) of Informer's front end.  W_enc / W_dec: the two tokenConv weights (D, 2C + 1, 3); pe_enc / pe_dec: the positional
+    tables (1, n, D) or (n, D).  The dropout masks are those of SITE_INFORMER_ENC / SITE_INFORMER_DEC under `seed` (None: a fresh
+    config.next_seed())."""
+    B, L, Cc = data.shape
+    D, Lp = W_enc.shape[0], tpp.shape[1]
+    pe_enc, pe_dec = pe_enc.reshape(-1, pe_enc.shape[-1]), pe_dec.reshape(-1, pe_dec.shape[-1])
+    if not (informer_model_supported(input_len, pred_len, Cc, D) and B >= 1 and 1 <= L <= input_len and 1 <= Lp <= pred_len) or \
+            tuple(mask.shape) != (B, L, Cc) or tuple(tp.shape) != (B, L) or tpp.shape[0] != B or \
+            tuple(W_enc.shape) != (D, 2 * Cc + 1, 3) or tuple(W_dec.shape) != (D, 2 * Cc + 1, 3) or \
+            any(t.shape[0] < max(input_len, pred_len) or t.shape[1] != D for t in (pe_enc, pe_dec)):
+        raise _lib.ImmtsfError(f"informer_front: shapes outside the fused kernel (B {B}, L {L}, input_len {input_len}, Lp {Lp}, pred_len "
+                               f"{pred_len}, C {Cc}, d_model {D})")
+    p = float(p_drop) if training else 0.0
+    drop = (p, (config.next_seed() if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF) if p > 0 else 0,
+            config.dropout_counter_ptr(data.device) if p > 0 else None)
+    enc, dec, stats = InformerFrontFn.apply(data, mask, tp, tpp, W_enc, W_dec, pe_enc, pe_dec, (int(input_len), int(pred_len)), drop)
+    return enc, dec, stats[0], stats[1]
+
+
+class InformerTailFn(torch.autograd.Function):
+    """decoder.norm -> decoder.projection -> * stdev + means on the rows t < Lp of x (B, pred_len, D) as ONE launch -> (B, Lp, C); backward =
+    dx (exact zeros in rows t >= Lp), d gamma, d beta, dW, d bias in TWO (immtsf_informer_tail_forward / _backward).  means / stdev
+    (B, 1, C) are data: no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, W, bias, means, stdev, Lp, eps):
+        lib = _lib.load()
+        x, gamma, beta, W, bias, means, stdev = (_c(t) for t in (x, gamma, beta, W, bias, means, stdev))
+        _need_gpu(x, gamma, beta, W, bias, means, stdev)
+        B, P, D = x.shape
+        Cc = W.shape[0]
+        y = torch.empty(B, Lp, Cc, dtype=torch.float32, device=x.device)
+        rows = torch.empty(2, B * Lp, dtype=torch.float32, device=x.device)      # mean, rstd of every normalised row
+        check(lib.immtsf_informer_tail_forward(B, Lp, P, Cc, D, ptr(x), ptr(gamma), ptr(beta), eps, ptr(W), ptr(bias), ptr(means), ptr(stdev),
+                                               ptr(y), ptr(rows[0]), ptr(rows[1]), stream_ptr()), "informer_tail_forward")
+        ctx.cfg = (B, Lp, P, Cc, D)
+        ctx.save_for_backward(x, gamma, beta, W, stdev, rows)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, gamma, beta, W, stdev, rows = ctx.saved_tensors
+        B, Lp, P, Cc, D = ctx.cfg
+        dx = torch.empty_like(x)
+        flat = torch.empty(2 * D + Cc * D + Cc, dtype=torch.float32, device=x.device)      # every entry is written: no zero fill
+        ws = _bytes(lib.immtsf_informer_tail_workspace_bytes(B, Lp, Cc, D), x.device)
+        check(lib.immtsf_informer_tail_backward(B, Lp, P, Cc, D, ptr(x), ptr(gamma), ptr(beta), ptr(W), ptr(stdev), ptr(rows[0]), ptr(rows[1]),
+                                                ptr(dy.contiguous()), ptr(dx), ptr(flat), ptr(ws), ws.numel(), stream_ptr()),
+              "informer_tail_backward")
+        rets = (dx, flat[:D], flat[D:2 * D], flat[2 * D:2 * D + Cc * D].view(Cc, D), flat[2 * D + Cc * D:])
+        return tuple(r if need else None for r, need in zip(rets, ctx.needs_input_grad[:5])) + (None,) * 4
+
+
+def informer_tail(x, norm, projection, means, stdev, Lp):
+    """x (B, pred_len, D) the last decoder layer's output, norm = nn.LayerNorm(D), projection = nn.Linear(D, C) with bias, means / stdev
+    (B, 1, C) of the front end -> the de-normalised forecast (B, Lp <= pred_len, C), contiguous"""
+    B, P, D = x.shape
+    Cc = projection.weight.shape[0]
+    if not (informer_model_supported(1, P, Cc, D) and 1 <= Lp <= P) or projection.bias is None or tuple(projection.weight.shape) != (Cc, D) or \
+            tuple(norm.weight.shape) != (D,) or norm.bias is None or means.numel() != B * Cc or stdev.numel() != B * Cc:
+        raise _lib.ImmtsfError(f"informer_tail: shapes outside the fused kernel (B {B}, Lp {Lp}, pred_len {P}, C {Cc}, d_model {D})")
+    return InformerTailFn.apply(x.float(), norm.weight, norm.bias, projection.weight, projection.bias, means, stdev, int(Lp), float(norm.eps))
+
+
 # ------------------------------------------------------------------------------------------------ CRU backbone
 def cru_supported(lsd, num_basis, bandwidth, T):
     """the limits of the fused CRU recurrence (immtsf_cru_supported): lsd even, 2 <= lsd <= 32, num_basis <= 256, bandwidth <= lsd / 2,

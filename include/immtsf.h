@@ -1133,6 +1133,46 @@ int immtsf_conv_distil_backward(int32_t B, int32_t L, int32_t d, int32_t trainin
                                 const float* mean, const float* rstd, const float* dout, float* dn, float* dy, float* dgamma, float* dbeta,
                                 void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
 
+/* ---- Informer's model stages (added within ABI 7: new functions only; csrc/informer.hip; reference models/Informer.py:119-184).  All fp32.
+ * front: data, mask (B, L, C), tp (B, L), tpp (B, Lp) at the caller's L <= input_len, Lp <= pred_len (rows beyond count as zeros; no
+ * padded copy), W_enc / W_dec (d_model, 2C+1, 3) the two tokenConv weights, pe_enc / pe_dec (>= max(input_len, pred_len), d_model) the
+ * positional tables.  forward, ONE launch: per (window, channel) cnt = max(sum_l mask, 1), mean = sum_l data mask / cnt,
+ * x = data mask - mean, stdev = sqrt(sum_l (x mask)^2 / cnt + 1e-5) -> means, stdev (B, C); with in = [x / stdev | mask | tp] (an
+ * unobserved or padded position carries -mean / stdev), formed on the fly,
+ *     enc[b, l, :] = drop(sum_k sum_c W_enc[:, c, k] in[b, (l + k - 1) mod input_len, c] + pe_enc[l, :])      (B, input_len, d_model)
+ *     dec[b, t, :] = drop(sum_k W_dec[:, 2C, k] tpp[b, (t + k - 1) mod pred_len] + pe_dec[t, :])            (B, pred_len, d_model)
+ * dropout: Philox keep-masks of site_enc / site_dec at the outputs' flat element indices (immtsf_dropout_mask reproduces them);
+ * seed_step_dev as everywhere (may be NULL).  backward, TWO launches: OVERWRITES dW_enc and dW_dec (d_model, 2C+1, 3) from d_enc, d_dec
+ * (the outputs' shapes), the raw batch and means / stdev of the forward; the masks are re-derived; dW_dec is exact zeros outside
+ * [:, 2C, :].  The batch gets no gradient.  tail: x (B, pred_len, d_model) the last decoder layer's output -> LayerNorm(gamma, beta,
+ * eps) -> W (C, d_model), bias (C) -> * stdev[b, c] + means[b, c] -> y (B, Lp, C) contiguous, rows t < Lp only, ONE launch; row_mean,
+ * row_rstd (B Lp) are kept for the backward, TWO launches, which OVERWRITES dx (B, pred_len, d_model; exact zeros in rows t >= Lp) and
+ * dparams = [d gamma (d_model) | d beta (d_model) | dW (C, d_model) | d bias (C)] from dy (B, Lp, C); means / stdev are data.  x, gamma,
+ * beta, W, dx 16-byte aligned.  No atomics, partial sums added in a fixed order: same inputs, same bits.
+ * ..._model_supported (host arithmetic only): 1 <= input_len, pred_len <= 512, 1 <= C <= 32, d_model % 4 == 0, 4 <= d_model <= 512 or a
+ * multiple of 64 up to 1024; otherwise the calls return IMMTSF_EUNSUPPORTED.  ..._workspace_bytes: the per-slice partial sums of the
+ * backward (host arithmetic only; 0 for unsupported dimensions). */
+int immtsf_informer_model_supported(int32_t input_len, int32_t pred_len, int32_t C, int32_t d_model);
+size_t immtsf_informer_front_workspace_bytes(int32_t B, int32_t input_len, int32_t pred_len, int32_t C, int32_t d_model);
+int immtsf_informer_front_forward(int32_t B, int32_t L, int32_t input_len, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model,
+                                  const float* data, const float* mask, const float* tp, const float* tpp, const float* W_enc,
+                                  const float* W_dec, const float* pe_enc, const float* pe_dec, float* means, float* stdev, float* enc,
+                                  float* dec, float p_drop, uint64_t seed, uint64_t site_enc, uint64_t site_dec,
+                                  const uint64_t* seed_step_dev, immtsf_stream_t stream);
+int immtsf_informer_front_backward(int32_t B, int32_t L, int32_t input_len, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model,
+                                   const float* data, const float* mask, const float* tp, const float* tpp, const float* means,
+                                   const float* stdev, const float* d_enc, const float* d_dec, float* dW_enc, float* dW_dec,
+                                   float p_drop, uint64_t seed, uint64_t site_enc, uint64_t site_dec, const uint64_t* seed_step_dev,
+                                   void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
+size_t immtsf_informer_tail_workspace_bytes(int32_t B, int32_t Lp, int32_t C, int32_t d_model);
+int immtsf_informer_tail_forward(int32_t B, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model, const float* x, const float* gamma,
+                                 const float* beta, float eps, const float* W, const float* bias, const float* means, const float* stdev,
+                                 float* y, float* row_mean, float* row_rstd, immtsf_stream_t stream);
+int immtsf_informer_tail_backward(int32_t B, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model, const float* x, const float* gamma,
+                                  const float* beta, const float* W, const float* stdev, const float* row_mean, const float* row_rstd,
+                                  const float* dy, float* dx, float* dparams, void* workspace, size_t workspace_bytes,
+                                  immtsf_stream_t stream);
+
 /* ---- device-side batch builder: the reference's collate functions over a dataset that is
  * resident in HBM.  Replaces lib/parse_datasets.py:252-295 (variable_time_collate_fn), :298-366 +
  * lib/utils.py:359-413 (patch_variable_time_collate_fn / split_and_patch_batch) and :764-824 (multimodal wrapper).

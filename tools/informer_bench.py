@@ -11,7 +11,12 @@ a synchronise at its end; a pass runs the number of steps that fills about `--se
 both paths in both modes (best pass, and all passes: their min - max is the run-to-run spread), and the device-kernel count of the step each graph captured
 (counted on an eager run of the same step: the profiler does not trace the kernels of a replayed graph).
 
-usage: python tools/informer_bench.py [--batch 32] [--len 96] [--pred 96] [--channels 8] [--passes 5] [--seconds 0.5] [--out FILE]
+With --model the module is models.Informer of this build and the two ways differ in what is AROUND the layers (the layers stay fused):
+  fused      config.informer_model_fused on: the front end one HIP launch and the output tail one (csrc/informer.hip), two each backward;
+  composed   IMMTSF_INFORMER_MODEL_FUSED=0: pad / masked norm / cat as torch ops, DataEmbedding, Decoder's own norm and projection.
+It then prints one line for the shape above and one for a small shape (B 64, input_len 96, pred_len 24, C 7, d_model 64, d_ff 256).
+
+usage: python tools/informer_bench.py [--model] [--batch 32] [--len 96] [--pred 96] [--channels 8] [--passes 5] [--seconds 0.5] [--out FILE]
 """
 import argparse
 import json
@@ -46,14 +51,25 @@ def main():
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--seconds", type=float, default=0.5)
     ap.add_argument("--out")
+    ap.add_argument("--model", action="store_true", help="models.Informer, fused stages against IMMTSF_INFORMER_MODEL_FUSED=0")
     a = ap.parse_args()
+    run(a, a.batch, a.len, a.pred, a.channels, 512, 2048)
+    if a.model:
+        run(a, 64, 96, 24, 7, 64, 256)
+
+
+def run(a, B, S, P, C, d_model, d_ff):
     import torch
     import informer_cases as IC
     from immtsf import config, step_plan
     dev = torch.device("cuda:0")
-    B, S, P, C = a.batch, a.len, a.pred, a.channels
-    opts = dict(C=C, c_out=C, input_len=S, pred_len=P, d_model=512, n_heads=2, d_ff=2048, e_layers=2, d_layers=1, factor=3, distil=True,
+    opts = dict(C=C, c_out=C, input_len=S, pred_len=P, d_model=d_model, n_heads=2, d_ff=d_ff, e_layers=2, d_layers=1, factor=3, distil=True,
                 activation="gelu", embed="fixed", freq="h")
+    if a.model:
+        from models.Informer import Informer as Model
+        knob = "informer_model_fused"
+    else:
+        Model, knob = IC.Stack, "informer_fused"
     torch.manual_seed(0)
     g = torch.Generator().manual_seed(1)
     data = torch.randn(B, S, C, generator=g).to(dev)
@@ -61,12 +77,12 @@ def main():
     tp = torch.sort(torch.rand(B, S, generator=g), 1).values.to(dev)
     tpp = torch.sort(torch.rand(B, P, generator=g), 1).values.to(dev)
     up = torch.randn(B, P, C, generator=g).to(dev)
-    models = {n: IC.Stack(IC.config(opts, batch_size=B, device=str(dev), dropout=0.1)).to(dev).train() for n in PATHS}
+    models = {n: Model(IC.config(opts, batch_size=B, device=str(dev), dropout=0.1)).to(dev).train() for n in PATHS}
     config.enable_device_counters(dev)      # a replayed graph draws fresh dropout masks
 
     def step(name):
         m = models[name]
-        config.informer_fused = name == "fused"
+        setattr(config, knob, name == "fused")
         m.zero_grad(set_to_none=True)
         (m.forecasting(tpp, data, tp, mask) * up).sum().backward()
 
@@ -102,11 +118,12 @@ def main():
     for _ in range(a.passes):
         for n in PATHS:
             replay[n].append(timed(graphs[n].replay, n_r[n]))
-    res = {"tool": "informer_bench", "B": B, "L": S, "pred": P, "C": C,
+    res = {"tool": "informer_bench", "what": "model stages" if a.model else "layers", "B": B, "L": S, "pred": P, "C": C, "d_model": d_model,
            "eager_us": {n: round(min(eager[n]), 1) for n in PATHS}, "replay_us": {n: round(min(replay[n]), 1) for n in PATHS},
            "eager_us_all": {n: [round(t, 1) for t in eager[n]] for n in PATHS},
            "replay_us_all": {n: [round(t, 1) for t in replay[n]] for n in PATHS},
            "graph_kernels": {n: count_kernels(lambda: step(n)) for n in PATHS}}
+    setattr(config, knob, True)      # the next shape starts from the default
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:
