@@ -3288,33 +3288,25 @@ def _gpt2_inner(cfg):
     return cfg.n_inner if cfg.n_inner is not None else 4 * cfg.n_embd
 
 
-def gpt2_body_supported(llm_model, S_p, S_t):
-    """the limits of gpt2_body: a transformers GPT2Model with head_dim 64, gelu_new, scaled attention weights, neither the inverse-layer
-    scale nor the reordered up-cast attention, no cross attention, fp32 parameters, S = S_p + S_t <= n_positions and <= 1024"""
+def _gpt2_model_ok(llm_model):
+    """what gpt2_body_supported and gpt2_embed_notes_supported ask of the model alone"""
     from transformers import GPT2Model
-    if not isinstance(llm_model, GPT2Model) or S_p < 0 or S_t < 1:
+    if not isinstance(llm_model, GPT2Model):
         return False
     cfg = llm_model.config
-    d, H = int(cfg.n_embd), int(cfg.n_head)
     if (cfg.activation_function != "gelu_new" or not cfg.scale_attn_weights or cfg.scale_attn_by_inverse_layer_idx or
             cfg.reorder_and_upcast_attn or getattr(cfg, "add_cross_attention", False) or len(llm_model.h) < 1):
         return False
-    if d % 8 or _gpt2_inner(cfg) % 8 or any(p.dtype != torch.float32 for p in llm_model.parameters()):
+    return not (int(cfg.n_embd) % 8 or _gpt2_inner(cfg) % 8 or any(p.dtype != torch.float32 for p in llm_model.parameters()))
+
+
+def gpt2_body_supported(llm_model, S_p, S_t):
+    """the limits of gpt2_body: a transformers GPT2Model with head_dim 64, gelu_new, scaled attention weights, neither the inverse-layer
+    scale nor the reordered up-cast attention, no cross attention, fp32 parameters, S = S_p + S_t <= n_positions and <= 1024"""
+    if S_p < 0 or S_t < 1 or not _gpt2_model_ok(llm_model):
         return False
-    return bool(_lib.load().immtsf_gpt2_supported(d, H, int(S_p + S_t), int(cfg.n_positions)))
-
-
-def _gpt2_w16(model, W):
-    """bf16 image of a frozen Conv1D weight, same (in, out) layout, cached on the model and keyed by the parameter's storage address and
-    version: load_state_dict(), .to() or any in-place write makes a new one"""
-    cache = model.__dict__.setdefault("_immtsf_gpt2_w16", {})
-    key = (W.data_ptr(), W._version, tuple(W.shape))
-    hit = cache.get(id(W))
-    if hit is None or hit[0] != key:
-        h = torch.empty(W.shape, dtype=torch.bfloat16, device=W.device)
-        check(_lib.load().immtsf_f32_to_bf16(ptr(W.detach().contiguous()), ptr(h), W.numel(), stream_ptr()), "f32_to_bf16")
-        hit = cache[id(W)] = (key, h)
-    return hit[1]
+    cfg = llm_model.config
+    return bool(_lib.load().immtsf_gpt2_supported(int(cfg.n_embd), int(cfg.n_head), int(S_p + S_t), int(cfg.n_positions)))
 
 
 split_product_calls = 0          # products of the frozen bodies / note-embedding operators that ran on immtsf_gemm_split
@@ -3328,21 +3320,93 @@ def _split_images(W):
     return hi, lo
 
 
+# ---- host helpers of the frozen-LLM drivers (the three TimeLLM bodies and the three note embedders below) --------------------------------
+class _FrozenEntry:
+    """what _frozen_cached keeps: the fp32 items `build` made (w: the first, the weight) and, made when first asked for, w's bf16 image
+    and its (hi, lo) pair"""
+    __slots__ = ("key", "items", "w", "w16", "split")
+
+    def __init__(self, key, items):
+        self.key, self.items, self.w, self.w16, self.split = key, items, items[0], None, None
+
+    def image(self, bf, sp):
+        if bf:
+            if self.w16 is None:
+                self.w16 = torch.empty(self.w.shape, dtype=torch.bfloat16, device=self.w.device)
+                check(_lib.load().immtsf_f32_to_bf16(ptr(self.w), ptr(self.w16), self.w.numel(), stream_ptr()), "f32_to_bf16")
+            return self.w16
+        if sp:
+            if self.split is None:
+                self.split = _split_images(self.w)
+            return self.split
+        return None
+
+
+def _frozen_cached(model, owner, slot, params, build):
+    """the _FrozenEntry of (owner, slot), cached on the model and keyed by the storage address, version and shape of every parameter in
+    `params`: load_state_dict(), .to() or any in-place write makes a new one, by build() -> the tuple of contiguous fp32 items"""
+    cache = model.__dict__.setdefault("_immtsf_frozen", {})
+    key = tuple([(p.data_ptr(), p._version, tuple(p.shape)) for p in params])
+    hit = cache.get((id(owner), slot))
+    if hit is None or hit.key != key:
+        hit = cache[(id(owner), slot)] = _FrozenEntry(key, build())
+    return hit
+
+
+def _gpt2_w(model, W):
+    return _frozen_cached(model, W, "w", (W,), lambda: (W.detach().contiguous(),))
+
+
+def _gpt2_w16(model, W):
+    """bf16 image of a frozen Conv1D weight, same (in, out) layout, cached and remade as _frozen_cached says"""
+    return _gpt2_w(model, W).image(True, False)
+
+
 def _gpt2_w_split(model, W):
-    """(hi, lo) bf16 images of a frozen weight, same layout, cached on the model and keyed exactly as _gpt2_w16 keys its image: by the
-    parameter's storage address and version, so load_state_dict(), .to() or any in-place write makes a new pair"""
-    cache = model.__dict__.setdefault("_immtsf_gpt2_w_split", {})
-    key = (W.data_ptr(), W._version, tuple(W.shape))
-    hit = cache.get(id(W))
-    if hit is None or hit[0] != key:
-        hit = cache[id(W)] = (key, _split_images(W.detach().contiguous()))
-    return hit[1]
+    """(hi, lo) bf16 images of a frozen weight, same layout, in the entry that holds _gpt2_w16's image"""
+    return _gpt2_w(model, W).image(False, True)
 
 
 def _w_img(model, W, bf, sp):
     """what a frozen product reads beside the fp32 weight: its bf16 image in bf16 mode, its (hi, lo) pair under
     config.frozen_products == "split" in fp32 mode, else nothing"""
-    return _gpt2_w16(model, W) if bf else _gpt2_w_split(model, W) if sp else None
+    return _gpt2_w(model, W).image(bf, sp) if (bf or sp) else None
+
+
+def _adr(t, off=0):
+    """device pointer of element `off` of a tensor (or None)"""
+    return None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())
+
+
+def _allocators(dev, bf=True):
+    """(f32, b16): torch.empty(*shape) in that dtype on dev; with bf false, b16 gives None (no bf16 copy is kept in fp32 mode)"""
+    f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
+    b16 = (lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)) if bf else (lambda *s: None)      # noqa: E731
+    return f32, b16
+
+
+def _tail_rows(t, B, rows_per_b, S_t):
+    """the last S_t rows of every sequence of a (B rows_per_b, ...) tensor, compact"""
+    if rows_per_b == S_t:
+        return t
+    return t.view(B, rows_per_b, -1)[:, rows_per_b - S_t:].contiguous().view(B * S_t, -1)
+
+
+class _Carver:
+    """carve(rows, cols, dt): the next matrix of a byte workspace, every start rounded up to 256 bytes -- the layout include/immtsf.h
+    documents for the *_workspace_bytes functions; done() checks the bound, once"""
+
+    def __init__(self, ws):
+        self.ws, self.off = ws, 0
+
+    def __call__(self, rows, cols, dt=torch.float32):
+        nbytes = rows * cols * (2 if dt == torch.bfloat16 else 4)
+        t = self.ws[self.off:self.off + nbytes].view(dt).view(rows, cols)
+        self.off += (nbytes + 255) & ~255
+        return t
+
+    def done(self):
+        assert self.off <= self.ws.numel()
 
 
 def _frozen_gemm(lib, layout, precision, pa32, pa16, lda, W, img, w_off, ldb, out, c_off, ldc, bias, M, N, K, st, what="gpt2_gemm"):
@@ -3351,19 +3415,115 @@ def _frozen_gemm(lib, layout, precision, pa32, pa16, lda, W, img, w_off, ldb, ou
     it, both read from element offset w_off at pitch ldb; out written from element offset c_off.  An (hi, lo) pair goes to
     immtsf_gemm_split when that supports the shape; anything else is immtsf_gpt2_gemm's call as it always was."""
     global split_product_calls
-
-    def off(t, o):
-        return None if t is None else C.c_void_p(t.data_ptr() + o * t.element_size())
-
     if isinstance(img, tuple):
         if lib.immtsf_gemm_split_supported(layout, M, N, K, lda, ldb, ldc):
-            check(lib.immtsf_gemm_split(layout, pa32, lda, off(img[0], w_off), off(img[1], w_off), ldb, off(out, c_off), ldc, bias, M, N, K, st),
+            check(lib.immtsf_gemm_split(layout, pa32, lda, _adr(img[0], w_off), _adr(img[1], w_off), ldb, _adr(out, c_off), ldc, bias, M, N, K, st),
                   what + " (split)")
             split_product_calls += 1
             return
         img = None
-    check(lib.immtsf_gpt2_gemm(layout, precision, pa32, pa16, lda, off(W, w_off), off(img, w_off), ldb, off(out, c_off), ldc, bias, M, N, K, st),
+    check(lib.immtsf_gpt2_gemm(layout, precision, pa32, pa16, lda, _adr(W, w_off), _adr(img, w_off), ldb, _adr(out, c_off), ldc, bias, M, N, K, st),
           what)
+
+
+class _FrozenProducts:
+    """the weight products of one pass over a frozen model in one precision mode: bf (bf16 mode), sp (fp32 mode under
+    config.frozen_products == "split") and _frozen_gemm's calls for nn.Linear weights (N, K) and GPT-2's Conv1D weights (in, out), each
+    read as it is stored"""
+
+    def __init__(self, lib, model, precision, st):
+        self.lib, self.model, self.precision, self.st = lib, model, precision, st
+        self.bf = precision == 1
+        self.sp = config.frozen_split(precision)
+
+    def pair(self, t32, t16):
+        """(fp32 pointer, bf16 pointer) of an operand or a result kept in the mode's format: the other one is None"""
+        return (None, ptr(t16)) if self.bf else (ptr(t32), None)
+
+    def img(self, W):
+        return _w_img(self.model, W, self.bf, self.sp)
+
+    def mm(self, a32, a16, W, img, bias, rows, out, ldc, w_row=0, n_out=None, c_off=0):
+        """out[:, c_off:c_off + n_out] = a (rows, K) W[w_row:w_row + n_out]^T + bias[w_row:..] (layout 0); img: W's image as _w_img gives it"""
+        K = W.shape[1]
+        n_out = W.shape[0] if n_out is None else n_out
+        p32, p16 = self.pair(a32, a16)
+        _frozen_gemm(self.lib, 0, self.precision, p32, p16, K, W, img, w_row * K, K, out, c_off, ldc, _adr(bias, w_row), rows, n_out, K, self.st)
+
+    def lin(self, a32, a16, dense, rows, out):
+        """out (rows, N) = a dense.weight^T + dense.bias"""
+        self.mm(a32, a16, dense.weight, self.img(dense.weight), dense.bias, rows, out, dense.weight.shape[0])
+
+    def mm_t(self, g32, g16, W, img, rows):
+        """g (rows, N) W -> (rows, K) fp32: the backward of mm (layout 1)"""
+        N, K = W.shape
+        o = torch.empty(rows, K, dtype=torch.float32, device=W.device)
+        p32, p16 = self.pair(g32, g16)
+        _frozen_gemm(self.lib, 1, self.precision, p32, p16, N, W, img, 0, K, o, 0, K, None, rows, K, N, self.st, "gpt2_gemm (backward)")
+        return o
+
+    def lin_t(self, g32, g16, dense, rows):
+        return self.mm_t(g32, g16, dense.weight, self.img(dense.weight), rows)
+
+    def conv(self, pa, conv, M, N, K, out, ldc, w_off=0, c_off=0):
+        """out[:, c_off:c_off + N] = a (M, K) W[:, w_off:w_off + N] + bias[w_off:..]: W (in, out) a Conv1D's weight (layout 1); pa: a's
+        (fp32, bf16) pointers"""
+        W = conv.weight
+        _frozen_gemm(self.lib, 1, self.precision, pa[0], pa[1], K, W, self.img(W), w_off, W.shape[1], out, c_off, ldc,
+                     _adr(conv.bias, w_off), M, N, K, self.st)
+
+    def conv_t(self, g, conv, N, K):
+        """g (M, K) fp32 W^T -> (M, N) fp32: the backward of conv (layout 0; the fp32 operand in either mode)"""
+        W = conv.weight
+        o = torch.empty(g.shape[0], N, dtype=torch.float32, device=g.device)
+        _frozen_gemm(self.lib, 0, self.precision, ptr(g), None, K, W, _w_img(self.model, W, False, self.sp), 0, K, o, 0, N, None,
+                     g.shape[0], N, K, self.st, "gpt2_gemm (backward)")
+        return o
+
+
+def _body_inputs(name, llm_model, prefix_embeds, tail_embeds, supported):
+    """(tail, prefix or None, need_bwd) as the body Functions take them; raises outside `supported`"""
+    tail = _c(tail_embeds.float())
+    prefix = None if prefix_embeds is None or prefix_embeds.shape[1] == 0 else _c(prefix_embeds.detach().float())
+    _need_gpu(tail, prefix)
+    if not supported(llm_model, 0 if prefix is None else prefix.shape[1], tail.shape[1]):
+        raise _lib.ImmtsfError(f"{name}: this body / sequence length is outside {name}_supported")
+    return tail, prefix, torch.is_grad_enabled() and tail.requires_grad
+
+
+def _body_drops(probs, training, seed):
+    """(the dropout probabilities, zeros outside training; the Philox key: `seed`, or config.next_seed() when a dropout is on)"""
+    drops = tuple(float(p) if training else 0.0 for p in probs)
+    if seed is None:
+        seed = config.next_seed() if any(p > 0.0 for p in drops) else 0
+    return drops, int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _notes_prologue(name, llm_model, ids, cu, precision, max_len, supported, d_of, widest_of, empty_first=False):
+    """what the three *_embed_notes do before their first launch: the checks in their order, max_len (read from cu when not given: one
+    device -> host copy), the pass's _FrozenProducts and the result buffer -> (pooled, done, ids, cu, max_len, products); done: pooled is
+    the result already (no note, or no token at all).  d_of(cfg): the width, read before `supported` is asked; widest_of(cfg): the
+    widest workspace row, read after it; empty_first: no note returns before the model is looked at"""
+    _need_gpu(ids, cu)
+    if ids.dtype != torch.int32 or cu.dtype != torch.int32 or ids.dim() != 1 or cu.dim() != 1 or cu.numel() < 1:
+        raise _lib.ImmtsfError(f"{name}: ids (sum L) and cu (N + 1) are int32 vectors")
+    ids, cu = _c(ids), _c(cu)
+    N, T = cu.numel() - 1, ids.numel()
+    d = d_of(llm_model.config)
+    if N == 0 and empty_first:
+        return torch.zeros(0, d, dtype=torch.float32, device=ids.device), True, ids, cu, max_len, None
+    if max_len is None:
+        max_len = int((cu[1:] - cu[:-1]).max()) if T and N else 1
+    max_len = max(int(max_len), 1)
+    if not supported(llm_model, max_len):
+        raise _lib.ImmtsfError(f"{name}: this model / note length is outside {name}_supported")
+    if N == 0:
+        return torch.zeros(0, d, dtype=torch.float32, device=ids.device), True, ids, cu, max_len, None
+    if T >= 2 ** 31 // (4 * widest_of(llm_model.config)):
+        raise _lib.ImmtsfError(f"{name}: too many tokens for one call (split the batch)")
+    products = _FrozenProducts(_lib.load(), llm_model, config.precision_code(precision), stream_ptr())
+    pooled = torch.empty(N, d, dtype=torch.float32, device=ids.device)
+    return (pooled.zero_() if T == 0 else pooled), T == 0, ids, cu, max_len, products
 
 
 class GPT2BodyFn(torch.autograd.Function):
@@ -3381,20 +3541,15 @@ class GPT2BodyFn(torch.autograd.Function):
         B, S_t, d = tail.shape
         S_p = 0 if prefix is None else prefix.shape[1]
         S, H, inner, L = S_p + S_t, int(cfg.n_head), _gpt2_inner(cfg), len(model.h)
-        dev = tail.device
-        bf = precision == 1
-        sp = config.frozen_split(precision)
+        P = _FrozenProducts(lib, model, precision, st)
+        bf = P.bf
         p_e, p_a, p_r = p_drops
         eps = float(cfg.layer_norm_epsilon)
         scale = 1.0 / float(d // H) ** 0.5
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
-        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)      # noqa: E731
-        adr = lambda t, off=0: None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
+        f32, b16 = _allocators(tail.device)
 
-        def mm(a32, a16, W, bias, M, N, K, out, ldc, w_off=0, c_off=0):
-            """out[:, c_off:c_off+N] = a (M, K) W[:, w_off:w_off+N] + bias[w_off:...]; W is the Conv1D weight (in, out)"""
-            _frozen_gemm(lib, 1, precision, ptr(a32), ptr(a16), K, W, _w_img(model, W, bf, sp), w_off, W.shape[1], out, c_off, ldc,
-                         adr(bias, w_off), M, N, K, st)
+        def mm(a32, a16, conv, M, N, K, out, ldc, w_off=0, c_off=0):      # (both pointers as they are: the attention output has both)
+            P.conv((ptr(a32), ptr(a16)), conv, M, N, K, out, ldc, w_off, c_off)
 
         def ln(x, rows_per_b, s_from, norm, stats):
             n = B * (rows_per_b - s_from)
@@ -3404,10 +3559,7 @@ class GPT2BodyFn(torch.autograd.Function):
                                             ptr(mean), ptr(rstd), st), "gpt2_layernorm")
             return y32, y16, mean, rstd
 
-        def tl(t, rows_per_b):        # the tail rows of a (B rows_per_b, ...) tensor, compact
-            if rows_per_b == S_t:
-                return t
-            return t.view(B, rows_per_b, -1)[:, rows_per_b - S_t:].contiguous().view(B * S_t, -1)
+        tl = lambda t, rows_per_b: _tail_rows(t, B, rows_per_b, S_t)      # noqa: E731
 
         x = f32(B * S, d)
         check(lib.immtsf_gpt2_embed(ptr(prefix), ptr(tail), ptr(model.wpe.weight), B, S_p, S_t, d, p_e, seed, GPT2_SITE_EMBD, ptr(x), st),
@@ -3421,29 +3573,29 @@ class GPT2BodyFn(torch.autograd.Function):
             h32, h16, mean1, rstd1 = ln(x, S, 0, blk.ln_1, need_bwd)
             qkv = f32(B * S, 3 * d)
             if qf == 0:
-                mm(h32, h16, ca.weight, ca.bias, B * S, 3 * d, d, qkv, 3 * d)
+                mm(h32, h16, ca, B * S, 3 * d, d, qkv, 3 * d)
                 q, ldq = qkv, 3 * d
             else:           # the last block: K and V of all rows, queries of the tail rows
-                mm(h32, h16, ca.weight, ca.bias, B * S, 2 * d, d, qkv, 3 * d, w_off=d, c_off=d)
+                mm(h32, h16, ca, B * S, 2 * d, d, qkv, 3 * d, w_off=d, c_off=d)
                 t32, t16, _, _ = ln(x, S, qf, blk.ln_1, False)
                 q, ldq = f32(B * Sq, d), d
-                mm(t32, t16, ca.weight, ca.bias, B * Sq, d, d, q, d)
+                mm(t32, t16, ca, B * Sq, d, d, q, d)
             ao32 = f32(B * Sq, d) if (need_bwd or not bf) else None
             ao16 = b16(B * Sq, d) if bf else None
             lse = f32(B, H, Sq) if need_bwd else None
-            check(lib.immtsf_gpt2_attention_forward(ptr(q), ldq, adr(qkv, d), adr(qkv, 2 * d), 3 * d, B, S, H, qf, scale, p_a, seed, s_attn,
+            check(lib.immtsf_gpt2_attention_forward(ptr(q), ldq, _adr(qkv, d), _adr(qkv, 2 * d), 3 * d, B, S, H, qf, scale, p_a, seed, s_attn,
                                                     ptr(ao32), ptr(ao16), ptr(lse), st), "gpt2_attention_forward")
             pr = f32(B * Sq, d)
-            mm(ao32, ao16, cp.weight, cp.bias, B * Sq, d, d, pr, d)
+            mm(ao32, ao16, cp, B * Sq, d, d, pr, d)
             x1 = f32(B * Sq, d)
             check(lib.immtsf_gpt2_residual(ptr(x), B, S, qf, Sq, S, qf, d, ptr(pr), p_r, seed, s_r1, ptr(x1), st), "gpt2_residual")
             g32, g16, mean2, rstd2 = ln(x1, Sq, 0, blk.ln_2, need_bwd)
             pre = f32(B * Sq, inner)
-            mm(g32, g16, fc.weight, fc.bias, B * Sq, inner, d, pre, inner)
+            mm(g32, g16, fc, B * Sq, inner, d, pre, inner)
             a32, a16 = (None, b16(B * Sq, inner)) if bf else (f32(B * Sq, inner), None)
             check(lib.immtsf_gpt2_gelu(ptr(pre), pre.numel(), ptr(a32), ptr(a16), st), "gpt2_gelu")
             mo = f32(B * Sq, d)
-            mm(a32, a16, mp.weight, mp.bias, B * Sq, d, inner, mo, d)
+            mm(a32, a16, mp, B * Sq, d, inner, mo, d)
             x2 = f32(B * Sq, d)
             check(lib.immtsf_gpt2_residual(ptr(x1), B, Sq, 0, Sq, S, qf, d, ptr(mo), p_r, seed, s_r2, ptr(x2), st), "gpt2_residual")
             if need_bwd:
@@ -3469,17 +3621,10 @@ class GPT2BodyFn(torch.autograd.Function):
         B, S_p, S_t, d, H, inner = ctx.dims
         S, M = S_p + S_t, B * S_t
         p_e, p_a, p_r = ctx.drops
-        seed, prec = ctx.seed, ctx.precision
-        sp = config.frozen_split(prec)
-        dev = dout.device
+        seed = ctx.seed
+        mm_t = _FrozenProducts(lib, model, ctx.precision, st).conv_t
         scale = 1.0 / float(d // H) ** 0.5
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
-        adr = lambda t, off=0: C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
-
-        def mm_t(g, W, N, K):          # g (M, K) W^T: W is the Conv1D weight (in = N, out = K), read as it is stored
-            o = f32(M, N)
-            _frozen_gemm(lib, 0, prec, ptr(g), None, K, W, _w_img(model, W, False, sp), 0, K, o, 0, N, None, M, N, K, st, "gpt2_gemm (backward)")
-            return o
+        f32, _ = _allocators(dout.device)
 
         def ln_bwd(g, x, mean, rstd, norm, resid):
             o = f32(M, d)
@@ -3500,16 +3645,16 @@ class GPT2BodyFn(torch.autograd.Function):
             blk = model.h[li]
             x_t, mean1, rstd1, q_t, qkv, ao_t, lse_t, x1_t, mean2, rstd2, pre_t = ctx.saved[li]
             s_attn, s_r1, s_r2 = gpt2_sites(li)
-            dact = mm_t(undrop(dx, p_r, s_r2), blk.mlp.c_proj.weight, inner, d)
+            dact = mm_t(undrop(dx, p_r, s_r2), blk.mlp.c_proj, inner, d)
             dpre = f32(M, inner)
             check(lib.immtsf_gpt2_gelu_backward(ptr(pre_t), ptr(dact), dpre.numel(), ptr(dpre), st), "gpt2_gelu_backward")
-            dx1 = ln_bwd(mm_t(dpre, blk.mlp.c_fc.weight, d, inner), x1_t, mean2, rstd2, blk.ln_2, dx)
-            dao = mm_t(undrop(dx1, p_r, s_r1), blk.attn.c_proj.weight, d, d)
+            dx1 = ln_bwd(mm_t(dpre, blk.mlp.c_fc, d, inner), x1_t, mean2, rstd2, blk.ln_2, dx)
+            dao = mm_t(undrop(dx1, p_r, s_r1), blk.attn.c_proj, d, d)
             dqkv = f32(M, 3 * d)
-            check(lib.immtsf_gpt2_attention_backward(ptr(q_t), d, adr(qkv, d), adr(qkv, 2 * d), 3 * d, ptr(dao), ptr(ao_t), ptr(lse_t), B, S, H,
-                                                     S_p, scale, p_a, seed, s_attn, ptr(dqkv), adr(dqkv, d), adr(dqkv, 2 * d), 3 * d, st),
+            check(lib.immtsf_gpt2_attention_backward(ptr(q_t), d, _adr(qkv, d), _adr(qkv, 2 * d), 3 * d, ptr(dao), ptr(ao_t), ptr(lse_t), B, S, H,
+                                                     S_p, scale, p_a, seed, s_attn, ptr(dqkv), _adr(dqkv, d), _adr(dqkv, 2 * d), 3 * d, st),
                   "gpt2_attention_backward")
-            dx = ln_bwd(mm_t(dqkv, blk.attn.c_attn.weight, d, 3 * d), x_t, mean1, rstd1, blk.ln_1, dx1)
+            dx = ln_bwd(mm_t(dqkv, blk.attn.c_attn, d, 3 * d), x_t, mean1, rstd1, blk.ln_1, dx1)
         dtail = undrop(dx, p_e, GPT2_SITE_EMBD)
         return dtail.view(B, S_t, d), None, None, None, None, None, None
 
@@ -3519,17 +3664,10 @@ def gpt2_body(llm_model, prefix_embeds, tail_embeds, training, precision=None, s
     tail_embeds takes a gradient (prefix_embeds may require one; it gets none).  training: the body's three dropouts (embd / attn / resid
     pdrop of its config) are drawn from immtsf's generator -- ops.dropout_keep_mask(seed, site, ...) reproduces them (GPT2_SITE_EMBD,
     gpt2_sites(layer)); seed: the Philox key, config.next_seed() by default.  Outside gpt2_body_supported this raises: callers check."""
-    tail = _c(tail_embeds.float())
-    prefix = None if prefix_embeds is None or prefix_embeds.shape[1] == 0 else _c(prefix_embeds.detach().float())
-    _need_gpu(tail, prefix)
-    if not gpt2_body_supported(llm_model, 0 if prefix is None else prefix.shape[1], tail.shape[1]):
-        raise _lib.ImmtsfError("gpt2_body: this body / sequence length is outside gpt2_body_supported")
+    tail, prefix, need_bwd = _body_inputs("gpt2_body", llm_model, prefix_embeds, tail_embeds, gpt2_body_supported)
     cfg = llm_model.config
-    drops = (float(cfg.embd_pdrop), float(cfg.attn_pdrop), float(cfg.resid_pdrop)) if training else (0.0, 0.0, 0.0)
-    if seed is None:
-        seed = config.next_seed() if any(p > 0.0 for p in drops) else 0
-    need_bwd = torch.is_grad_enabled() and tail.requires_grad
-    return GPT2BodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), int(seed) & 0xFFFFFFFFFFFFFFFF, need_bwd)
+    drops, seed = _body_drops((cfg.embd_pdrop, cfg.attn_pdrop, cfg.resid_pdrop), training, seed)
+    return GPT2BodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), seed, need_bwd)
 
 
 # ------------------------------------------------------------------------------------------------ raw-text mode: notes through a frozen GPT-2
@@ -3537,17 +3675,10 @@ def gpt2_embed_notes_supported(llm_model, max_len):
     """the limits of gpt2_embed_notes: gpt2_body_supported's conditions on the model (a transformers GPT2Model with head_dim 64, gelu_new,
     scaled attention weights, neither the inverse-layer scale nor the reordered up-cast attention, no cross attention, fp32 parameters,
     d and the MLP width multiples of 8) and 1 <= max_len <= n_positions, <= 1024"""
-    from transformers import GPT2Model
-    if not isinstance(llm_model, GPT2Model) or max_len < 1:
+    if max_len < 1 or not _gpt2_model_ok(llm_model):
         return False
     cfg = llm_model.config
-    d, H = int(cfg.n_embd), int(cfg.n_head)
-    if (cfg.activation_function != "gelu_new" or not cfg.scale_attn_weights or cfg.scale_attn_by_inverse_layer_idx or
-            cfg.reorder_and_upcast_attn or getattr(cfg, "add_cross_attention", False) or len(llm_model.h) < 1):
-        return False
-    if d % 8 or _gpt2_inner(cfg) % 8 or any(p.dtype != torch.float32 for p in llm_model.parameters()):
-        return False
-    return bool(_lib.load().immtsf_note_embed_supported(d, H, int(max_len), int(cfg.n_positions)))
+    return bool(_lib.load().immtsf_note_embed_supported(int(cfg.n_embd), int(cfg.n_head), int(max_len), int(cfg.n_positions)))
 
 
 def gpt2_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
@@ -3558,58 +3689,29 @@ def gpt2_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
     given: one device -> host copy).  The model's parameters are read in place (the bf16 weight images of bf16 mode are gpt2_body's
     cache); runs under no_grad and saves nothing.  Outside gpt2_embed_notes_supported this raises: callers check."""
     with torch.no_grad():
-        _need_gpu(ids, cu)
-        if ids.dtype != torch.int32 or cu.dtype != torch.int32 or ids.dim() != 1 or cu.dim() != 1 or cu.numel() < 1:
-            raise _lib.ImmtsfError("gpt2_embed_notes: ids (sum L) and cu (N + 1) are int32 vectors")
-        ids, cu = _c(ids), _c(cu)
-        N, T = cu.numel() - 1, ids.numel()
+        pooled, done, ids, cu, max_len, P = _notes_prologue(
+            "gpt2_embed_notes", llm_model, ids, cu, precision, max_len, gpt2_embed_notes_supported, lambda cfg: int(cfg.n_embd),
+            lambda cfg: max(int(cfg.n_embd), _gpt2_inner(cfg)), empty_first=True)
+        if done:
+            return pooled
+        lib, st, precision, bf = P.lib, P.st, P.precision, P.bf
         cfg = llm_model.config
-        d = int(cfg.n_embd)
-        dev = ids.device
-        if N == 0:
-            return torch.zeros(0, d, dtype=torch.float32, device=dev)
-        if max_len is None:
-            max_len = int((cu[1:] - cu[:-1]).max()) if T else 1
-        max_len = max(int(max_len), 1)
-        if not gpt2_embed_notes_supported(llm_model, max_len):
-            raise _lib.ImmtsfError("gpt2_embed_notes: this model / note length is outside gpt2_embed_notes_supported")
-        if T >= 2 ** 31 // (4 * max(d, _gpt2_inner(cfg))):
-            raise _lib.ImmtsfError("gpt2_embed_notes: too many tokens for one call (split the batch)")
-        lib = _lib.load()
-        st = stream_ptr()
-        precision = config.precision_code(precision)
-        bf = precision == 1
-        sp = config.frozen_split(precision)
+        (N, d), T = pooled.shape, ids.numel()
         H, inner = int(cfg.n_head), _gpt2_inner(cfg)
         eps = float(cfg.layer_norm_epsilon)
         scale = 1.0 / float(d // H) ** 0.5
-        pooled = torch.empty(N, d, dtype=torch.float32, device=dev)
-        if T == 0:
-            return pooled.zero_()
         # one workspace for the whole pass, carved as include/immtsf.h lists it
-        ws = _bytes(lib.immtsf_note_embed_workspace_bytes(T, d, inner, precision), dev)
-        off = [0]
-
-        def carve(cols, op=False):
-            dt = torch.bfloat16 if (op and bf) else torch.float32
-            nbytes = T * cols * (2 if dt == torch.bfloat16 else 4)
-            t = ws[off[0]:off[0] + nbytes].view(dt).view(T, cols)
-            off[0] += (nbytes + 255) & ~255
-            return t
-
-        x, x1, h, qkv, ao, pr, pre, act = (carve(d), carve(d), carve(d, True), carve(3 * d), carve(d, True), carve(d), carve(inner),
-                                           carve(inner, True))
-        assert off[0] <= ws.numel()
-        a32 = lambda t: None if bf else ptr(t)      # noqa: E731
-        a16 = lambda t: ptr(t) if bf else None      # noqa: E731
+        carve = _Carver(_bytes(lib.immtsf_note_embed_workspace_bytes(T, d, inner, precision), ids.device))
+        op = torch.bfloat16 if bf else torch.float32
+        x, x1, h, qkv, ao, pr, pre, act = (carve(T, d), carve(T, d), carve(T, d, op), carve(T, 3 * d), carve(T, d, op), carve(T, d),
+                                           carve(T, inner), carve(T, inner, op))
+        carve.done()
 
         def mm(a, conv, N_out, K, out):
-            W = conv.weight
-            _frozen_gemm(lib, 1, precision, a32(a), a16(a), K, W, _w_img(llm_model, W, bf, sp), 0, W.shape[1], out, 0, N_out, ptr(conv.bias),
-                         T, N_out, K, st)
+            P.conv(P.pair(a, a), conv, T, N_out, K, out, N_out)
 
         def ln(src, norm, dst):
-            check(lib.immtsf_gpt2_layernorm(ptr(src), 1, T, 0, d, ptr(norm.weight), ptr(norm.bias), eps, a32(dst), a16(dst), None, None, st),
+            check(lib.immtsf_gpt2_layernorm(ptr(src), 1, T, 0, d, ptr(norm.weight), ptr(norm.bias), eps, *P.pair(dst, dst), None, None, st),
                   "gpt2_layernorm")
 
         def add(base, y, dst):
@@ -3620,13 +3722,13 @@ def gpt2_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         for blk in llm_model.h:
             ln(x, blk.ln_1, h)
             mm(h, blk.attn.c_attn, 3 * d, d, qkv)
-            check(lib.immtsf_note_embed_attention(ptr(qkv), 3 * d, ptr(cu), N, T, H, max_len, scale, precision, a32(ao), a16(ao), st),
+            check(lib.immtsf_note_embed_attention(ptr(qkv), 3 * d, ptr(cu), N, T, H, max_len, scale, precision, *P.pair(ao, ao), st),
                   "note_embed_attention")
             mm(ao, blk.attn.c_proj, d, d, pr)
             add(x, pr, x1)
             ln(x1, blk.ln_2, h)
             mm(h, blk.mlp.c_fc, inner, d, pre)
-            check(lib.immtsf_gpt2_gelu(ptr(pre), pre.numel(), a32(act), a16(act), st), "gpt2_gelu")
+            check(lib.immtsf_gpt2_gelu(ptr(pre), pre.numel(), *P.pair(act, act), st), "gpt2_gelu")
             mm(act, blk.mlp.c_proj, d, inner, pr)
             add(x1, pr, x)
         check(lib.immtsf_note_embed_pool(ptr(x), ptr(cu), N, T, d, ptr(llm_model.ln_f.weight), ptr(llm_model.ln_f.bias), eps, ptr(pooled), st),
@@ -3657,21 +3759,10 @@ def _bert_qkv(model, att, bf, sp=False):
     """(W (3d, d), bias (3d), bf16 image of W or None) of one layer's query | key | value Linears, concatenated once and cached on the model,
     keyed by the six parameters' storage address and version: load_state_dict(), .to() or any in-place write makes a new one.  sp (fp32
     mode under config.frozen_products == "split"): the third item is W's (hi, lo) pair, cached in the same entry"""
-    cache = model.__dict__.setdefault("_immtsf_bert_qkv", {})
     params = (att.query.weight, att.key.weight, att.value.weight, att.query.bias, att.key.bias, att.value.bias)
-    key = tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in params)
-    hit = cache.get(id(att))
-    if hit is None or hit[0] != key:
-        hit = cache[id(att)] = [key, torch.cat([p.detach() for p in params[:3]], 0).contiguous(),
-                                torch.cat([p.detach() for p in params[3:]], 0).contiguous(), None]
-    if bf and hit[3] is None:
-        hit[3] = torch.empty(hit[1].shape, dtype=torch.bfloat16, device=hit[1].device)
-        check(_lib.load().immtsf_f32_to_bf16(ptr(hit[1]), ptr(hit[3]), hit[1].numel(), stream_ptr()), "f32_to_bf16")
-    if sp and not bf:
-        if len(hit) == 4:
-            hit.append(_split_images(hit[1]))
-        return hit[1], hit[2], hit[4]
-    return hit[1], hit[2], hit[3]
+    hit = _frozen_cached(model, att, "qkv", params, lambda: (torch.cat([p.detach() for p in params[:3]], 0).contiguous(),
+                                                             torch.cat([p.detach() for p in params[3:]], 0).contiguous()))
+    return hit.w, hit.items[1], hit.image(bf, sp)
 
 
 def bert_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
@@ -3683,59 +3774,24 @@ def bert_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
     parameters are read in place, but for the cached query | key | value concatenation and, in bf16 mode, the cached bf16 weight images;
     runs under no_grad and saves nothing.  Outside bert_embed_notes_supported this raises: callers check."""
     with torch.no_grad():
-        _need_gpu(ids, cu)
-        if ids.dtype != torch.int32 or cu.dtype != torch.int32 or ids.dim() != 1 or cu.dim() != 1 or cu.numel() < 1:
-            raise _lib.ImmtsfError("bert_embed_notes: ids (sum L) and cu (N + 1) are int32 vectors")
-        ids, cu = _c(ids), _c(cu)
-        N, T = cu.numel() - 1, ids.numel()
+        pooled, done, ids, cu, max_len, P = _notes_prologue(
+            "bert_embed_notes", llm_model, ids, cu, precision, max_len, bert_embed_notes_supported,
+            lambda cfg: int(getattr(cfg, "hidden_size", 0)), lambda cfg: max(3 * int(cfg.hidden_size), int(cfg.intermediate_size)))
+        if done:
+            return pooled
+        lib, st, precision, bf = P.lib, P.st, P.precision, P.bf
         cfg = llm_model.config
-        d = int(getattr(cfg, "hidden_size", 0))
-        dev = ids.device
-        if max_len is None:
-            max_len = int((cu[1:] - cu[:-1]).max()) if T and N else 1
-        max_len = max(int(max_len), 1)
-        if not bert_embed_notes_supported(llm_model, max_len):
-            raise _lib.ImmtsfError("bert_embed_notes: this model / note length is outside bert_embed_notes_supported")
-        if N == 0:
-            return torch.zeros(0, d, dtype=torch.float32, device=dev)
-        inner = int(cfg.intermediate_size)
-        if T >= 2 ** 31 // (4 * max(3 * d, inner)):
-            raise _lib.ImmtsfError("bert_embed_notes: too many tokens for one call (split the batch)")
-        lib = _lib.load()
-        st = stream_ptr()
-        precision = config.precision_code(precision)
-        bf = precision == 1
-        sp = config.frozen_split(precision)
-        H = int(cfg.num_attention_heads)
+        (N, d), T = pooled.shape, ids.numel()
+        H, inner = int(cfg.num_attention_heads), int(cfg.intermediate_size)
         eps = float(cfg.layer_norm_eps)
         scale = 1.0 / float(d // H) ** 0.5
-        pooled = torch.empty(N, d, dtype=torch.float32, device=dev)
-        if T == 0:
-            return pooled.zero_()
         # one workspace for the whole pass, carved as include/immtsf.h lists it
-        ws = _bytes(lib.immtsf_bert_embed_workspace_bytes(T, d, inner, precision), dev)
-        off = [0]
-
-        def carve(cols, dt=torch.float32):
-            nbytes = T * cols * (2 if dt == torch.bfloat16 else 4)
-            t = ws[off[0]:off[0] + nbytes].view(dt).view(T, cols)
-            off[0] += (nbytes + 255) & ~255
-            return t
-
+        carve = _Carver(_bytes(lib.immtsf_bert_embed_workspace_bytes(T, d, inner, precision), ids.device))
         op = torch.bfloat16 if bf else torch.float32
-        x, x1 = carve(d), carve(d)
-        h = carve(d, torch.bfloat16) if bf else None
-        qkv, ao, pr, pre, act = carve(3 * d), carve(d, op), carve(d), carve(inner), carve(inner, op)
-        assert off[0] <= ws.numel()
-
-        def mm(a32, a16, W, W16, bias, out):
-            """out (T, N_out) = a (T, K) W^T + bias: W (N_out, K) is the nn.Linear weight as stored (layout 0)"""
-            N_out, K = W.shape
-            _frozen_gemm(lib, 0, precision, None if bf else ptr(a32), ptr(a16) if bf else None, K, W, W16, 0, K, out, 0, N_out, ptr(bias),
-                         T, N_out, K, st)
-
-        def lin(a32, a16, dense, out):
-            mm(a32, a16, dense.weight, _w_img(llm_model, dense.weight, bf, sp), dense.bias, out)
+        x, x1 = carve(T, d), carve(T, d)
+        h = carve(T, d, torch.bfloat16) if bf else None
+        qkv, ao, pr, pre, act = carve(T, 3 * d), carve(T, d, op), carve(T, d), carve(T, inner), carve(T, inner, op)
+        carve.done()
 
         def add_ln(y, base, norm, dst):
             check(lib.immtsf_bert_embed_add_layernorm(ptr(y), ptr(base), T, d, ptr(norm.weight), ptr(norm.bias), eps, ptr(dst), ptr(h), st),
@@ -3748,15 +3804,15 @@ def bert_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
                                          ptr(x), ptr(h), st), "bert_embed_rows")
         for layer in llm_model.encoder.layer:
             att = layer.attention
-            Wqkv, bqkv, Wqkv16 = _bert_qkv(llm_model, att.self, bf, sp)
-            mm(x, h, Wqkv, Wqkv16, bqkv, qkv)
-            check(lib.immtsf_bert_embed_attention(ptr(qkv), 3 * d, ptr(cu), N, T, H, max_len, scale, precision, None if bf else ptr(ao),
-                                                  ptr(ao) if bf else None, st), "bert_embed_attention")
-            lin(ao, ao, att.output.dense, pr)
+            Wqkv, bqkv, Wqkv16 = _bert_qkv(llm_model, att.self, bf, P.sp)
+            P.mm(x, h, Wqkv, Wqkv16, bqkv, T, qkv, 3 * d)
+            check(lib.immtsf_bert_embed_attention(ptr(qkv), 3 * d, ptr(cu), N, T, H, max_len, scale, precision, *P.pair(ao, ao), st),
+                  "bert_embed_attention")
+            P.lin(ao, ao, att.output.dense, T, pr)
             add_ln(pr, x, att.output.LayerNorm, x1)
-            lin(x1, h, layer.intermediate.dense, pre)
-            check(lib.immtsf_bert_embed_gelu(ptr(pre), pre.numel(), None if bf else ptr(act), ptr(act) if bf else None, st), "bert_embed_gelu")
-            lin(act, act, layer.output.dense, pr)
+            P.lin(x1, h, layer.intermediate.dense, T, pre)
+            check(lib.immtsf_bert_embed_gelu(ptr(pre), pre.numel(), *P.pair(act, act), st), "bert_embed_gelu")
+            P.lin(act, act, layer.output.dense, T, pr)
             add_ln(pr, x1, layer.output.LayerNorm, x)
         check(lib.immtsf_bert_embed_pool(ptr(x), ptr(cu), N, T, d, ptr(pooled), st), "bert_embed_pool")
         return pooled
@@ -3796,20 +3852,17 @@ def _llama_cat(model, owner, slot, linears, bf, sp=False):
     """(W, bf16 image of W or None): the weights of `linears` concatenated along the output axis, once, cached on the model under
     (owner, slot) and keyed by the parameters' storage address and version: load_state_dict(), .to() or any in-place write makes a new one.
     sp (fp32 mode under config.frozen_products == "split"): the second item is W's (hi, lo) pair, cached in the same entry"""
-    cache = model.__dict__.setdefault("_immtsf_llama_cat", {})
     params = tuple(lin.weight for lin in linears)
-    key = tuple((p.data_ptr(), p._version, tuple(p.shape)) for p in params)
-    hit = cache.get((id(owner), slot))
-    if hit is None or hit[0] != key:
-        hit = cache[(id(owner), slot)] = [key, torch.cat([p.detach() for p in params], 0).contiguous(), None]
-    if bf and hit[2] is None:
-        hit[2] = torch.empty(hit[1].shape, dtype=torch.bfloat16, device=hit[1].device)
-        check(_lib.load().immtsf_f32_to_bf16(ptr(hit[1]), ptr(hit[2]), hit[1].numel(), stream_ptr()), "f32_to_bf16")
-    if sp and not bf:
-        if len(hit) == 3:
-            hit.append(_split_images(hit[1]))
-        return hit[1], hit[3]
-    return hit[1], hit[2]
+    hit = _frozen_cached(model, owner, slot, params, lambda: (torch.cat([p.detach() for p in params], 0).contiguous(),))
+    return hit.w, hit.image(bf, sp)
+
+
+def _llama_qkv(model, att, P):
+    return _llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), P.bf, P.sp)
+
+
+def _llama_gu(model, mlp, P):
+    return _llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), P.bf, P.sp)
 
 
 def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
@@ -3821,60 +3874,30 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
     given: one device -> host copy).  The model's parameters are read in place, but for the cached q | k | v and gate | up concatenations
     and, in bf16 mode, the cached bf16 weight images; runs under no_grad and saves nothing.  Outside llama_embed_notes_supported this
     raises: callers check."""
-    with torch.no_grad():
-        _need_gpu(ids, cu)
-        if ids.dtype != torch.int32 or cu.dtype != torch.int32 or ids.dim() != 1 or cu.dim() != 1 or cu.numel() < 1:
-            raise _lib.ImmtsfError("llama_embed_notes: ids (sum L) and cu (N + 1) are int32 vectors")
-        ids, cu = _c(ids), _c(cu)
-        N, T = cu.numel() - 1, ids.numel()
-        cfg = llm_model.config
-        dev = ids.device
-        if max_len is None:
-            max_len = int((cu[1:] - cu[:-1]).max()) if T and N else 1
-        max_len = max(int(max_len), 1)
-        if not llama_embed_notes_supported(llm_model, max_len):
-            raise _lib.ImmtsfError("llama_embed_notes: this model / note length is outside llama_embed_notes_supported")
+    def widest(cfg):
         d, H, H_kv, hd, inner = _llama_dims(cfg)
-        if N == 0:
-            return torch.zeros(0, d, dtype=torch.float32, device=dev)
+        return max(d, (H + 2 * H_kv) * hd, 2 * inner)
+
+    with torch.no_grad():
+        pooled, done, ids, cu, max_len, P = _notes_prologue(
+            "llama_embed_notes", llm_model, ids, cu, precision, max_len, llama_embed_notes_supported,
+            lambda cfg: int(getattr(cfg, "hidden_size", 0)), widest)
+        if done:
+            return pooled
+        lib, st, precision, bf = P.lib, P.st, P.precision, P.bf
+        cfg = llm_model.config
+        N, T, dev = pooled.shape[0], ids.numel(), ids.device
+        d, H, H_kv, hd, inner = _llama_dims(cfg)
         dq, dqkv = H * hd, (H + 2 * H_kv) * hd
-        if T >= 2 ** 31 // (4 * max(d, dqkv, 2 * inner)):
-            raise _lib.ImmtsfError("llama_embed_notes: too many tokens for one call (split the batch)")
-        lib = _lib.load()
-        st = stream_ptr()
-        precision = config.precision_code(precision)
-        bf = precision == 1
-        sp = config.frozen_split(precision)
         eps = float(cfg.rms_norm_eps)
         scale = 1.0 / float(hd) ** 0.5
-        pooled = torch.empty(N, d, dtype=torch.float32, device=dev)
-        if T == 0:
-            return pooled.zero_()
         # one workspace for the whole pass, carved as include/immtsf.h lists it
-        ws = _bytes(lib.immtsf_llama_embed_workspace_bytes(T, d, H, H_kv, inner, max_len, precision), dev)
-        off = [0]
-
-        def carve(rows, cols, dt=torch.float32):
-            nbytes = rows * cols * (2 if dt == torch.bfloat16 else 4)
-            t = ws[off[0]:off[0] + nbytes].view(dt).view(rows, cols)
-            off[0] += (nbytes + 255) & ~255
-            return t
-
+        carve = _Carver(_bytes(lib.immtsf_llama_embed_workspace_bytes(T, d, H, H_kv, inner, max_len, precision), dev))
         op = torch.bfloat16 if bf else torch.float32
         x, h, qkv, ao, pr, gu, act = (carve(T, d), carve(T, d, op), carve(T, dqkv), carve(T, dq, op), carve(T, d), carve(T, 2 * inner),
                                       carve(T, inner, op))
         cos_t, sin_t, rstd = carve(max_len, 64), carve(max_len, 64), carve(T, 1)
-        assert off[0] <= ws.numel()
-        o32 = lambda t: None if bf else ptr(t)      # noqa: E731
-        o16 = lambda t: ptr(t) if bf else None      # noqa: E731
-
-        def mm(a, W, W16, out):
-            """out (T, N_out) = a (T, K) W^T: W (N_out, K) is the nn.Linear weight as stored (layout 0); Llama's Linears have no bias"""
-            N_out, K = W.shape
-            _frozen_gemm(lib, 0, precision, o32(a), o16(a), K, W, W16, 0, K, out, 0, N_out, None, T, N_out, K, st)
-
-        def lin(a, dense, out):
-            mm(a, dense.weight, _w_img(llm_model, dense.weight, bf, sp), out)
+        carve.done()
 
         rope = llm_model.rotary_emb
         inv_freq = rope.inv_freq.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -3886,19 +3909,21 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
             att, mlp = layer.self_attn, layer.mlp
             w_in = layer.input_layernorm.weight
             if i == 0:
-                check(lib.immtsf_llama_embed_rmsnorm(ptr(x), T, d, ptr(w_in), eps, o32(h), o16(h), st), "llama_embed_rmsnorm")
+                check(lib.immtsf_llama_embed_rmsnorm(ptr(x), T, d, ptr(w_in), eps, *P.pair(h, h), st), "llama_embed_rmsnorm")
             else:      # the residual add of the layer before rides on this norm
-                check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(w_in), eps, o32(h), o16(h), st), "llama_embed_add_rmsnorm")
-            mm(h, *_llama_cat(llm_model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf, sp), qkv)
+                check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(w_in), eps, *P.pair(h, h), st), "llama_embed_add_rmsnorm")
+            W, W16 = _llama_qkv(llm_model, att, P)
+            P.mm(h, h, W, W16, None, T, qkv, dqkv)
             check(lib.immtsf_llama_embed_rope(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, ptr(cos_t), ptr(sin_t), st), "llama_embed_rope")
-            check(lib.immtsf_llama_embed_attention(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, scale, precision, o32(ao), o16(ao), st),
+            check(lib.immtsf_llama_embed_attention(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, scale, precision, *P.pair(ao, ao), st),
                   "llama_embed_attention")
-            lin(ao, att.o_proj, pr)
-            check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(layer.post_attention_layernorm.weight), eps, o32(h), o16(h), st),
+            P.lin(ao, ao, att.o_proj, T, pr)
+            check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(layer.post_attention_layernorm.weight), eps, *P.pair(h, h), st),
                   "llama_embed_add_rmsnorm")
-            mm(h, *_llama_cat(llm_model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf, sp), gu)
-            check(lib.immtsf_llama_embed_swiglu(ptr(gu), T, inner, o32(act), o16(act), st), "llama_embed_swiglu")
-            lin(act, mlp.down_proj, pr)
+            W, W16 = _llama_gu(llm_model, mlp, P)
+            P.mm(h, h, W, W16, None, T, gu, 2 * inner)
+            check(lib.immtsf_llama_embed_swiglu(ptr(gu), T, inner, *P.pair(act, act), st), "llama_embed_swiglu")
+            P.lin(act, act, mlp.down_proj, T, pr)
         check(lib.immtsf_llama_embed_pool(ptr(x), ptr(pr), ptr(cu), N, T, d, ptr(llm_model.norm.weight), eps, ptr(rstd), ptr(pooled), st),
               "llama_embed_pool")
         return pooled
@@ -3936,23 +3961,11 @@ class LlamaBodyFn(torch.autograd.Function):
         dq, dkv = H * hd, H_kv * hd
         dqkv = dq + 2 * dkv
         dev = tail.device
-        bf = precision == 1
-        sp = config.frozen_split(precision)
+        P = _FrozenProducts(lib, model, precision, st)
+        bf = P.bf
         eps = float(cfg.rms_norm_eps)
         scale = 1.0 / float(hd) ** 0.5
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
-        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev)      # noqa: E731
-        adr = lambda t, off=0: None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
-
-        def mm(a, W, W16, M, out, ldc, w_row=0, n_out=None, c_off=0):
-            """out[:, c_off:c_off + n_out] = a (M, K) W[w_row:w_row + n_out]^T: W (N, K) is the nn.Linear weight as stored (layout 0)"""
-            K = W.shape[1]
-            n_out = W.shape[0] if n_out is None else n_out
-            _frozen_gemm(lib, 0, precision, None if bf else ptr(a), ptr(a) if bf else None, K, W, W16, w_row * K, K, out, c_off, ldc, None,
-                         M, n_out, K, st)
-
-        def lin(a, dense, M, out):
-            mm(a, dense.weight, _w_img(model, dense.weight, bf, sp), M, out, dense.weight.shape[0])
+        f32, b16 = _allocators(dev)
 
         def rms(xin, S_in, s_from, y, w, stats):
             """(row sums xin + y or xin itself, normed operand, rstd) of the rows s_from .. S_in - 1, compact"""
@@ -3960,18 +3973,15 @@ class LlamaBodyFn(torch.autograd.Function):
             xo = f32(n, d) if y is not None else None
             h = b16(n, d) if bf else f32(n, d)
             rstd = f32(n) if stats else None
-            check(lib.immtsf_llama_body_rmsnorm(ptr(xin), B, S_in, s_from, d, ptr(y), ptr(xo), ptr(w), eps, None if bf else ptr(h),
-                                                ptr(h) if bf else None, ptr(rstd), st), "llama_body_rmsnorm")
+            check(lib.immtsf_llama_body_rmsnorm(ptr(xin), B, S_in, s_from, d, ptr(y), ptr(xo), ptr(w), eps, *P.pair(h, h), ptr(rstd), st),
+                  "llama_body_rmsnorm")
             return (xin if xo is None else xo), h, rstd
 
         def rope(buf, off, ld, rows, rows_per_b, pos0, heads):
-            check(lib.immtsf_llama_body_rope(adr(buf, off), ld, rows, rows_per_b, pos0, heads, S, ptr(cos_t), ptr(sin_t), 0, None, st),
+            check(lib.immtsf_llama_body_rope(_adr(buf, off), ld, rows, rows_per_b, pos0, heads, S, ptr(cos_t), ptr(sin_t), 0, None, st),
                   "llama_body_rope")
 
-        def tl(t, rows_per_b):        # the tail rows of a (B rows_per_b, ...) tensor, compact
-            if rows_per_b == S_t:
-                return t
-            return t.view(B, rows_per_b, -1)[:, rows_per_b - S_t:].contiguous().view(B * S_t, -1)
+        tl = lambda t, rows_per_b: _tail_rows(t, B, rows_per_b, S_t)      # noqa: E731
 
         rot = model.rotary_emb
         inv_freq = rot.inv_freq.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -3986,36 +3996,35 @@ class LlamaBodyFn(torch.autograd.Function):
             qf = S_p if li == L - 1 else 0
             Sq = S - qf
             x, h, rstd1 = rms(x, Sx, 0, y, layer.input_layernorm.weight, need_bwd)
-            W, W16 = _llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf, sp)
+            W, W16 = _llama_qkv(model, att, P)
             if qf == 0:
                 qkv = f32(B * S, dqkv)
-                mm(h, W, W16, B * S, qkv, dqkv)
+                P.mm(h, h, W, W16, None, B * S, qkv, dqkv)
                 rope(qkv, 0, dqkv, B * S, S, 0, H + H_kv)
                 q, ldq, kv, ldkv, k_off = qkv, dqkv, qkv, dqkv, dq
             else:           # the last layer: K and V of all rows, queries of the tail rows
                 kv = f32(B * S, 2 * dkv)
-                mm(h, W, W16, B * S, kv, 2 * dkv, w_row=dq, n_out=2 * dkv)
+                P.mm(h, h, W, W16, None, B * S, kv, 2 * dkv, w_row=dq, n_out=2 * dkv)
                 rope(kv, 0, 2 * dkv, B * S, S, 0, H_kv)
                 _, ht, _ = rms(x, S, qf, None, layer.input_layernorm.weight, False)
                 q = f32(B * Sq, dq)
-                mm(ht, W, W16, B * Sq, q, dq, n_out=dq)
+                P.mm(ht, ht, W, W16, None, B * Sq, q, dq, n_out=dq)
                 rope(q, 0, dq, B * Sq, Sq, qf, H)
                 ldq, ldkv, k_off = dq, 2 * dkv, 0
             ao32 = f32(B * Sq, dq) if (need_bwd or not bf) else None
             ao16 = b16(B * Sq, dq) if bf else None
             lse = f32(B * Sq, H) if need_bwd else None
-            check(lib.immtsf_llama_body_attention_forward(ptr(q), ldq, adr(kv, k_off), adr(kv, k_off + dkv), ldkv, B, S, H, H_kv, qf, scale,
+            check(lib.immtsf_llama_body_attention_forward(ptr(q), ldq, _adr(kv, k_off), _adr(kv, k_off + dkv), ldkv, B, S, H, H_kv, qf, scale,
                                                           precision, ptr(ao32), ptr(ao16), ptr(lse), st), "llama_body_attention_forward")
             pr = f32(B * Sq, d)
-            lin(ao16 if bf else ao32, att.o_proj, B * Sq, pr)
+            P.lin(ao32, ao16, att.o_proj, B * Sq, pr)
             x1, g, rstd2 = rms(x, S, qf, pr, layer.post_attention_layernorm.weight, need_bwd)
             gu = f32(B * Sq, 2 * inner)
-            mm(g, *_llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf, sp), B * Sq, gu, 2 * inner)
+            P.mm(g, g, *_llama_gu(model, mlp, P), None, B * Sq, gu, 2 * inner)
             act = b16(B * Sq, inner) if bf else f32(B * Sq, inner)
-            check(lib.immtsf_llama_embed_swiglu(ptr(gu), B * Sq, inner, None if bf else ptr(act), ptr(act) if bf else None, st),
-                  "llama_embed_swiglu")
+            check(lib.immtsf_llama_embed_swiglu(ptr(gu), B * Sq, inner, *P.pair(act, act), st), "llama_embed_swiglu")
             mo = f32(B * Sq, d)
-            lin(act, mlp.down_proj, B * Sq, mo)
+            P.lin(act, act, mlp.down_proj, B * Sq, mo)
             if need_bwd:
                 if qf == 0:
                     q_t = tl(qkv[:, :dq], S)
@@ -4040,29 +4049,16 @@ class LlamaBodyFn(torch.autograd.Function):
     def backward(ctx, dout):
         lib = _lib.load()
         st = stream_ptr()
-        model, prec = ctx.model, ctx.precision
+        model = ctx.model
         B, S_p, S_t, d, H, H_kv, hd, inner = ctx.dims
         S, M = S_p + S_t, B * S_t
         dq, dkv = H * hd, H_kv * hd
         dqkv = dq + 2 * dkv
-        bf = prec == 1
-        sp = config.frozen_split(prec)
-        dev = dout.device
+        P = _FrozenProducts(lib, model, ctx.precision, st)
+        bf = P.bf
         scale = 1.0 / float(hd) ** 0.5
         cos_t, sin_t = ctx.rope
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
-        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev) if bf else None      # noqa: E731
-        adr = lambda t, off=0: C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
-
-        def mm_t(g32, g16, W, W16):       # g (M, N) W: W (N, K) is the nn.Linear weight as stored, read as it is (layout 1)
-            N, K = W.shape
-            o = f32(M, K)
-            _frozen_gemm(lib, 1, prec, None if bf else ptr(g32), ptr(g16) if bf else None, N, W, W16, 0, K, o, 0, K, None, M, K, N, st,
-                         "gpt2_gemm (backward)")
-            return o
-
-        def lin_t(g32, g16, dense):
-            return mm_t(g32, g16, dense.weight, _w_img(model, dense.weight, bf, sp))
+        f32, b16 = _allocators(dout.device, bf)
 
         def rms_bwd(g, x, rstd, w, resid):
             o, o16 = f32(M, d), b16(M, d)
@@ -4076,21 +4072,21 @@ class LlamaBodyFn(torch.autograd.Function):
             layer = model.layers[li]
             att, mlp = layer.self_attn, layer.mlp
             x_t, rstd1, q_t, kv, kv_ld, ao_t, lse_t, x1_t, rstd2, gu_t = ctx.saved[li]
-            dact = lin_t(dx, dx16, mlp.down_proj)
+            dact = P.lin_t(dx, dx16, mlp.down_proj, M)
             dgu, dgu16 = (None, b16(M, 2 * inner)) if bf else (f32(M, 2 * inner), None)
             check(lib.immtsf_llama_body_swiglu_backward(ptr(gu_t), ptr(dact), M, inner, ptr(dgu), ptr(dgu16), st),
                   "llama_body_swiglu_backward")
-            dg = mm_t(dgu, dgu16, *_llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), bf, sp))
+            dg = P.mm_t(dgu, dgu16, *_llama_gu(model, mlp, P), M)
             dx1, dx1_16 = rms_bwd(dg, x1_t, rstd2, layer.post_attention_layernorm.weight, dx)
-            dao = lin_t(dx1, dx1_16, att.o_proj)
+            dao = P.lin_t(dx1, dx1_16, att.o_proj, M)
             dbuf, dbuf16 = f32(M, dqkv), b16(M, dqkv)
             kp = C.c_void_p(kv.data_ptr())            # (a view into the q | k | v buffer starts at its K columns)
             check(lib.immtsf_llama_body_attention_backward(ptr(q_t), dq, kp, C.c_void_p(kv.data_ptr() + 4 * dkv), kv_ld, ptr(dao), ptr(ao_t),
-                                                           ptr(lse_t), B, S, H, H_kv, S_p, scale, ptr(dbuf), adr(dbuf, dq),
-                                                           adr(dbuf, dq + dkv), dqkv, st), "llama_body_attention_backward")
+                                                           ptr(lse_t), B, S, H, H_kv, S_p, scale, ptr(dbuf), _adr(dbuf, dq),
+                                                           _adr(dbuf, dq + dkv), dqkv, st), "llama_body_attention_backward")
             check(lib.immtsf_llama_body_rope(ptr(dbuf), dqkv, M, S_t, S_p, H + H_kv, S, ptr(cos_t), ptr(sin_t), 1, ptr(dbuf16), st),
                   "llama_body_rope (backward)")
-            dh = mm_t(dbuf, dbuf16, *_llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), bf, sp))
+            dh = P.mm_t(dbuf, dbuf16, *_llama_qkv(model, att, P), M)
             dx, dx16 = rms_bwd(dh, x_t, rstd1, layer.input_layernorm.weight, dx1)
         return dx.view(B, S_t, d), None, None, None, None
 
@@ -4101,14 +4097,9 @@ def llama_body(llm_model, prefix_embeds, tail_embeds, training, precision=None):
     `training` with config.attention_dropout > 0 is not supported (callers take the stock path).  The model's parameters are read in
     place, but for the cached q | k | v and gate | up concatenations and, in bf16 mode, the cached bf16 weight images (shared with
     llama_embed_notes).  Outside llama_body_supported this raises: callers check."""
-    tail = _c(tail_embeds.float())
-    prefix = None if prefix_embeds is None or prefix_embeds.shape[1] == 0 else _c(prefix_embeds.detach().float())
-    _need_gpu(tail, prefix)
-    if not llama_body_supported(llm_model, 0 if prefix is None else prefix.shape[1], tail.shape[1]):
-        raise _lib.ImmtsfError("llama_body: this body / sequence length is outside llama_body_supported")
+    tail, prefix, need_bwd = _body_inputs("llama_body", llm_model, prefix_embeds, tail_embeds, llama_body_supported)
     if training and float(getattr(llm_model.config, "attention_dropout", 0.0) or 0.0) > 0.0:
         raise _lib.ImmtsfError("llama_body: attention dropout in training mode is not supported (take the stock path)")
-    need_bwd = torch.is_grad_enabled() and tail.requires_grad
     return LlamaBodyFn.apply(tail, prefix, llm_model, config.precision_code(precision), need_bwd)
 
 
@@ -4153,26 +4144,12 @@ class BertBodyFn(torch.autograd.Function):
         S_p = 0 if prefix is None else prefix.shape[1]
         S, H, inner, L = S_p + S_t, int(cfg.num_attention_heads), int(cfg.intermediate_size), len(model.encoder.layer)
         M = B * S_t
-        dev = tail.device
-        bf = precision == 1
-        sp = config.frozen_split(precision)
+        P = _FrozenProducts(lib, model, precision, st)
+        bf, mm, lin = P.bf, P.mm, P.lin
         p_h, p_a = p_drops
         eps = float(cfg.layer_norm_eps)
         scale = 1.0 / float(d // H) ** 0.5
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
-        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev) if bf else None      # noqa: E731
-        adr = lambda t, off=0: None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
-
-        def mm(a32, a16, W, W16, bias, rows, out, ldc, w_row=0, n_out=None, c_off=0):
-            """out[:, c_off:c_off + n_out] = a (rows, K) W[w_row:w_row + n_out]^T + bias[w_row:..]: W (N, K) is the nn.Linear weight as
-            stored (layout 0)"""
-            K = W.shape[1]
-            n_out = W.shape[0] if n_out is None else n_out
-            _frozen_gemm(lib, 0, precision, None if bf else ptr(a32), ptr(a16) if bf else None, K, W, W16, w_row * K, K, out, c_off, ldc,
-                         adr(bias, w_row), rows, n_out, K, st)
-
-        def lin(a32, a16, dense, rows, out):
-            mm(a32, a16, dense.weight, _w_img(model, dense.weight, bf, sp), dense.bias, rows, out, dense.weight.shape[0])
+        f32, b16 = _allocators(tail.device, bf)
 
         def add_ln(xin, S_in, s_from, y, q_from, norm, site, out32, keep16):
             """LayerNorm(xin rows + dropout(y)) -> (out32, bf16 image or None, pre-norm sum, mean, rstd)"""
@@ -4204,7 +4181,7 @@ class BertBodyFn(torch.autograd.Function):
             Mq = B * Sq
             s_attn, s_h1, s_h2 = bert_sites(li)
             att = layer.attention
-            W, bias, W16 = _bert_qkv(model, att.self, bf, sp)
+            W, bias, W16 = _bert_qkv(model, att.self, bf, P.sp)
             qkv = f32(B * S, 3 * d)
             if qf == 0:
                 mm(x, x16, W, W16, bias, B * S, qkv, 3 * d)
@@ -4216,7 +4193,7 @@ class BertBodyFn(torch.autograd.Function):
             ao32 = f32(Mq, d) if (need_bwd or not bf) else None
             ao16 = b16(Mq, d)
             lse = f32(B, H, Sq) if need_bwd else None
-            check(lib.immtsf_bert_body_attention_forward(ptr(q), ldq, adr(qkv, d), adr(qkv, 2 * d), 3 * d, B, S, H, qf, scale, precision, p_a,
+            check(lib.immtsf_bert_body_attention_forward(ptr(q), ldq, _adr(qkv, d), _adr(qkv, 2 * d), 3 * d, B, S, H, qf, scale, precision, p_a,
                                                          seed, s_attn, ptr(ao32), ptr(ao16), ptr(lse), st), "bert_body_attention_forward")
             pr = f32(Mq, d)
             lin(ao32, ao16, att.output.dense, Mq, pr)
@@ -4246,23 +4223,10 @@ class BertBodyFn(torch.autograd.Function):
         B, S_p, S_t, d, H, inner = ctx.dims
         S, M, L = S_p + S_t, B * S_t, len(model.encoder.layer)
         p_h, p_a = ctx.drops
-        bf = prec == 1
-        sp = config.frozen_split(prec)
-        dev = dout.device
+        P = _FrozenProducts(lib, model, prec, st)
+        bf, mm_t, lin_t = P.bf, P.mm_t, P.lin_t
         scale = 1.0 / float(d // H) ** 0.5
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)       # noqa: E731
-        b16 = lambda *s: torch.empty(*s, dtype=torch.bfloat16, device=dev) if bf else None      # noqa: E731
-        adr = lambda t, off=0: C.c_void_p(t.data_ptr() + off * t.element_size())      # noqa: E731
-
-        def mm_t(g32, g16, W, W16, rows):       # g (rows, N) W: W (N, K) is the nn.Linear weight as stored, read as it is (layout 1)
-            N, K = W.shape
-            o = f32(rows, K)
-            _frozen_gemm(lib, 1, prec, None if bf else ptr(g32), ptr(g16) if bf else None, N, W, W16, 0, K, o, 0, K, None, rows, K, N, st,
-                         "gpt2_gemm (backward)")
-            return o
-
-        def lin_t(g32, g16, dense, rows):
-            return mm_t(g32, g16, dense.weight, _w_img(model, dense.weight, bf, sp), rows)
+        f32, b16 = _allocators(dout.device, bf)
 
         def ln_bwd(dy, Sn, sm, mean, rstd, norm, q_from, site):
             """dy = (dy_a, Sa, sa_from, dy_b, tb_from) -> (d_sum fp32, the branch's gradient as the next product reads it: fp32, bf16)"""
@@ -4304,14 +4268,14 @@ class BertBodyFn(torch.autograd.Function):
             if dq_off:          # the last layer of several: the prefix rows have keys and values but no query
                 dqkv.view(B, S, 3 * d)[:, :S_p, :d].zero_()
             dsum = f32(Mq, H) if bf else None
-            check(lib.immtsf_bert_body_attention_backward(ptr(q), ldq, adr(qkv, d), adr(qkv, 2 * d), 3 * d, ptr(dao), ptr(ao32), ptr(lse), B, S, H,
-                                                          qf, dq_from, k_from, scale, prec, p_a, seed, s_attn, adr(dqkv, dq_off), rows_b,
-                                                          adr(dqkv, d), adr(dqkv, 2 * d), rows_b, 3 * d, ptr(dsum), st),
+            check(lib.immtsf_bert_body_attention_backward(ptr(q), ldq, _adr(qkv, d), _adr(qkv, 2 * d), 3 * d, ptr(dao), ptr(ao32), ptr(lse), B, S, H,
+                                                          qf, dq_from, k_from, scale, prec, p_a, seed, s_attn, _adr(dqkv, dq_off), rows_b,
+                                                          _adr(dqkv, d), _adr(dqkv, 2 * d), rows_b, 3 * d, ptr(dsum), st),
                   "bert_body_attention_backward")
             dqkv16 = b16(B * rows_b, 3 * d)
             if bf:
                 check(lib.immtsf_f32_to_bf16(ptr(dqkv), ptr(dqkv16), dqkv.numel(), st), "f32_to_bf16")
-            W, _, W16 = _bert_qkv(model, att.self, bf, sp)
+            W, _, W16 = _bert_qkv(model, att.self, bf, P.sp)
             gq = mm_t(dqkv, dqkv16, W, W16, B * rows_b)
             if first:
                 dy = (dsum1, Sq, S_p - qf, gq, 0)
@@ -4341,20 +4305,13 @@ def bert_body(llm_model, prefix_embeds, tail_embeds, training, precision=None, s
     ops.dropout_keep_mask(seed, site, ...) reproduces them (BERT_SITE_EMBD, bert_sites(layer)); seed: the Philox key, config.next_seed()
     by default.  The model's parameters are read in place, but for the cached query | key | value concatenation and, in bf16 mode, the
     cached bf16 weight images (shared with bert_embed_notes).  Outside bert_body_supported this raises: callers check."""
-    tail = _c(tail_embeds.float())
-    prefix = None if prefix_embeds is None or prefix_embeds.shape[1] == 0 else _c(prefix_embeds.detach().float())
-    _need_gpu(tail, prefix)
-    if not bert_body_supported(llm_model, 0 if prefix is None else prefix.shape[1], tail.shape[1]):
-        raise _lib.ImmtsfError("bert_body: this body / sequence length is outside bert_body_supported")
+    tail, prefix, need_bwd = _body_inputs("bert_body", llm_model, prefix_embeds, tail_embeds, bert_body_supported)
     if tail.dim() != 3 or tail.shape[2] != llm_model.config.hidden_size or \
             (prefix is not None and (prefix.shape[0] != tail.shape[0] or prefix.shape[2] != tail.shape[2])):
         raise _lib.ImmtsfError("bert_body: prefix (B, S_p, d) and tail (B, S_t, d) with d the body's hidden_size")
     cfg = llm_model.config
-    drops = (float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)) if training else (0.0, 0.0)
-    if seed is None:
-        seed = config.next_seed() if any(p > 0.0 for p in drops) else 0
-    need_bwd = torch.is_grad_enabled() and tail.requires_grad
-    return BertBodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), int(seed) & 0xFFFFFFFFFFFFFFFF, need_bwd)
+    drops, seed = _body_drops((cfg.hidden_dropout_prob, cfg.attention_probs_dropout_prob), training, seed)
+    return BertBodyFn.apply(tail, prefix, llm_model, drops, config.precision_code(precision), seed, need_bwd)
 
 
 # ---- TimeLLM's prompt statistics (csrc/timellm_prompt.hip) -------------------------------------------------------------------------------

@@ -170,6 +170,56 @@ def test_weight_images_follow_the_weight():
             W.copy_(keep)
 
 
+def _image_cases():
+    """name -> (image(bf): the bf16 image (bf) or the (hi, lo) pair of the cached fp32 weight, weight(): that weight restated, the
+    parameter the test writes) on the one-layer bodies of the three body test files"""
+    from immtsf import ops
+    g, b, m = TG._body(1, 0.0), TB._model("a", 1), TL._model("a", 1)
+    Wg, att, sa = g.h[0].mlp.c_fc.weight, b.encoder.layer[0].attention.self, m.layers[0].self_attn
+    qkv = (sa.q_proj, sa.k_proj, sa.v_proj)
+    return {"gpt2_w16": (lambda bf: ops._gpt2_w16(g, Wg) if bf else ops._gpt2_w_split(g, Wg), lambda: Wg.detach(), Wg),
+            "bert_qkv": (lambda bf: ops._bert_qkv(b, att, bf, not bf)[2],
+                         lambda: torch.cat([att.query.weight, att.key.weight, att.value.weight], 0), att.key.bias),
+            "llama_cat": (lambda bf: ops._llama_cat(m, sa, "qkv", qkv, bf, not bf)[1], lambda: torch.cat([p.weight for p in qkv], 0),
+                          sa.k_proj.weight)}
+
+
+def _is_rounding_of(img, W):
+    if isinstance(img, tuple):
+        return torch.equal(img[0], W.to(torch.bfloat16)) and torch.equal(img[1], (W - img[0].float()).to(torch.bfloat16))
+    return torch.equal(img, W.to(torch.bfloat16))
+
+
+@pytest.mark.parametrize("name", ["gpt2_w16", "bert_qkv", "llama_cat"])
+def test_cached_images_follow_their_parameters(name):
+    """_gpt2_w16, _bert_qkv and _llama_cat: the same object on a second call, the image equal to the weight's rounding, a new object after
+    an in-place write to one of the keyed parameters (for _bert_qkv the key's bias, the fifth of its six) -- and the bf16 image and the
+    (hi, lo) pair live side by side in one entry, whichever is asked for first"""
+    from immtsf import ops
+    TG._dev()
+    image, weight, written = _image_cases()[name]
+    a16 = image(True)
+    assert image(True) is a16 and _is_rounding_of(a16, weight())
+    pair = image(False)
+    assert isinstance(pair, tuple) and image(False) is pair and _is_rounding_of(pair, weight())
+    assert image(True) is a16                                   # the pair did not displace the image
+    keep = written.detach().clone()
+    try:
+        with torch.no_grad():
+            written.mul_(1.5)
+        pair2 = image(False)                                    # the other way round on the new entry: the pair first
+        assert pair2 is not pair and pair2[0] is not pair[0] and _is_rounding_of(pair2, weight())
+        b16 = image(True)
+        assert b16 is not a16 and _is_rounding_of(b16, weight())
+        assert image(False) is pair2 and image(True) is b16
+        if name == "bert_qkv":
+            att = TB._model("a", 1).encoder.layer[0].attention.self
+            assert torch.equal(ops._bert_qkv(TB._model("a", 1), att, False)[1], torch.cat([att.query.bias, att.key.bias, att.value.bias], 0))
+    finally:
+        with torch.no_grad():
+            written.copy_(keep)
+
+
 def test_timellm_end_to_end():
     """forecasting() + backward at the toy size of tests/test_gpu_gpt2.py, offline GPT-2, the model in eval mode (no dropout anywhere -- the
     reprogramming layer's and the body's draw a fresh key per call -- so that the two runs are the same function): split against fp32 products within the fp32 bars"""
