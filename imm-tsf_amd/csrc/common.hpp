@@ -34,6 +34,14 @@ __device__ __forceinline__ float mul_rounded(float a, float b) {
     return a * b;
 }
 
+// ---- parameters of a frozen model as the row kernels read them: fp32, or bf16 as a checkpoint stores them ("_p16" entry points), up-cast
+// in registers (exact), so that the arithmetic behind the load is one definition for both
+__device__ __forceinline__ float4 param4(const float* p, int e4) { return reinterpret_cast<const float4*>(p)[e4]; }
+__device__ __forceinline__ float4 param4(const bf16_t* p, int e4) {
+    const bf16x4 v = reinterpret_cast<const bf16x4*>(p)[e4];
+    return float4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+}
+
 // ---- wave / block reductions ----------------------------------------------------------------------
 // Cross-lane steps without the LDS crossbar: __shfl_xor compiles to ds_bpermute_b32 (an LDS-pipeline round trip per step and
 // an address register); inside a row of 16 lanes the DPP modifiers of the VALU add / max do the exchange for free, and

@@ -18,6 +18,10 @@
 // A stage holds A hi | A lo | B hi | B lo: (BM + BN) * 256 bytes, twice gemm2's for the same tile.
 // Out-of-range k chunks and T-image columns come from a 16-byte zero page (B) or are zero registers (A); out-of-range rows of an R
 // image are clamped to the last row (their products only reach output elements that are never stored).
+// immtsf_gemm_asplit: the same kernel for a weight that is STORED in bf16 (a Llama checkpoint read in place): B is the one image, bit for
+// bit the weight, so there is no Blo (template flag LO off), a stage holds A hi | A lo | B, (2 BM + BN) * 128 bytes, and a step is two MFMAs,
+//     acc += a_lo b;  acc += a_hi b
+// in that order -- fp32-grade in A, exact in B.  Same tiles, same selection, same support set.
 // Supported (immtsf_gemm_split_supported): layout 0 | 1, K and N multiples of 8, lda a multiple of 4, ldb a multiple of 8, pitches
 // at least as long as their rows; pointers: A, Bhi, Blo 16-byte aligned.  Anything else returns IMMTSF_EUNSUPPORTED before a launch.
 #include "../../include/immtsf.h"
@@ -41,7 +45,7 @@ struct SplitArgs {
 
 constexpr int SBK = 64;
 
-template <bool TB, int BM, int BN, int WM, int WN>
+template <bool TB, bool LO, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_split_kernel(const SplitArgs g) {
     constexpr int NT = WM * WN * 64;
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_split_kernel(const SplitArgs
     static_assert((BM / WM) % 16 == 0 && (BN / WN) % 16 == 0 && TM >= 1 && TN >= 1, "wave tile = whole 16x16 MFMA tiles");
     static_assert(BN % 64 == 0, "T images come in 64-column blocks");
     constexpr int A_IMG = BM * 128, B_IMG = BN * 128;                 // bytes of one image of one stage
-    constexpr int SB = 2 * A_IMG + 2 * B_IMG;
+    constexpr int SB = 2 * A_IMG + (LO ? 2 : 1) * B_IMG;           // LO: B comes as (hi, lo); else B is the weight itself, one image
 
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * SB];
 
@@ -101,7 +105,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_split_kernel(const SplitArgs
             const bool ok = k0 + kb[i] < K;
             const size_t o = ob[i] + (size_t)t * stepB;
             __builtin_amdgcn_global_load_lds((glb_vp)(ok ? g.Bhi + o : zp), (lds_vp)(sb + i * (NT * 16)), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((glb_vp)(ok ? g.Blo + o : zp), (lds_vp)(sb + B_IMG + i * (NT * 16)), 16, 0, 0);
+            if (LO) __builtin_amdgcn_global_load_lds((glb_vp)(ok ? g.Blo + o : zp), (lds_vp)(sb + B_IMG + i * (NT * 16)), 16, 0, 0);
         }
     };
     float4 ra[CA][2];
@@ -194,14 +198,14 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_split_kernel(const SplitArgs
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 bh[j] = TB ? frag_t(st + 2 * A_IMG, offB[j], kk) : frag_r(st + 2 * A_IMG, offB[j], kk);
-                bl[j] = TB ? frag_t(st + 2 * A_IMG + B_IMG, offB[j], kk) : frag_r(st + 2 * A_IMG + B_IMG, offB[j], kk);
+                if (LO) bl[j] = TB ? frag_t(st + 2 * A_IMG + B_IMG, offB[j], kk) : frag_r(st + 2 * A_IMG + B_IMG, offB[j], kk);
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                    if (LO) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
                 }
         }
@@ -244,13 +248,35 @@ __global__ void __launch_bounds__(256) split_bf16_kernel(const float* __restrict
     }
 }
 
-template <int BM, int BN, int WM, int WN>
+template <bool LO, int BM, int BN, int WM, int WN>
 int launch_split(int layout, const SplitArgs& g, hipStream_t stream) {
     const dim3 grid((unsigned)(cdiv(g.M, BM) * cdiv(g.N, BN))), block(WM * WN * 64);
-    if (layout == 0) hipLaunchKernelGGL((gemm_split_kernel<false, BM, BN, WM, WN>), grid, block, 0, stream, g);
-    else hipLaunchKernelGGL((gemm_split_kernel<true, BM, BN, WM, WN>), grid, block, 0, stream, g);
+    if (layout == 0) hipLaunchKernelGGL((gemm_split_kernel<false, LO, BM, BN, WM, WN>), grid, block, 0, stream, g);
+    else hipLaunchKernelGGL((gemm_split_kernel<true, LO, BM, BN, WM, WN>), grid, block, 0, stream, g);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
+}
+
+// few rows (the bodies' tail-row products): 16-row tiles, a wave per 16 columns; up to a CU's worth of 128 x 128 tiles: 64 x 64, two
+// workgroups per CU (three without Blo); beyond: 128 x 128 on eight waves, one workgroup per CU (128 KiB of LDS, 96 KiB without Blo)
+template <bool LO>
+int route_split(int layout, const SplitArgs& g, hipStream_t s) {
+    if (g.M <= 32) return launch_split<LO, 16, 64, 1, 4>(layout, g, s);
+    if ((long)cdiv(g.M, 128) * cdiv(g.N, 128) < 256) return launch_split<LO, 64, 64, 2, 2>(layout, g, s);
+    return launch_split<LO, 128, 128, 2, 4>(layout, g, s);
+}
+
+SplitArgs split_args(const float* A, int lda, const void* Bhi, const void* Blo, int ldb, float* C, int ldc, const float* bias, int M, int N,
+                     int K) {
+    SplitArgs g;
+    g.A = A;
+    g.Bhi = static_cast<const bf16_t*>(Bhi);
+    g.Blo = static_cast<const bf16_t*>(Blo);
+    g.C = C;
+    g.bias = bias;
+    g.M = M; g.N = N; g.K = K;
+    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+    return g;
 }
 
 }  // namespace
@@ -279,20 +305,18 @@ int immtsf_gemm_split(int32_t layout, const float* A, int32_t lda, const void* B
                       const float* bias, int32_t M, int32_t N, int32_t K, immtsf_stream_t stream) {
     if (!A || !Bhi || !Blo || !C || (layout != 0 && layout != 1) || M <= 0 || N <= 0 || K <= 0) return IMMTSF_EINVAL;
     if (!immtsf_gemm_split_supported(layout, M, N, K, lda, ldb, ldc) || !al16(A) || !al16(Bhi) || !al16(Blo)) return IMMTSF_EUNSUPPORTED;
-    SplitArgs g;
-    g.A = A;
-    g.Bhi = static_cast<const bf16_t*>(Bhi);
-    g.Blo = static_cast<const bf16_t*>(Blo);
-    g.C = C;
-    g.bias = bias;
-    g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // few rows (the bodies' tail-row products): 16-row tiles, a wave per 16 columns; up to a CU's worth of 128 x 128 tiles: 64 x 64,
-    // two workgroups per CU; beyond: 128 x 128 on eight waves, one workgroup per CU (128 KiB of LDS)
-    if (M <= 32) return launch_split<16, 64, 1, 4>(layout, g, s);
-    if ((long)cdiv(M, 128) * cdiv(N, 128) < 256) return launch_split<64, 64, 2, 2>(layout, g, s);
-    return launch_split<128, 128, 2, 4>(layout, g, s);
+    return route_split<true>(layout, split_args(A, lda, Bhi, Blo, ldb, C, ldc, bias, M, N, K), static_cast<hipStream_t>(stream));
+}
+
+int immtsf_gemm_asplit_supported(int32_t layout, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc) {
+    return immtsf_gemm_split_supported(layout, M, N, K, lda, ldb, ldc);
+}
+
+int immtsf_gemm_asplit(int32_t layout, const float* A, int32_t lda, const void* B16, int32_t ldb, float* C, int32_t ldc, const float* bias,
+                       int32_t M, int32_t N, int32_t K, immtsf_stream_t stream) {
+    if (!A || !B16 || !C || (layout != 0 && layout != 1) || M <= 0 || N <= 0 || K <= 0) return IMMTSF_EINVAL;
+    if (!immtsf_gemm_asplit_supported(layout, M, N, K, lda, ldb, ldc) || !al16(A) || !al16(B16)) return IMMTSF_EUNSUPPORTED;
+    return route_split<false>(layout, split_args(A, lda, B16, nullptr, ldb, C, ldc, bias, M, N, K), static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

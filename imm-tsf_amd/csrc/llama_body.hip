@@ -31,9 +31,10 @@ constexpr int QB = 16;        // queries per LDS tile of the dK / dV kernel
 
 // ---- RMSNorm of the rows (b, s_from + t), t < Sn, of xin (B, S_in, d); compact outputs; one wave per row ----------------------------------
 // y given: the row is xin + y[r] (y compact), written to xout[r] (compact; may be xin itself when the rows coincide).  Lane l writes, and
-// alone reads back, its own elements.
+// alone reads back, its own elements.  PT: the type of the weight w (float, or bf16_t for a model stored in bf16; up-cast in registers).
+template <typename PT>
 __global__ void __launch_bounds__(256) llama_body_rms_kernel(const float* xin, int S_in, int s_from, int Sn, const float* __restrict__ y,
-                                                             float* xout, long rows, int d, const float* __restrict__ w, float eps,
+                                                             float* xout, long rows, int d, const PT* __restrict__ w, float eps,
                                                              float* __restrict__ out32, bf16_t* __restrict__ out16,
                                                              float* __restrict__ rstd_out) {
     const int lane = threadIdx.x & 63;
@@ -62,9 +63,8 @@ __global__ void __launch_bounds__(256) llama_body_rms_kernel(const float* xin, i
     const float rstd = rsqrtf(wave_sum(ss) / (float)d + eps);
     if (rstd_out && lane == 0) rstd_out[r] = rstd;
     if (!out32 && !out16) return;
-    const float4* w4 = reinterpret_cast<const float4*>(w);
     for (int e = lane; e < d4; e += 64) {
-        const float4 v = src[e], g = w4[e];
+        const float4 v = src[e], g = param4(w, e);
         const float4 z = {v.x * rstd * g.x, v.y * rstd * g.y, v.z * rstd * g.z, v.w * rstd * g.w};
         if (out32) reinterpret_cast<float4*>(out32 + (size_t)r * d)[e] = z;
         if (out16) reinterpret_cast<bf16x4*>(out16 + (size_t)r * d)[e] = bf16x4{(bf16_t)z.x, (bf16_t)z.y, (bf16_t)z.z, (bf16_t)z.w};
@@ -72,8 +72,9 @@ __global__ void __launch_bounds__(256) llama_body_rms_kernel(const float* xin, i
 }
 
 // dx[r] = resid[r] + rstd (g - x rstd^2 mean(g x)), g = w dy; the weights are frozen: data gradient only.  Rows compact, one wave per row.
+template <typename PT>
 __global__ void __launch_bounds__(256) llama_body_rms_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                 const float* __restrict__ rstd, const float* __restrict__ w,
+                                                                 const float* __restrict__ rstd, const PT* __restrict__ w,
                                                                  const float* __restrict__ resid, long rows, int d, float* __restrict__ dx32,
                                                                  bf16_t* __restrict__ dx16) {
     const int lane = threadIdx.x & 63;
@@ -82,16 +83,15 @@ __global__ void __launch_bounds__(256) llama_body_rms_bwd_kernel(const float* __
     const float rs = rstd[r];
     const float4* xr = reinterpret_cast<const float4*>(x + (size_t)r * d);
     const float4* gr = reinterpret_cast<const float4*>(dy + (size_t)r * d);
-    const float4* w4 = reinterpret_cast<const float4*>(w);
     const int d4 = d >> 2;
     float s = 0.f;
     for (int e = lane; e < d4; e += 64) {
-        const float4 g = gr[e], ww = w4[e], xx = xr[e];
+        const float4 g = gr[e], ww = param4(w, e), xx = xr[e];
         s += g.x * ww.x * xx.x + g.y * ww.y * xx.y + g.z * ww.z * xx.z + g.w * ww.w * xx.w;
     }
     const float c = wave_sum(s) / (float)d * rs * rs;
     for (int e = lane; e < d4; e += 64) {
-        const float4 g = gr[e], ww = w4[e], xx = xr[e];
+        const float4 g = gr[e], ww = param4(w, e), xx = xr[e];
         float4 v = {rs * (g.x * ww.x - xx.x * c), rs * (g.y * ww.y - xx.y * c), rs * (g.z * ww.z - xx.z * c), rs * (g.w * ww.w - xx.w * c)};
         if (resid) {
             const float4 q = reinterpret_cast<const float4*>(resid + (size_t)r * d)[e];
@@ -386,6 +386,38 @@ void launch_fwd(dim3 grid, hipStream_t s, int32_t precision, const float* q, int
         hipLaunchKernelGGL((gqa128::attn_valu_kernel<G, DenseRows>), grid, dim3(64 * G), 0, s, rows, H, scale, out32, static_cast<bf16_t*>(out16));
 }
 
+// a parameter pointer is aligned for the four-element loads of its type
+inline bool param_al(const float* p) { return al16(p); }
+inline bool param_al(const bf16_t* p) { return al8(p); }
+
+template <typename PT>
+int launch_rms(const float* xin, int32_t B, int32_t S_in, int32_t s_from, int32_t d, const float* y, float* xout, const PT* w, float eps,
+               float* out32, void* out16, float* rstd, immtsf_stream_t stream) {
+    if (!xin || !w || B <= 0 || d <= 0 || s_from < 0 || s_from >= S_in || (!out32 && !out16 && !rstd) || (y && !xout)) return IMMTSF_EINVAL;
+    if ((d & 3) || !al16(xin) || !param_al(w) || (y && (!al16(y) || !al16(xout))) || (out32 && !al16(out32)) || (out16 && !al8(out16)))
+        return IMMTSF_EUNSUPPORTED;
+    const int Sn = S_in - s_from;
+    const long rows = (long)B * Sn;
+    if (rows > 0x7fffffffL) return IMMTSF_EUNSUPPORTED;
+    hipLaunchKernelGGL(llama_body_rms_kernel<PT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), xin, S_in,
+                       s_from, Sn, y, xout, rows, d, w, eps, out32, static_cast<bf16_t*>(out16), rstd);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
+template <typename PT>
+int launch_rms_bwd(const float* dy, const float* x, const float* rstd, const PT* w, const float* resid, int64_t rows, int32_t d, float* dx32,
+                   void* dx16, immtsf_stream_t stream) {
+    if (!dy || !x || !rstd || !w || (!dx32 && !dx16) || rows <= 0 || d <= 0) return IMMTSF_EINVAL;
+    if (rows > 0x7fffffffLL || (d & 3) || !al16(dy) || !al16(x) || !param_al(w) || (resid && !al16(resid)) || (dx32 && !al16(dx32)) ||
+        (dx16 && !al8(dx16)))
+        return IMMTSF_EUNSUPPORTED;
+    hipLaunchKernelGGL(llama_body_rms_bwd_kernel<PT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), dy, x, rstd,
+                       w, resid, (long)rows, d, dx32, static_cast<bf16_t*>(dx16));
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -397,28 +429,23 @@ int immtsf_llama_body_supported(int32_t d, int32_t H, int32_t H_kv, int32_t inne
 
 int immtsf_llama_body_rmsnorm(const float* xin, int32_t B, int32_t S_in, int32_t s_from, int32_t d, const float* y, float* xout, const float* w,
                               float eps, float* out32, void* out16, float* rstd, immtsf_stream_t stream) {
-    if (!xin || !w || B <= 0 || d <= 0 || s_from < 0 || s_from >= S_in || (!out32 && !out16 && !rstd) || (y && !xout)) return IMMTSF_EINVAL;
-    if ((d & 3) || !al16(xin) || !al16(w) || (y && (!al16(y) || !al16(xout))) || (out32 && !al16(out32)) || (out16 && !al8(out16)))
-        return IMMTSF_EUNSUPPORTED;
-    const int Sn = S_in - s_from;
-    const long rows = (long)B * Sn;
-    if (rows > 0x7fffffffL) return IMMTSF_EUNSUPPORTED;
-    hipLaunchKernelGGL(llama_body_rms_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), xin, S_in, s_from,
-                       Sn, y, xout, rows, d, w, eps, out32, static_cast<bf16_t*>(out16), rstd);
-    IMMTSF_LAUNCH_CHECK();
-    return IMMTSF_OK;
+    return launch_rms(xin, B, S_in, s_from, d, y, xout, w, eps, out32, out16, rstd, stream);
+}
+
+// the _p16 entry points: the same kernels with the RMSNorm weight read as bf16 (a model stored in bf16)
+int immtsf_llama_body_rmsnorm_p16(const float* xin, int32_t B, int32_t S_in, int32_t s_from, int32_t d, const float* y, float* xout,
+                                  const void* w16, float eps, float* out32, void* out16, float* rstd, immtsf_stream_t stream) {
+    return launch_rms(xin, B, S_in, s_from, d, y, xout, static_cast<const bf16_t*>(w16), eps, out32, out16, rstd, stream);
+}
+
+int immtsf_llama_body_rmsnorm_backward_p16(const float* dy, const float* x, const float* rstd, const void* w16, const float* resid,
+                                           int64_t rows, int32_t d, float* dx32, void* dx16, immtsf_stream_t stream) {
+    return launch_rms_bwd(dy, x, rstd, static_cast<const bf16_t*>(w16), resid, rows, d, dx32, dx16, stream);
 }
 
 int immtsf_llama_body_rmsnorm_backward(const float* dy, const float* x, const float* rstd, const float* w, const float* resid, int64_t rows,
                                        int32_t d, float* dx32, void* dx16, immtsf_stream_t stream) {
-    if (!dy || !x || !rstd || !w || (!dx32 && !dx16) || rows <= 0 || d <= 0) return IMMTSF_EINVAL;
-    if (rows > 0x7fffffffLL || (d & 3) || !al16(dy) || !al16(x) || !al16(w) || (resid && !al16(resid)) || (dx32 && !al16(dx32)) ||
-        (dx16 && !al8(dx16)))
-        return IMMTSF_EUNSUPPORTED;
-    hipLaunchKernelGGL(llama_body_rms_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), dy, x, rstd, w,
-                       resid, (long)rows, d, dx32, static_cast<bf16_t*>(dx16));
-    IMMTSF_LAUNCH_CHECK();
-    return IMMTSF_OK;
+    return launch_rms_bwd(dy, x, rstd, w, resid, rows, d, dx32, dx16, stream);
 }
 
 int immtsf_llama_body_rope(float* buf, int32_t ld, int64_t rows, int32_t rows_per_b, int32_t pos0, int32_t heads, int32_t max_len,

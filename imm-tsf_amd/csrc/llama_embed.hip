@@ -60,23 +60,26 @@ struct RaggedRows {
 };
 
 // ---- x[r, :] = embed[ids[r], :], one wave per row; an id outside the table is clamped into it (the host raises first) --------------------
-__global__ void __launch_bounds__(256) llama_tokens_kernel(const int32_t* __restrict__ ids, int rows, const float* __restrict__ embed, int vocab,
+// PT: the table's element type (float, or bf16_t for a model stored in bf16: the row is up-cast, exactly)
+template <typename PT>
+__global__ void __launch_bounds__(256) llama_tokens_kernel(const int32_t* __restrict__ ids, int rows, const PT* __restrict__ embed, int vocab,
                                                            int d, float* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
     int id = ids[r];
     id = id < 0 ? 0 : id >= vocab ? vocab - 1 : id;
-    const float4* a = reinterpret_cast<const float4*>(embed + (size_t)id * d);
+    const PT* a = embed + (size_t)id * d;
     float4* o = reinterpret_cast<float4*>(out + (size_t)r * d);
-    for (int e = lane; e < (d >> 2); e += 64) o[e] = a[e];
+    for (int e = lane; e < (d >> 2); e += 64) o[e] = param4(a, e);
 }
 
 // ---- RMSNorm rows, one wave per row -------------------------------------------------------------------------------------------------------
 // y given: x[r] <- x[r] + y[r] first (the residual add of the product before).  Then, each when its pointer is given: out32 / out16[r] =
 // x[r] rsqrt(mean(x[r]^2) + eps) w, and rstd[r] = that rsqrt alone (what the pool reads).  Lane l writes, and alone reads back, its own
-// elements of x.
-__global__ void __launch_bounds__(256) llama_rms_rows_kernel(float* x, const float* __restrict__ y, long rows, int d, const float* __restrict__ w,
+// elements of x.  PT: the type of the weight w (float | bf16_t).
+template <typename PT>
+__global__ void __launch_bounds__(256) llama_rms_rows_kernel(float* x, const float* __restrict__ y, long rows, int d, const PT* __restrict__ w,
                                                              float eps, float* __restrict__ out32, bf16_t* __restrict__ out16,
                                                              float* __restrict__ rstd_out) {
     const int lane = threadIdx.x & 63;
@@ -102,9 +105,8 @@ __global__ void __launch_bounds__(256) llama_rms_rows_kernel(float* x, const flo
     const float rstd = rsqrtf(wave_sum(ss) / (float)d + eps);
     if (rstd_out && lane == 0) rstd_out[r] = rstd;
     if (!out32 && !out16) return;
-    const float4* w4 = reinterpret_cast<const float4*>(w);
     for (int e = lane; e < d4; e += 64) {
-        const float4 v = xr[e], g = w4[e];
+        const float4 v = xr[e], g = param4(w, e);
         const float4 z = {v.x * rstd * g.x, v.y * rstd * g.y, v.z * rstd * g.z, v.w * rstd * g.w};
         if (out32) reinterpret_cast<float4*>(out32 + (size_t)r * d)[e] = z;
         if (out16) reinterpret_cast<bf16x4*>(out16 + (size_t)r * d)[e] = bf16x4{(bf16_t)z.x, (bf16_t)z.y, (bf16_t)z.z, (bf16_t)z.w};
@@ -165,8 +167,9 @@ __global__ void __launch_bounds__(256) llama_swiglu_kernel(const float* __restri
 // ---- pooled[n, e] = w[e] sum over the rows of note n, in position order, of x[row, e] rstd[row], / max(L, 1) -------------------------------
 // grid (note, 256-column slice): a thread owns one output column and walks the note's rows (coalesced across the workgroup); rstd comes
 // from llama_rms_rows_kernel.  A range that does not lie inside [0, rows) or is longer than MAXL counts as empty.
+template <typename PT>
 __global__ void __launch_bounds__(256) llama_pool_kernel(const float* __restrict__ x, const float* __restrict__ rstd,
-                                                         const int32_t* __restrict__ cu, int rows, int d, const float* __restrict__ w,
+                                                         const int32_t* __restrict__ cu, int rows, int d, const PT* __restrict__ w,
                                                          float* __restrict__ pooled) {
     const int n = blockIdx.x, e = blockIdx.y * 256 + threadIdx.x;
     if (e >= d) return;
@@ -174,7 +177,7 @@ __global__ void __launch_bounds__(256) llama_pool_kernel(const float* __restrict
     const float* xb = x + (size_t)nr.r0 * d + e;
     float acc = 0.f;
     for (int p = 0; p < nr.L; ++p) acc += xb[(size_t)p * d] * rstd[nr.r0 + p];
-    pooled[(size_t)n * d + e] = acc * w[e] / (float)(nr.L > 1 ? nr.L : 1);
+    pooled[(size_t)n * d + e] = acc * (float)w[e] / (float)(nr.L > 1 ? nr.L : 1);
 }
 
 inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -184,13 +187,18 @@ inline bool group_ok(int H, int Hkv) {
     return G == 1 || G == 2 || G == 4 || G == 8;
 }
 
-int launch_rms_rows(float* x, const float* y, int64_t rows, int32_t d, const float* w, float eps, float* out32, void* out16, float* rstd,
+// a parameter pointer is aligned for the four-element loads of its type
+inline bool param_al(const float* p) { return al16(p); }
+inline bool param_al(const bf16_t* p) { return al8(p); }
+
+template <typename PT>
+int launch_rms_rows(float* x, const float* y, int64_t rows, int32_t d, const PT* w, float eps, float* out32, void* out16, float* rstd,
                     immtsf_stream_t stream) {
     if (!x || !w || rows <= 0 || d <= 0 || (!out32 && !out16 && !rstd)) return IMMTSF_EINVAL;
-    if (rows > 0x7fffffffLL || (d & 3) || !al16(x) || !al16(w) || (y && !al16(y)) || (out32 && !al16(out32)) ||
+    if (rows > 0x7fffffffLL || (d & 3) || !al16(x) || !param_al(w) || (y && !al16(y)) || (out32 && !al16(out32)) ||
         (out16 && !al8(out16)))
         return IMMTSF_EUNSUPPORTED;
-    hipLaunchKernelGGL(llama_rms_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, (long)rows, d,
+    hipLaunchKernelGGL(llama_rms_rows_kernel<PT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, (long)rows, d,
                        w, eps, out32, static_cast<bf16_t*>(out16), rstd);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
@@ -204,6 +212,31 @@ void launch_attention(dim3 grid, hipStream_t s, int32_t precision, const float* 
         hipLaunchKernelGGL((gqa128::attn_mfma_kernel<G, RaggedRows>), grid, dim3(64 * G), 0, s, notes, H, scale, out32, static_cast<bf16_t*>(out16));
     else
         hipLaunchKernelGGL((gqa128::attn_valu_kernel<G, RaggedRows>), grid, dim3(64 * G), 0, s, notes, H, scale, out32, static_cast<bf16_t*>(out16));
+}
+
+template <typename PT>
+int launch_tokens(const int32_t* ids, int32_t rows, const PT* embed, int32_t vocab, int32_t d, float* out, immtsf_stream_t stream) {
+    if (!ids || !embed || !out || rows <= 0 || vocab <= 0 || d <= 0) return IMMTSF_EINVAL;
+    if ((d & 3) || !param_al(embed) || !al16(out)) return IMMTSF_EUNSUPPORTED;
+    hipLaunchKernelGGL(llama_tokens_kernel<PT>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), ids, rows, embed,
+                       vocab, d, out);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
+}
+
+template <typename PT>
+int launch_pool(float* x, const float* y, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const PT* w, float eps, float* rstd,
+                float* pooled, immtsf_stream_t stream) {
+    if (!cu || !w || !pooled || N <= 0 || rows < 0 || d <= 0 || (rows > 0 && (!x || !rstd))) return IMMTSF_EINVAL;
+    if ((d + 255) / 256 > 65535) return IMMTSF_EUNSUPPORTED;
+    if (rows > 0) {
+        const int rc = launch_rms_rows(x, y, rows, d, w, eps, nullptr, nullptr, rstd, stream);
+        if (rc != IMMTSF_OK) return rc;
+    }
+    hipLaunchKernelGGL(llama_pool_kernel<PT>, dim3((unsigned)N, (unsigned)((d + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                       rstd, cu, rows, d, w, pooled);
+    IMMTSF_LAUNCH_CHECK();
+    return IMMTSF_OK;
 }
 
 }  // namespace
@@ -226,12 +259,30 @@ size_t immtsf_llama_embed_workspace_bytes(int64_t rows, int32_t d, int32_t H, in
 }
 
 int immtsf_llama_embed_tokens(const int32_t* ids, int32_t rows, const float* embed, int32_t vocab, int32_t d, float* out, immtsf_stream_t stream) {
-    if (!ids || !embed || !out || rows <= 0 || vocab <= 0 || d <= 0) return IMMTSF_EINVAL;
-    if ((d & 3) || !al16(embed) || !al16(out)) return IMMTSF_EUNSUPPORTED;
-    hipLaunchKernelGGL(llama_tokens_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), ids, rows, embed,
-                       vocab, d, out);
-    IMMTSF_LAUNCH_CHECK();
-    return IMMTSF_OK;
+    return launch_tokens(ids, rows, embed, vocab, d, out, stream);
+}
+
+// the _p16 entry points: the same kernels with the model's parameter (the table, an RMSNorm weight) read as bf16
+int immtsf_llama_embed_tokens_p16(const int32_t* ids, int32_t rows, const void* embed16, int32_t vocab, int32_t d, float* out,
+                                  immtsf_stream_t stream) {
+    return launch_tokens(ids, rows, static_cast<const bf16_t*>(embed16), vocab, d, out, stream);
+}
+
+int immtsf_llama_embed_rmsnorm_p16(const float* x, int64_t rows, int32_t d, const void* w16, float eps, float* out32, void* out16,
+                                   immtsf_stream_t stream) {
+    if (!out32 && !out16) return IMMTSF_EINVAL;
+    return launch_rms_rows(const_cast<float*>(x), nullptr, rows, d, static_cast<const bf16_t*>(w16), eps, out32, out16, nullptr, stream);
+}
+
+int immtsf_llama_embed_add_rmsnorm_p16(float* x, const float* y, int64_t rows, int32_t d, const void* w16, float eps, float* out32, void* out16,
+                                       immtsf_stream_t stream) {
+    if (!y || (!out32 && !out16)) return IMMTSF_EINVAL;
+    return launch_rms_rows(x, y, rows, d, static_cast<const bf16_t*>(w16), eps, out32, out16, nullptr, stream);
+}
+
+int immtsf_llama_embed_pool_p16(float* x, const float* y, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const void* w16, float eps,
+                                float* rstd, float* pooled, immtsf_stream_t stream) {
+    return launch_pool(x, y, cu, N, rows, d, static_cast<const bf16_t*>(w16), eps, rstd, pooled, stream);
 }
 
 int immtsf_llama_embed_rmsnorm(const float* x, int64_t rows, int32_t d, const float* w, float eps, float* out32, void* out16,
@@ -297,16 +348,7 @@ int immtsf_llama_embed_swiglu(const float* gu, int64_t rows, int32_t inner, floa
 
 int immtsf_llama_embed_pool(float* x, const float* y, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const float* w, float eps,
                             float* rstd, float* pooled, immtsf_stream_t stream) {
-    if (!cu || !w || !pooled || N <= 0 || rows < 0 || d <= 0 || (rows > 0 && (!x || !rstd))) return IMMTSF_EINVAL;
-    if ((d + 255) / 256 > 65535) return IMMTSF_EUNSUPPORTED;
-    if (rows > 0) {
-        const int rc = launch_rms_rows(x, y, rows, d, w, eps, nullptr, nullptr, rstd, stream);
-        if (rc != IMMTSF_OK) return rc;
-    }
-    hipLaunchKernelGGL(llama_pool_kernel, dim3((unsigned)N, (unsigned)((d + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), x, rstd,
-                       cu, rows, d, w, pooled);
-    IMMTSF_LAUNCH_CHECK();
-    return IMMTSF_OK;
+    return launch_pool(x, y, cu, N, rows, d, w, eps, rstd, pooled, stream);
 }
 
 }  // extern "C"

@@ -10,9 +10,12 @@ LlamaModel (Llama-3.1, deepseek-llm) on the GPU behind a right-padding tokenizer
 rotary positions are arange(seq) whatever the mask is; immtsf.ops.bert_embed_notes: a padded key has an exact zero weight in a real
 query's softmax; the average never reads a pad row), so only the real ids are uploaded.  The padded-out notes of a window are the empty
 string: where that has no tokens (GPT-2) their rows are zeros without being run, where it has some (BERT's [CLS] [SEP], Llama's BOS) the
-one note is run once in the same call and copied to every such row.  Every other case -- another model class, a Llama outside
-llama_embed_notes_supported (parameters stored in bf16, dynamic / yarn / longrope RoPE), a left-padding tokenizer, the CPU,
-immtsf.config.note_embed_fused off, a model left in training mode with dropout -- runs the padded formulation on torch ops.
+one note is run once in the same call and copied to every such row.  A Llama whose parameters are all stored in bf16 (what load_llm
+returns for the Llama / DeepSeek aliases: their checkpoints are bf16 and from_pretrained keeps the stored dtype) takes the same path with
+immtsf.config.llama_stored_bf16 on, its weights read in place, and the pooled rows come back in bf16 as the padded call returns them.
+Every other case -- another model class, a Llama outside llama_embed_notes_supported (parameters stored in bf16 with that knob off, fp16
+or mixed dtypes, dynamic / yarn / longrope RoPE), a left-padding tokenizer, the CPU, immtsf.config.note_embed_fused off, a model left in
+training mode with dropout -- runs the padded formulation on torch ops.
 path_calls counts which way each call went.
 """
 import torch
@@ -146,7 +149,9 @@ def _pool_rows(llm_model, ids, attn, rows, device):
         cu = torch.zeros(rows.numel() + 1, dtype=torch.int32)
         cu[1:] = torch.cumsum(counts, 0)
         path_calls["fused"] += 1
-        return _family(llm_model)[0](llm_model, real.to(torch.int32).to(device), cu.to(device), max_len=max(int(counts.max()), 1))
+        emb = _family(llm_model)[0](llm_model, real.to(torch.int32).to(device), cu.to(device), max_len=max(int(counts.max()), 1))
+        stored = next(llm_model.parameters()).dtype       # (the padded call returns the model's dtype: so does this one)
+        return emb if stored == torch.float32 else emb.to(stored)
     path_calls["stock"] += 1
     return _pool_padded(llm_model, ids.to(device), attn.to(device))
 
@@ -175,8 +180,8 @@ def embed_notes(notes_text: list[list[str]], tokenizer, llm_model, max_length: i
     run = torch.cat([real, one_fill])
     counts, is_prefix = _token_counts(attn[run])
     if is_prefix and run.numel() and _fused_ok(llm_model, device, int(ids.shape[1]), int(run.numel())):
-        out = torch.zeros(B * N_max, _hidden_size(llm_model), device=device)
         emb = _pool_rows(llm_model, ids, attn, run, device)
+        out = torch.zeros(B * N_max, _hidden_size(llm_model), device=device, dtype=emb.dtype)
         out[real.to(device)] = emb[:real.numel()]
         if one_fill.numel():
             out[fill.to(device)] = emb[-1]

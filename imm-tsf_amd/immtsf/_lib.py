@@ -195,7 +195,19 @@ _PROTOS = {
     "immtsf_gemm_split_supported": (C.c_int, [C.c_int32] * 7),
     "immtsf_gemm_split": (C.c_int, [C.c_int32, c_f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32,
                                     C.c_int32, C.c_int32, c_stream]),
-    "immtsf_gpt2_embed": (C.c_int, [c_f32p, c_f32p, c_f32p] + [C.c_int32] * 4 + [C.c_float, C.c_uint64, C.c_uint64, c_f32p, c_stream]),
+    "immtsf_gemm_asplit_supported": (C.c_int, [C.c_int32] * 7),
+    "immtsf_gemm_asplit": (C.c_int, [C.c_int32, c_f32p, C.c_int32, C.c_void_p, C.c_int32, c_f32p, C.c_int32, c_f32p, C.c_int32, C.c_int32,
+                                     C.c_int32, c_stream]),
+    "immtsf_llama_embed_tokens_p16": (C.c_int, [c_i32p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, c_f32p, c_stream]),
+    "immtsf_llama_embed_rmsnorm_p16": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_float, c_f32p, C.c_void_p, c_stream]),
+    "immtsf_llama_embed_add_rmsnorm_p16": (C.c_int, [c_f32p, c_f32p, C.c_int64, C.c_int32, C.c_void_p, C.c_float, c_f32p, C.c_void_p,
+                                                     c_stream]),
+    "immtsf_llama_embed_pool_p16": (C.c_int, [c_f32p, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, c_f32p, c_f32p,
+                                              c_stream]),
+    "immtsf_llama_body_rmsnorm_p16": (C.c_int, [c_f32p] + [C.c_int32] * 4 + [c_f32p, c_f32p, C.c_void_p, C.c_float, c_f32p, C.c_void_p, c_f32p,
+                                                c_stream]),
+    "immtsf_llama_body_rmsnorm_backward_p16": (C.c_int, [c_f32p] * 3 + [C.c_void_p, c_f32p, C.c_int64, C.c_int32, c_f32p, C.c_void_p, c_stream]),
+    "immtsf_gpt2_embed": (C.c_int, [c_f32p, c_f32p, c_f32p]+ [C.c_int32] * 4 + [C.c_float, C.c_uint64, C.c_uint64, c_f32p, c_stream]),
     "immtsf_gpt2_layernorm": (C.c_int, [c_f32p] + [C.c_int32] * 4 + [c_f32p, c_f32p, C.c_float, c_f32p, C.c_void_p, c_f32p, c_f32p, c_stream]),
     "immtsf_gpt2_layernorm_backward": (C.c_int, [c_f32p] * 6 + [C.c_int64, C.c_int32, c_f32p, c_stream]),
     "immtsf_gpt2_residual": (C.c_int, [c_f32p] + [C.c_int32] * 7 + [c_f32p, C.c_float, C.c_uint64, C.c_uint64, c_f32p, c_stream]),

@@ -194,6 +194,13 @@ bert_embed_fp32_min_notes = int(os.environ.get("IMMTSF_BERT_EMBED_FP32_MIN_NOTES
 # Measured at Llama-3.1-8B's widths a single note per call is 3.0x the padded call in fp32 and 32 notes 2.0x (bf16: 8.5x /
 # 20x), so nothing is gated off: the threshold is 1
 llama_embed_fp32_min_notes = int(os.environ.get("IMMTSF_LLAMA_EMBED_FP32_MIN_NOTES", "1"))
+# A frozen LlamaModel STORED in bf16 (every parameter torch.bfloat16: what from_pretrained returns for Llama-3.1 / deepseek-llm under
+# dtype="auto") on the same two operators, read in place: in bf16 mode the GEMM family takes the parameter's own storage as the
+# bf16 image, in fp32 mode every product is immtsf_gemm_asplit (fp32 activations cut in registers against the stored weight, whatever
+# frozen_products says), the row kernels read bf16 parameters (the _p16 entry points), and q | k | v and gate | up are products side by
+# side instead of one product on a concatenated copy -- no second image of any weight.  OFF unless IMMTSF_LLAMA_STORED_BF16=1:
+# tests/test_gpu_llama_embed.py and test_gpu_llama_body.py pin that a bf16 model with nothing set is refused (the padded stock call)
+llama_stored_bf16 = os.environ.get("IMMTSF_LLAMA_STORED_BF16", "0") == "1"
 # LatentODE's forecasting() as one HIP launch forward and two backward (csrc/latent_ode.hip) wherever the encoder is the ODE-RNN with
 # rec_layers = gen_layers = 1, one trajectory sample, and immtsf_latent_ode_supported allows; IMMTSF_LATENTODE_FUSED=0: the composed path
 # (the reference's loop over the observed points on torch ops, the step plan copied to the host once) -- the cross-check.  fp32 in

@@ -3310,6 +3310,7 @@ def gpt2_body_supported(llm_model, S_p, S_t):
 
 
 split_product_calls = 0          # products of the frozen bodies / note-embedding operators that ran on immtsf_gemm_split
+asplit_product_calls = 0         # ... and, for a Llama stored in bf16 in fp32 mode, on immtsf_gemm_asplit
 
 
 def _split_images(W):
@@ -3373,6 +3374,9 @@ def _w_img(model, W, bf, sp):
     return _gpt2_w(model, W).image(bf, sp) if (bf or sp) else None
 
 
+_IN_PLACE = "in place"           # the `img` of a weight that is stored in bf16: the parameter is the image (a stored-bf16 Llama)
+
+
 def _adr(t, off=0):
     """device pointer of element `off` of a tensor (or None)"""
     return None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())
@@ -3413,8 +3417,18 @@ def _frozen_gemm(lib, layout, precision, pa32, pa16, lda, W, img, w_off, ldb, ou
     """out[.. c_off ..] (M, N; pitch ldc) = a (M, K; pitch lda) op(W[.. w_off ..]) + bias: one product of a frozen body.  pa32 / pa16
     and bias: pointers as the caller made them (bias already at its offset, or None); W the fp32 weight and `img` what _w_img gave for
     it, both read from element offset w_off at pitch ldb; out written from element offset c_off.  An (hi, lo) pair goes to
-    immtsf_gemm_split when that supports the shape; anything else is immtsf_gpt2_gemm's call as it always was."""
-    global split_product_calls
+    immtsf_gemm_split when that supports the shape; anything else is immtsf_gpt2_gemm's call as it always was.  img _IN_PLACE: W is
+    stored in bf16 and there is no fp32 weight -- bf16 mode hands its storage to immtsf_gpt2_gemm as the image (no route of that call
+    reads a null fp32 operand: a shape the bf16-in-memory kernels refuse comes back as an error), fp32 mode is immtsf_gemm_asplit."""
+    global split_product_calls, asplit_product_calls
+    if img is _IN_PLACE:
+        if precision == 1:
+            check(lib.immtsf_gpt2_gemm(layout, 1, None, pa16, lda, None, _adr(W, w_off), ldb, _adr(out, c_off), ldc, bias, M, N, K, st),
+                  what + " (stored bf16)")
+        else:
+            check(lib.immtsf_gemm_asplit(layout, pa32, lda, _adr(W, w_off), ldb, _adr(out, c_off), ldc, bias, M, N, K, st), what + " (asplit)")
+            asplit_product_calls += 1
+        return
     if isinstance(img, tuple):
         if lib.immtsf_gemm_split_supported(layout, M, N, K, lda, ldb, ldc):
             check(lib.immtsf_gemm_split(layout, pa32, lda, _adr(img[0], w_off), _adr(img[1], w_off), ldb, _adr(out, c_off), ldc, bias, M, N, K, st),
@@ -3429,19 +3443,21 @@ def _frozen_gemm(lib, layout, precision, pa32, pa16, lda, W, img, w_off, ldb, ou
 class _FrozenProducts:
     """the weight products of one pass over a frozen model in one precision mode: bf (bf16 mode), sp (fp32 mode under
     config.frozen_products == "split") and _frozen_gemm's calls for nn.Linear weights (N, K) and GPT-2's Conv1D weights (in, out), each
-    read as it is stored"""
+    read as it is stored.  stored: the model is a Llama stored in bf16 (_llama_model_kind) -- every weight is its own image, nothing is
+    cached, and fp32 mode runs immtsf_gemm_asplit whatever config.frozen_products says"""
 
     def __init__(self, lib, model, precision, st):
         self.lib, self.model, self.precision, self.st = lib, model, precision, st
         self.bf = precision == 1
-        self.sp = config.frozen_split(precision)
+        self.stored = config.llama_stored_bf16 and _llama_model_kind(model) == "bf16"
+        self.sp = config.frozen_split(precision) and not self.stored
 
     def pair(self, t32, t16):
         """(fp32 pointer, bf16 pointer) of an operand or a result kept in the mode's format: the other one is None"""
         return (None, ptr(t16)) if self.bf else (ptr(t32), None)
 
     def img(self, W):
-        return _w_img(self.model, W, self.bf, self.sp)
+        return _IN_PLACE if self.stored else _w_img(self.model, W, self.bf, self.sp)
 
     def mm(self, a32, a16, W, img, bias, rows, out, ldc, w_row=0, n_out=None, c_off=0):
         """out[:, c_off:c_off + n_out] = a (rows, K) W[w_row:w_row + n_out]^T + bias[w_row:..] (layout 0); img: W's image as _w_img gives it"""
@@ -3454,12 +3470,14 @@ class _FrozenProducts:
         """out (rows, N) = a dense.weight^T + dense.bias"""
         self.mm(a32, a16, dense.weight, self.img(dense.weight), dense.bias, rows, out, dense.weight.shape[0])
 
-    def mm_t(self, g32, g16, W, img, rows):
-        """g (rows, N) W -> (rows, K) fp32: the backward of mm (layout 1)"""
+    def mm_t(self, g32, g16, W, img, rows, g_off=0, ldg=None):
+        """g (rows, N) W -> (rows, K) fp32: the backward of mm (layout 1); g_off, ldg: g is the columns g_off .. g_off + N - 1 of a buffer
+        of pitch ldg"""
         N, K = W.shape
         o = torch.empty(rows, K, dtype=torch.float32, device=W.device)
-        p32, p16 = self.pair(g32, g16)
-        _frozen_gemm(self.lib, 1, self.precision, p32, p16, N, W, img, 0, K, o, 0, K, None, rows, K, N, self.st, "gpt2_gemm (backward)")
+        p32, p16 = (None, _adr(g16, g_off)) if self.bf else (_adr(g32, g_off), None)
+        _frozen_gemm(self.lib, 1, self.precision, p32, p16, N if ldg is None else ldg, W, img, 0, K, o, 0, K, None, rows, K, N, self.st,
+                     "gpt2_gemm (backward)")
         return o
 
     def lin_t(self, g32, g16, dense, rows):
@@ -3828,23 +3846,45 @@ def _llama_dims(cfg):
     return d, H, int(getattr(cfg, "num_key_value_heads", None) or H), int(getattr(cfg, "head_dim", None) or d // H), int(cfg.intermediate_size)
 
 
-def llama_embed_notes_supported(llm_model, max_len):
-    """the limits of llama_embed_notes: a transformers LlamaModel (the class itself) with head_dim 128, H query heads over H_kv K/V heads
-    with H / H_kv in {1, 2, 4, 8}, hidden_act "silu", neither attention nor MLP bias, rope_type default / linear / llama3 (those whose
-    inv_freq does not depend on the call: dynamic, yarn and longrope keep the stock path), at least one layer, fp32 parameters,
-    hidden_size and intermediate_size multiples of 8, and 1 <= max_len <= max_position_embeddings, <= 1024"""
+def _llama_model_kind(llm_model):
+    """what llama_embed_notes_supported and llama_body_supported ask of the model alone, short of the library's answer on its widths and
+    lengths: None outside the limits; "fp32" when every parameter is fp32; "bf16" when config.llama_stored_bf16 is on and every
+    parameter is bf16 (a checkpoint stored in bf16, read in place: DESIGN 4v).  Mixed dtypes, fp16 and anything else: None"""
     from transformers import LlamaModel
-    if type(llm_model) is not LlamaModel or max_len < 1:
-        return False
+    if type(llm_model) is not LlamaModel:
+        return None
     cfg = llm_model.config
-    d, H, H_kv, hd, inner = _llama_dims(cfg)
+    _, _, _, hd, _ = _llama_dims(cfg)
     rope = getattr(llm_model, "rotary_emb", None)
     if (hd != 128 or cfg.hidden_act != "silu" or getattr(cfg, "attention_bias", False) or getattr(cfg, "mlp_bias", False) or
             len(llm_model.layers) < 1 or getattr(rope, "rope_type", None) not in _LLAMA_ROPE_TYPES or
             tuple(getattr(rope, "inv_freq", torch.zeros(0)).shape) != (64,)):
+        return None
+    dtypes = {p.dtype for p in llm_model.parameters()}
+    if dtypes == {torch.float32}:
+        return "fp32"
+    if dtypes == {torch.bfloat16} and config.llama_stored_bf16:
+        return "bf16"
+    return None
+
+
+def llama_embed_notes_supported(llm_model, max_len):
+    """the limits of llama_embed_notes: a transformers LlamaModel (the class itself) with head_dim 128, H query heads over H_kv K/V heads
+    with H / H_kv in {1, 2, 4, 8}, hidden_act "silu", neither attention nor MLP bias, rope_type default / linear / llama3 (those whose
+    inv_freq does not depend on the call: dynamic, yarn and longrope keep the stock path), at least one layer, fp32 parameters -- or,
+    with config.llama_stored_bf16 on, every parameter bf16 on one CUDA device --, hidden_size and intermediate_size multiples of 8, and
+    1 <= max_len <= max_position_embeddings, <= 1024"""
+    if max_len < 1:
         return False
-    if any(p.dtype != torch.float32 for p in llm_model.parameters()):
+    kind = _llama_model_kind(llm_model)
+    if kind is None:
         return False
+    if kind == "bf16":
+        devices = {p.device for p in llm_model.parameters()}
+        if len(devices) != 1 or next(iter(devices)).type != "cuda":
+            return False
+    cfg = llm_model.config
+    d, H, H_kv, hd, inner = _llama_dims(cfg)
     return bool(_lib.load().immtsf_llama_embed_supported(d, H, H_kv, inner, int(max_len), int(cfg.max_position_embeddings)))
 
 
@@ -3857,12 +3897,53 @@ def _llama_cat(model, owner, slot, linears, bf, sp=False):
     return hit.w, hit.image(bf, sp)
 
 
-def _llama_qkv(model, att, P):
-    return _llama_cat(model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj), P.bf, P.sp)
+class _LlamaCat:
+    """the weights of `linears` (q | k | v of an attention, gate | up of an MLP) as ONE weight along the output axis.  An fp32 model: the
+    cached concatenation of _llama_cat, one product per call.  A model stored in bf16 (P.stored): nothing is concatenated or cached --
+    mm is one product per member into the shared buffer at the member's column offset, and mm_t one layout-1 product per member over
+    its columns of g, summed in a fixed order, the members' order (q, then k, then v; gate, then up): (g_q W_q + g_k W_k) + g_v W_v."""
+
+    def __init__(self, P, model, owner, slot, linears):
+        self.P, self.linears = P, linears
+        self.cat = None if P.stored else _llama_cat(model, owner, slot, linears, P.bf, P.sp)
+        self.widths = [int(lin.weight.shape[0]) for lin in linears]
+
+    def mm(self, a32, a16, rows, out, ldc, first=0, count=None):
+        """out[:, :n] = a (rows, K) [W_first | .. | W_(first + count - 1)]^T, n the members' widths together"""
+        last = len(self.linears) if count is None else first + count
+        if self.cat is not None:
+            self.P.mm(a32, a16, *self.cat, None, rows, out, ldc, w_row=sum(self.widths[:first]), n_out=sum(self.widths[first:last]))
+            return
+        c = 0
+        for lin, n in zip(self.linears[first:last], self.widths[first:last]):
+            self.P.mm(a32, a16, lin.weight, _IN_PLACE, None, rows, out, ldc, c_off=c)
+            c += n
+
+    def mm_t(self, g32, g16, rows):
+        """g (rows, sum of the widths) [W_0 ; W_1 ; ..] -> (rows, K) fp32"""
+        if self.cat is not None:
+            return self.P.mm_t(g32, g16, *self.cat, rows)
+        o, off, ldg = None, 0, sum(self.widths)
+        for lin, n in zip(self.linears, self.widths):
+            part = self.P.mm_t(g32, g16, lin.weight, _IN_PLACE, rows, g_off=off, ldg=ldg)
+            o = part if o is None else o.add_(part)
+            off += n
+        return o
 
 
-def _llama_gu(model, mlp, P):
-    return _llama_cat(model, mlp, "gu", (mlp.gate_proj, mlp.up_proj), P.bf, P.sp)
+def _llama_qkv_cat(model, att, P):
+    return _LlamaCat(P, model, att, "qkv", (att.q_proj, att.k_proj, att.v_proj))
+
+
+def _llama_gu_cat(model, mlp, P):
+    return _LlamaCat(P, model, mlp, "gu", (mlp.gate_proj, mlp.up_proj))
+
+
+def _llama_rows(lib, P):
+    """the row kernels that read a parameter, by the model's storage: name -> the entry point (the _p16 one for a stored-bf16 model)"""
+    sfx = "_p16" if P.stored else ""
+    return {n: getattr(lib, f"immtsf_llama_{n}{sfx}") for n in ("embed_tokens", "embed_rmsnorm", "embed_add_rmsnorm", "embed_pool",
+                                                                "body_rmsnorm", "body_rmsnorm_backward")}
 
 
 def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
@@ -3872,8 +3953,9 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
     are 0 .. L - 1 inside each note, the cos / sin table is built per call from the model's own rotary_emb.inv_freq and
     attention_scaling.  A note of no tokens gives an exact zero row.  max_len: an upper bound of the token counts (read from cu when not
     given: one device -> host copy).  The model's parameters are read in place, but for the cached q | k | v and gate | up concatenations
-    and, in bf16 mode, the cached bf16 weight images; runs under no_grad and saves nothing.  Outside llama_embed_notes_supported this
-    raises: callers check."""
+    and, in bf16 mode, the cached bf16 weight images; runs under no_grad and saves nothing.  A model stored in bf16
+    (config.llama_stored_bf16) is read in place altogether: no concatenation, no image, nothing cached (_LlamaCat, _frozen_gemm); the
+    result is fp32 all the same.  Outside llama_embed_notes_supported this raises: callers check."""
     def widest(cfg):
         d, H, H_kv, hd, inner = _llama_dims(cfg)
         return max(d, (H + 2 * H_kv) * hd, 2 * inner)
@@ -3904,27 +3986,26 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
         check(lib.immtsf_llama_embed_rope_table(ptr(inv_freq), float(rope.attention_scaling), max_len, ptr(cos_t), ptr(sin_t), st),
               "llama_embed_rope_table")
         emb = llm_model.embed_tokens.weight
-        check(lib.immtsf_llama_embed_tokens(ptr(ids), T, ptr(emb), int(emb.shape[0]), d, ptr(x), st), "llama_embed_tokens")
+        rows = _llama_rows(lib, P)
+        check(rows["embed_tokens"](ptr(ids), T, ptr(emb), int(emb.shape[0]), d, ptr(x), st), "llama_embed_tokens")
         for i, layer in enumerate(llm_model.layers):
             att, mlp = layer.self_attn, layer.mlp
             w_in = layer.input_layernorm.weight
             if i == 0:
-                check(lib.immtsf_llama_embed_rmsnorm(ptr(x), T, d, ptr(w_in), eps, *P.pair(h, h), st), "llama_embed_rmsnorm")
+                check(rows["embed_rmsnorm"](ptr(x), T, d, ptr(w_in), eps, *P.pair(h, h), st), "llama_embed_rmsnorm")
             else:      # the residual add of the layer before rides on this norm
-                check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(w_in), eps, *P.pair(h, h), st), "llama_embed_add_rmsnorm")
-            W, W16 = _llama_qkv(llm_model, att, P)
-            P.mm(h, h, W, W16, None, T, qkv, dqkv)
+                check(rows["embed_add_rmsnorm"](ptr(x), ptr(pr), T, d, ptr(w_in), eps, *P.pair(h, h), st), "llama_embed_add_rmsnorm")
+            _llama_qkv_cat(llm_model, att, P).mm(h, h, T, qkv, dqkv)
             check(lib.immtsf_llama_embed_rope(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, ptr(cos_t), ptr(sin_t), st), "llama_embed_rope")
             check(lib.immtsf_llama_embed_attention(ptr(qkv), dqkv, ptr(cu), N, T, H, H_kv, max_len, scale, precision, *P.pair(ao, ao), st),
                   "llama_embed_attention")
             P.lin(ao, ao, att.o_proj, T, pr)
-            check(lib.immtsf_llama_embed_add_rmsnorm(ptr(x), ptr(pr), T, d, ptr(layer.post_attention_layernorm.weight), eps, *P.pair(h, h), st),
+            check(rows["embed_add_rmsnorm"](ptr(x), ptr(pr), T, d, ptr(layer.post_attention_layernorm.weight), eps, *P.pair(h, h), st),
                   "llama_embed_add_rmsnorm")
-            W, W16 = _llama_gu(llm_model, mlp, P)
-            P.mm(h, h, W, W16, None, T, gu, 2 * inner)
+            _llama_gu_cat(llm_model, mlp, P).mm(h, h, T, gu, 2 * inner)
             check(lib.immtsf_llama_embed_swiglu(ptr(gu), T, inner, *P.pair(act, act), st), "llama_embed_swiglu")
             P.lin(act, act, mlp.down_proj, T, pr)
-        check(lib.immtsf_llama_embed_pool(ptr(x), ptr(pr), ptr(cu), N, T, d, ptr(llm_model.norm.weight), eps, ptr(rstd), ptr(pooled), st),
+        check(rows["embed_pool"](ptr(x), ptr(pr), ptr(cu), N, T, d, ptr(llm_model.norm.weight), eps, ptr(rstd), ptr(pooled), st),
               "llama_embed_pool")
         return pooled
 
@@ -3932,8 +4013,9 @@ def llama_embed_notes(llm_model, ids, cu, precision=None, max_len=None):
 # ------------------------------------------------------------------------------------------------ TimeLLM: the frozen Llama body
 def llama_body_supported(llm_model, S_p, S_t):
     """the limits of llama_body: llama_embed_notes_supported's conditions on the model (the LlamaModel class itself, head_dim 128,
-    H / H_kv in {1, 2, 4, 8}, silu, no attention or MLP bias, rope_type default / linear / llama3, fp32 parameters, widths multiples of
-    8), S_p >= 0, S_t >= 1 and S = S_p + S_t <= max_position_embeddings, <= 1024"""
+    H / H_kv in {1, 2, 4, 8}, silu, no attention or MLP bias, rope_type default / linear / llama3, fp32 parameters or -- with
+    config.llama_stored_bf16 on -- all bf16 on one CUDA device, widths multiples of 8), S_p >= 0, S_t >= 1 and
+    S = S_p + S_t <= max_position_embeddings, <= 1024"""
     if S_p < 0 or S_t < 1 or not llama_embed_notes_supported(llm_model, 1):
         return False
     cfg = llm_model.config
@@ -3962,6 +4044,7 @@ class LlamaBodyFn(torch.autograd.Function):
         dqkv = dq + 2 * dkv
         dev = tail.device
         P = _FrozenProducts(lib, model, precision, st)
+        rows_k = _llama_rows(lib, P)
         bf = P.bf
         eps = float(cfg.rms_norm_eps)
         scale = 1.0 / float(hd) ** 0.5
@@ -3973,7 +4056,7 @@ class LlamaBodyFn(torch.autograd.Function):
             xo = f32(n, d) if y is not None else None
             h = b16(n, d) if bf else f32(n, d)
             rstd = f32(n) if stats else None
-            check(lib.immtsf_llama_body_rmsnorm(ptr(xin), B, S_in, s_from, d, ptr(y), ptr(xo), ptr(w), eps, *P.pair(h, h), ptr(rstd), st),
+            check(rows_k["body_rmsnorm"](ptr(xin), B, S_in, s_from, d, ptr(y), ptr(xo), ptr(w), eps, *P.pair(h, h), ptr(rstd), st),
                   "llama_body_rmsnorm")
             return (xin if xo is None else xo), h, rstd
 
@@ -3996,19 +4079,19 @@ class LlamaBodyFn(torch.autograd.Function):
             qf = S_p if li == L - 1 else 0
             Sq = S - qf
             x, h, rstd1 = rms(x, Sx, 0, y, layer.input_layernorm.weight, need_bwd)
-            W, W16 = _llama_qkv(model, att, P)
+            Wqkv = _llama_qkv_cat(model, att, P)
             if qf == 0:
                 qkv = f32(B * S, dqkv)
-                P.mm(h, h, W, W16, None, B * S, qkv, dqkv)
+                Wqkv.mm(h, h, B * S, qkv, dqkv)
                 rope(qkv, 0, dqkv, B * S, S, 0, H + H_kv)
                 q, ldq, kv, ldkv, k_off = qkv, dqkv, qkv, dqkv, dq
             else:           # the last layer: K and V of all rows, queries of the tail rows
                 kv = f32(B * S, 2 * dkv)
-                P.mm(h, h, W, W16, None, B * S, kv, 2 * dkv, w_row=dq, n_out=2 * dkv)
+                Wqkv.mm(h, h, B * S, kv, 2 * dkv, first=1)
                 rope(kv, 0, 2 * dkv, B * S, S, 0, H_kv)
                 _, ht, _ = rms(x, S, qf, None, layer.input_layernorm.weight, False)
                 q = f32(B * Sq, dq)
-                P.mm(ht, ht, W, W16, None, B * Sq, q, dq, n_out=dq)
+                Wqkv.mm(ht, ht, B * Sq, q, dq, count=1)
                 rope(q, 0, dq, B * Sq, Sq, qf, H)
                 ldq, ldkv, k_off = dq, 2 * dkv, 0
             ao32 = f32(B * Sq, dq) if (need_bwd or not bf) else None
@@ -4020,7 +4103,7 @@ class LlamaBodyFn(torch.autograd.Function):
             P.lin(ao32, ao16, att.o_proj, B * Sq, pr)
             x1, g, rstd2 = rms(x, S, qf, pr, layer.post_attention_layernorm.weight, need_bwd)
             gu = f32(B * Sq, 2 * inner)
-            P.mm(g, g, *_llama_gu(model, mlp, P), None, B * Sq, gu, 2 * inner)
+            _llama_gu_cat(model, mlp, P).mm(g, g, B * Sq, gu, 2 * inner)
             act = b16(B * Sq, inner) if bf else f32(B * Sq, inner)
             check(lib.immtsf_llama_embed_swiglu(ptr(gu), B * Sq, inner, *P.pair(act, act), st), "llama_embed_swiglu")
             mo = f32(B * Sq, d)
@@ -4038,8 +4121,8 @@ class LlamaBodyFn(torch.autograd.Function):
         out = f32(B, S_t, d)
         xf = f32(B * S_t, d)
         rstd_f = f32(B * S_t) if need_bwd else None
-        check(lib.immtsf_llama_body_rmsnorm(ptr(x), B, Sx, Sx - S_t, d, ptr(tl(y, Sx)), ptr(xf), ptr(model.norm.weight), eps, ptr(out), None,
-                                            ptr(rstd_f), st), "llama_body_rmsnorm")
+        check(rows_k["body_rmsnorm"](ptr(x), B, Sx, Sx - S_t, d, ptr(tl(y, Sx)), ptr(xf), ptr(model.norm.weight), eps, ptr(out), None,
+                                     ptr(rstd_f), st), "llama_body_rmsnorm")
         if need_bwd:
             ctx.saved, ctx.final = saved, (xf, rstd_f)
             ctx.model, ctx.dims, ctx.precision, ctx.rope = model, (B, S_p, S_t, d, H, H_kv, hd, inner), precision, (cos_t, sin_t)
@@ -4055,6 +4138,7 @@ class LlamaBodyFn(torch.autograd.Function):
         dq, dkv = H * hd, H_kv * hd
         dqkv = dq + 2 * dkv
         P = _FrozenProducts(lib, model, ctx.precision, st)
+        rms_backward = _llama_rows(lib, P)["body_rmsnorm_backward"]
         bf = P.bf
         scale = 1.0 / float(hd) ** 0.5
         cos_t, sin_t = ctx.rope
@@ -4062,7 +4146,7 @@ class LlamaBodyFn(torch.autograd.Function):
 
         def rms_bwd(g, x, rstd, w, resid):
             o, o16 = f32(M, d), b16(M, d)
-            check(lib.immtsf_llama_body_rmsnorm_backward(ptr(g), ptr(x), ptr(rstd), ptr(w), ptr(resid), M, d, ptr(o), ptr(o16), st),
+            check(rms_backward(ptr(g), ptr(x), ptr(rstd), ptr(w), ptr(resid), M, d, ptr(o), ptr(o16), st),
                   "llama_body_rmsnorm_backward")
             return o, o16
 
@@ -4076,7 +4160,7 @@ class LlamaBodyFn(torch.autograd.Function):
             dgu, dgu16 = (None, b16(M, 2 * inner)) if bf else (f32(M, 2 * inner), None)
             check(lib.immtsf_llama_body_swiglu_backward(ptr(gu_t), ptr(dact), M, inner, ptr(dgu), ptr(dgu16), st),
                   "llama_body_swiglu_backward")
-            dg = P.mm_t(dgu, dgu16, *_llama_gu(model, mlp, P), M)
+            dg = _llama_gu_cat(model, mlp, P).mm_t(dgu, dgu16, M)
             dx1, dx1_16 = rms_bwd(dg, x1_t, rstd2, layer.post_attention_layernorm.weight, dx)
             dao = P.lin_t(dx1, dx1_16, att.o_proj, M)
             dbuf, dbuf16 = f32(M, dqkv), b16(M, dqkv)
@@ -4086,7 +4170,7 @@ class LlamaBodyFn(torch.autograd.Function):
                                                            _adr(dbuf, dq + dkv), dqkv, st), "llama_body_attention_backward")
             check(lib.immtsf_llama_body_rope(ptr(dbuf), dqkv, M, S_t, S_p, H + H_kv, S, ptr(cos_t), ptr(sin_t), 1, ptr(dbuf16), st),
                   "llama_body_rope (backward)")
-            dh = P.mm_t(dbuf, dbuf16, *_llama_qkv(model, att, P), M)
+            dh = _llama_qkv_cat(model, att, P).mm_t(dbuf, dbuf16, M)
             dx, dx16 = rms_bwd(dh, x_t, rstd1, layer.input_layernorm.weight, dx1)
         return dx.view(B, S_t, d), None, None, None, None
 
@@ -4096,7 +4180,9 @@ def llama_body(llm_model, prefix_embeds, tail_embeds, training, precision=None):
     Only tail_embeds takes a gradient (prefix_embeds may require one; it gets none).  Llama's only dropout is attention_dropout:
     `training` with config.attention_dropout > 0 is not supported (callers take the stock path).  The model's parameters are read in
     place, but for the cached q | k | v and gate | up concatenations and, in bf16 mode, the cached bf16 weight images (shared with
-    llama_embed_notes).  Outside llama_body_supported this raises: callers check."""
+    llama_embed_notes).  A model stored in bf16 (config.llama_stored_bf16) is read in place altogether, as llama_embed_notes says; inputs,
+    result, gradient and saved tensors stay fp32, and a data gradient through q | k | v (gate | up) is its members' layout-1 products
+    summed in the order q, k, v (gate, up).  Outside llama_body_supported this raises: callers check."""
     tail, prefix, need_bwd = _body_inputs("llama_body", llm_model, prefix_embeds, tail_embeds, llama_body_supported)
     if training and float(getattr(llm_model.config, "attention_dropout", 0.0) or 0.0) > 0.0:
         raise _lib.ImmtsfError("llama_body: attention dropout in training mode is not supported (take the stock path)")

@@ -11,7 +11,9 @@ weights stays unpinned.  The sub-layers on the
 hot-path scope -- PatchEmbedding on values and on timestamps, ReprogrammingLayer projections, FlattenHead -- use the
 HIP GEMM.  A GPT-2 body inside immtsf.ops.gpt2_body_supported runs on immtsf.ops.gpt2_body (csrc/gpt2.hip, DESIGN 4l: the frozen body
 with its backward over the patch rows only; config.timellm_fused / IMMTSF_TIMELLM_FUSED=0 turns it off, `fused_body_calls` counts),
-a Llama body inside immtsf.ops.llama_body_supported on immtsf.ops.llama_body (csrc/llama_body.hip) and a BERT body inside
+a Llama body inside immtsf.ops.llama_body_supported on immtsf.ops.llama_body (csrc/llama_body.hip; a body whose parameters are
+all stored in bf16 is inside it with config.llama_stored_bf16 on, DESIGN 4v, and runs ONLY on that route: the stock call raises torch's
+dtype error on the fp32 inputs_embeds this module forms, with the knob on or off) and a BERT body inside
 immtsf.ops.bert_body_supported on immtsf.ops.bert_body (csrc/bert_body.hip, DESIGN 4s: bidirectional, so its backward runs through the
 prompt rows too; its dropouts are drawn in the kernels; in bf16 mode only, where it measured 2.8x the stock call -- in fp32 mode the
 stock call is faster and stays, unless config.timellm_bert_fp32 / IMMTSF_TIMELLM_BERT_FP32=1) under the same knob; `self.llm_model` stays the transformers model, and every

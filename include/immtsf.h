@@ -1068,6 +1068,35 @@ int immtsf_gemm_split_supported(int32_t layout, int32_t M, int32_t N, int32_t K,
 int immtsf_gemm_split(int32_t layout, const float* A, int32_t lda, const void* Bhi, const void* Blo, int32_t ldb, float* C, int32_t ldc,
                       const float* bias, int32_t M, int32_t N, int32_t K, immtsf_stream_t stream);
 
+/* ---- A frozen Llama stored in bf16, read in place (added within ABI 7: new functions only; csrc/gemm_split.hip, csrc/llama_embed.hip,
+ * csrc/llama_body.hip): what immtsf.ops.llama_embed_notes / llama_body run for a LlamaModel whose every parameter is bf16 when
+ * immtsf.config.llama_stored_bf16 is on.  No fp32 copy and no second bf16 image of any parameter is made.
+ * ..._gemm_asplit: ..._gemm_split for a weight that IS its bf16 image: C (M, N; pitch ldc) = op(A) op(B16) + bias, A (M, K; pitch lda) fp32,
+ *   B16 bf16 with the layouts, pitch rule and pointer-offset sub-blocks of ..._gemm_split.  A is cut in registers into a_hi, a_lo and every
+ *   32-deep step of an output fragment is a_lo b + a_hi b, in that order, on v_mfma_f32_16x16x32_bf16 with fp32 sums: exact in B, 16 - 17
+ *   bits of A.  Integer operands with |A| < 2^16 and every partial sum below 2^24 give the exact product.  Same three tiles and selection
+ *   as ..._gemm_split, no split-K, no atomics: the same inputs give the same bits.
+ * ..._gemm_asplit_supported: ..._gemm_split_supported's set.  Outside it, or with A / B16 not 16-byte aligned, ..._gemm_asplit returns
+ *   IMMTSF_EUNSUPPORTED before anything is launched and C is untouched.
+ * ..._p16: the row kernels of the same name with the model's parameter -- the embedding table (vocab, d), an RMSNorm weight (d) -- read as
+ *   bf16 and up-cast in registers; every other argument, every check and the arithmetic are those of the fp32 entry point, so bf16
+ *   parameters give bit for bit what the fp32 entry point gives on their up-cast copy.  The parameter pointer must be 8-byte aligned. */
+int immtsf_gemm_asplit_supported(int32_t layout, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldb, int32_t ldc);
+int immtsf_gemm_asplit(int32_t layout, const float* A, int32_t lda, const void* B16, int32_t ldb, float* C, int32_t ldc, const float* bias,
+                       int32_t M, int32_t N, int32_t K, immtsf_stream_t stream);
+int immtsf_llama_embed_tokens_p16(const int32_t* ids, int32_t rows, const void* embed16, int32_t vocab, int32_t d, float* out,
+                                  immtsf_stream_t stream);
+int immtsf_llama_embed_rmsnorm_p16(const float* x, int64_t rows, int32_t d, const void* w16, float eps, float* out32, void* out16,
+                                   immtsf_stream_t stream);
+int immtsf_llama_embed_add_rmsnorm_p16(float* x, const float* y, int64_t rows, int32_t d, const void* w16, float eps, float* out32, void* out16,
+                                       immtsf_stream_t stream);
+int immtsf_llama_embed_pool_p16(float* x, const float* y, const int32_t* cu, int32_t N, int32_t rows, int32_t d, const void* w16, float eps,
+                                float* rstd, float* pooled, immtsf_stream_t stream);
+int immtsf_llama_body_rmsnorm_p16(const float* xin, int32_t B, int32_t S_in, int32_t s_from, int32_t d, const float* y, float* xout,
+                                  const void* w16, float eps, float* out32, void* out16, float* rstd, immtsf_stream_t stream);
+int immtsf_llama_body_rmsnorm_backward_p16(const float* dy, const float* x, const float* rstd, const void* w16, const float* resid,
+                                           int64_t rows, int32_t d, float* dx32, void* dx16, immtsf_stream_t stream);
+
 /* ---- TTM backbone (added within ABI 7: new functions only; csrc/ttm.hip): the narrow mixer blocks of reference layers/MLP.py
  * (TTMMixerBlock in mode "patch" / "channel") as ONE launch forward and TWO backward, and the feature mixer's gate + residual as one
  * launch per direction.  All fp32.

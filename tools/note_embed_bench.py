@@ -19,8 +19,13 @@ ratios stand), max_length 1024, the GPT-2 note mix behind a begin-of-text token 
 --products split: config.frozen_products = "split" for the whole run -- in fp32 mode the fused operator forms its weight products on
 the split-bf16 kernel (csrc/gemm_split.hip); bf16 mode and the stock side do not read it.  The same lines, with "products".
 
-usage: python tools/note_embed_bench.py [--model gpt2|bert|llama] [--products fp32|split] [--layers 2] [--notes 32] [--passes 3]
-                                        [--single 8] [--out FILE]
+--stored bf16 (with --model llama): every parameter of the body cast to bf16 as from_pretrained leaves a bf16 checkpoint (buffers
+untouched) and config.llama_stored_bf16 on -- the fused operator reads the checkpoint in place and the stock side is
+transformers' padded call OF THE SAME bf16 MODEL, in both precision modes.  Every line also carries each side's peak allocated memory
+(torch.cuda.max_memory_allocated over its timed passes, MiB, the model included).
+
+usage: python tools/note_embed_bench.py [--model gpt2|bert|llama] [--products fp32|split] [--stored fp32|bf16] [--layers 2] [--notes 32]
+                                        [--passes 3] [--single 8] [--out FILE]
 """
 import argparse
 import json
@@ -69,6 +74,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("gpt2", "bert", "llama"), default="gpt2")
     ap.add_argument("--products", choices=("fp32", "split"), default="fp32", help="config.frozen_products for the run (read in fp32 mode)")
+    ap.add_argument("--stored", choices=("fp32", "bf16"), default="fp32", help="dtype the --model llama body is stored in")
     ap.add_argument("--layers", type=int, default=2, help="layers of the --model llama body")
     ap.add_argument("--notes", type=int, default=32)
     ap.add_argument("--single", type=int, default=8, help="notes of the one-call-per-note workload (the first ones of the mix)")
@@ -76,6 +82,8 @@ def main():
     ap.add_argument("--stock-slice", type=int, default=8)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.stored == "bf16" and args.model != "llama":
+        ap.error("--stored bf16 needs --model llama")
     import torch
     from transformers import BertConfig, BertModel, GPT2Config, GPT2Model, LlamaConfig, LlamaModel
 
@@ -108,6 +116,10 @@ def main():
         lengths = note_lengths(args.notes)
         notes = [chr(97 + i % 26) * n for i, n in enumerate(lengths)]
     model = model.requires_grad_(False).to(dev).eval()
+    if args.stored == "bf16":
+        for p in model.parameters():
+            p.data = p.data.to(torch.bfloat16)
+        config.llama_stored_bf16 = True
     ratio = sum(lengths) / (len(lengths) * max_length)
     print(f"note lengths (tokens): {lengths}", flush=True)
     print(f"rows: real {sum(lengths)} of padded {len(lengths) * max_length} (ratio {ratio:.4f})", flush=True)
@@ -128,28 +140,34 @@ def main():
                 L.embed_notes([[note]], tok, model, max_length=max_length)
 
     def timed(fn):
+        """(milliseconds, peak allocated MiB) of one pass"""
         torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
         fn()
         torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3
+        return (time.perf_counter() - t0) * 1e3, torch.cuda.max_memory_allocated() / 2 ** 20
 
     lines = []
     for prec in ("fp32", "bf16"):
         config.precision = prec
-        line = {"tool": "note_embed_bench", "model": args.model, "precision": prec, "products": args.products, "layers": layers, "d": int(getattr(model.config, "hidden_size", 768)), "max_length": max_length,
+        line = {"tool": "note_embed_bench", "model": args.model, "precision": prec, "products": args.products, "stored": args.stored,
+                "layers": layers, "d": int(getattr(model.config, "hidden_size", 768)), "max_length": max_length,
                 "notes": len(notes), "row_ratio": round(ratio, 4), "single_notes": args.single, "single_row_ratio":
                 round(sum(lengths[:args.single]) / (args.single * max_length), 4), "passes": args.passes}
         for what, fn in (("batch", batch), ("single", single)):
             for fused in (True, False):
                 fn(fused)
-            t = {True: [], False: []}
+            t, peak = {True: [], False: []}, {True: 0.0, False: 0.0}
             for _ in range(args.passes):
                 for fused in (True, False):
-                    t[fused].append(timed(lambda: fn(fused)))
+                    ms, mib = timed(lambda: fn(fused))
+                    t[fused].append(ms)
+                    peak[fused] = max(peak[fused], mib)
             for fused, name in ((True, "fused"), (False, "stock")):
                 line[f"{what}_{name}_ms"] = round(min(t[fused]), 3)
                 line[f"{what}_{name}_ms_passes"] = [round(v, 3) for v in t[fused]]
+                line[f"{what}_{name}_peak_mib"] = round(peak[fused], 1)
             line[f"{what}_speedup"] = round(min(t[False]) / min(t[True]), 2)
         config.note_embed_fused = True
         print(json.dumps(line), flush=True)

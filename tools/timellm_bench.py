@@ -31,8 +31,14 @@ forecasting() + backward, the same alternating passes; one JSON line per precisi
 --products split: config.frozen_products = "split" for the whole run -- in fp32 mode the fused body forms its weight products on the
 split-bf16 kernel (csrc/gemm_split.hip); bf16 mode and the stock side do not read it.  The same lines, with "products" in them.
 
-usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--products fp32|split] [--prompt | --reprogram] [--iters 5] [--passes 5]
-                                     [--batch 64] [--out FILE]
+--stored bf16 (with --llm LLAMA): every parameter of the body cast to bf16 as from_pretrained leaves a bf16 checkpoint (buffers
+untouched) and config.llama_stored_bf16 on -- the fused body reads the checkpoint in place (fp32 inputs, fp32 result and
+gradient) and the stock side is transformers' call OF THE SAME bf16 MODEL on the inputs cast to bf16 (it raises on fp32 inputs_embeds), in
+both precision modes.  Every body line also carries each side's peak allocated memory (torch.cuda.max_memory_allocated over its timed
+passes, MiB, the model included).
+
+usage: python tools/timellm_bench.py [--llm GPT2|LLAMA|BERT] [--products fp32|split] [--stored fp32|bf16] [--prompt | --reprogram]
+                                     [--iters 5] [--passes 5] [--batch 64] [--out FILE]
 """
 import argparse
 import json
@@ -57,6 +63,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--llm", choices=("GPT2", "LLAMA", "BERT"), default="GPT2")
     ap.add_argument("--products", choices=("fp32", "split"), default="fp32", help="config.frozen_products for the run (read in fp32 mode)")
+    ap.add_argument("--stored", choices=("fp32", "bf16"), default="fp32", help="dtype the --llm LLAMA body is stored in")
     ap.add_argument("--prompt", action="store_true", help="time the prompt statistics, knob on against knob off (GPT-2 body)")
     ap.add_argument("--reprogram", action="store_true", help="time the folded word prototypes, knob on against knob off (GPT-2 body)")
     args = ap.parse_args()
@@ -65,6 +72,8 @@ def main():
     if args.prompt and args.reprogram:
         ap.error("--prompt and --reprogram are separate legs")
     llama, bert = args.llm == "LLAMA", args.llm == "BERT"
+    if args.stored == "bf16" and not llama:
+        ap.error("--stored bf16 needs --llm LLAMA")
     layers = 2 if llama else LAYERS
     import torch
     from immtsf import config, ops
@@ -79,6 +88,10 @@ def main():
         immtsf_offline_llm=dict(hidden_size=4096, num_attention_heads=32, num_key_value_heads=32, intermediate_size=11008) if llama
         else dict(hidden_size=768, num_attention_heads=12, intermediate_size=3072, max_position_embeddings=1024) if bert
         else True)).to(dev).train()
+    if args.stored == "bf16":
+        for p in m.llm_model.parameters():
+            p.data = p.data.to(torch.bfloat16)
+        config.llama_stored_bf16 = True
     m.word_embeddings = m.llm_model.get_input_embeddings().weight
     g = torch.Generator().manual_seed(1)
     mask = (torch.rand(B, L, C, generator=g) < 0.7).float().to(dev)
@@ -101,7 +114,7 @@ def main():
         if fused:
             out = (ops.llama_body if llama else ops.bert_body if bert else ops.gpt2_body)(m.llm_model, prefix, tail, True)
         else:
-            out = m.llm_model(inputs_embeds=torch.cat([prefix, tail], 1)).last_hidden_state[:, -S_t:]
+            out = m.llm_model(inputs_embeds=torch.cat([prefix, tail.to(prefix.dtype)], 1)).last_hidden_state[:, -S_t:]
         (out * up_b).sum().backward()
 
     def whole(fused):
@@ -195,7 +208,7 @@ def main():
         config.timellm_reprogram_fused = default
     for prec in (() if (args.prompt or args.reprogram) else ("fp32", "bf16")):
         config.precision = prec
-        line = {"tool": "timellm_bench", "precision": prec, "products": args.products, "B": B, "layers": layers, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
+        line = {"tool": "timellm_bench", "precision": prec, "products": args.products, "stored": args.stored, "B": B, "layers": layers, "d": d, "S_p": S_p, "S_t": S_t, "iters": args.iters,
                 "passes": args.passes}
         if llama:       # the fused plan: 9 launches a layer + 3 for the last layer's tail queries + table and final norm;
             #             10 a layer backward (the attention backward is two) + the final norm's
@@ -208,16 +221,21 @@ def main():
             for fused in (True, False):
                 for _ in range(2):
                     fn(fused)
-            t = {True: [], False: []}
+            t, peak = {True: [], False: []}, {True: 0.0, False: 0.0}
             for _ in range(args.passes):
                 for fused in (True, False):
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
                     t[fused].append(timed(lambda: fn(fused), args.iters))
+                    peak[fused] = max(peak[fused], torch.cuda.max_memory_allocated() / 2 ** 20)
             for fused, name in ((True, "fused"), (False, "stock")):
                 line[f"{what}_{name}_ms"] = round(min(t[fused]), 3)
                 line[f"{what}_{name}_ms_passes"] = [round(v, 3) for v in t[fused]]
+                line[f"{what}_{name}_peak_mib"] = round(peak[fused], 1)
             line[f"{what}_speedup"] = round(min(t[False]) / min(t[True]), 2)
         config.timellm_fused = True
         line["split_product_calls"] = ops.split_product_calls
+        line["asplit_product_calls"] = ops.asplit_product_calls
         print(json.dumps(line), flush=True)
         lines.append(json.dumps(line))
     if args.out:
