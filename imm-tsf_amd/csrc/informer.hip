@@ -299,11 +299,11 @@ __global__ __launch_bounds__(256) void informer_front_reduce_kernel(int D, int K
 
 // ---- tail -----------------------------------------------------------------------------------------------------------------------------
 struct TailDims {
-    int B, Lp, P, C, D;
+    int B, Lp, P, C, D, off;      // x (B, P, D): a window's rows off .. off + Lp - 1 are the ones normalised and projected
 };
 
 bool tail_bad(const TailDims& t) {
-    return t.B < 1 || t.Lp < 1 || t.Lp > t.P || !immtsf_informer_model_supported(1, t.P, t.C, t.D);
+    return t.B < 1 || t.Lp < 1 || t.off < 0 || t.off + t.Lp > t.P || !immtsf_informer_model_supported(1, t.P, t.C, t.D);
 }
 
 int tail_slices(const TailDims& t) {
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256) void informer_tail_fwd_kernel(TailDims t, cons
     const long q = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= (long)t.B * t.Lp) return;
     const int b = (int)(q / t.Lp), tt = (int)(q - (long)b * t.Lp), n4 = t.D >> 2;
-    const float4* xr = reinterpret_cast<const float4*>(x + ((size_t)b * t.P + tt) * t.D);
+    const float4* xr = reinterpret_cast<const float4*>(x + ((size_t)b * t.P + t.off + tt) * t.D);
     float4 v[4];
     float s = 0.f;
 #pragma unroll
@@ -375,7 +375,7 @@ __global__ __launch_bounds__(256) void informer_tail_fwd_kernel(TailDims t, cons
     if (lane < t.C) y[(size_t)q * t.C + lane] = fmaf(mine + bias[lane], stdevs[(size_t)b * t.C + lane], means[(size_t)b * t.C + lane]);
 }
 
-// blocks [0, ceil(B P / 4)): dx, a wave per row of x (exact zeros for t >= Lp).  The DT * ns blocks behind them: the parameter partials,
+// blocks [0, ceil(B P / 4)): dx, a wave per row of x (exact zeros outside the rows off .. off + Lp - 1).  The DT * ns blocks behind them: the parameter partials,
 // 64 columns x 4 row lanes over a slice of the B Lp rows, part [ns][2 D + C D + C] = [d gamma | d beta | dW | db]
 __global__ __launch_bounds__(256) void informer_tail_bwd_kernel(TailDims t, int ns, const float* __restrict__ x, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, const float* __restrict__ W,
@@ -391,9 +391,9 @@ __global__ __launch_bounds__(256) void informer_tail_bwd_kernel(TailDims t, int 
     if ((int)blockIdx.x < nrb) {
         const long q = (long)blockIdx.x * 4 + (tid >> 6);
         if (q >= xrows) return;
-        const int b = (int)(q / t.P), tt = (int)(q - (long)b * t.P), n4 = t.D >> 2;
+        const int b = (int)(q / t.P), tt = (int)(q - (long)b * t.P) - t.off, n4 = t.D >> 2;
         float4* dxr = reinterpret_cast<float4*>(dx + (size_t)q * t.D);
-        if (tt >= t.Lp) {
+        if (tt < 0 || tt >= t.Lp) {
             for (int j = lane; j < n4; j += 64) dxr[j] = make_float4(0.f, 0.f, 0.f, 0.f);
             return;
         }
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256) void informer_tail_bwd_kernel(TailDims t, int 
             const long r = rc + rr;
             if (r >= r1) break;
             const int b = (int)(r / t.Lp), tt = (int)(r - (long)b * t.Lp);
-            const float xv = live ? x[((size_t)b * t.P + tt) * t.D + d] : 0.f;
+            const float xv = live ? x[((size_t)b * t.P + t.off + tt) * t.D + d] : 0.f;
             const float xh = (xv - ms[rr]) * rs[rr], n = fmaf(xh, gam, bet);
             float dn = 0.f;
 #pragma unroll
@@ -604,15 +604,14 @@ int immtsf_informer_front_backward(int32_t B, int32_t L, int32_t input_len, int3
 }
 
 size_t immtsf_informer_tail_workspace_bytes(int32_t B, int32_t Lp, int32_t C, int32_t d_model) {
-    const TailDims t{B, Lp, Lp, C, d_model};
+    const TailDims t{B, Lp, Lp, C, d_model, 0};
     if (Lp > IM_LMAX || tail_bad(t)) return 0;
     return (size_t)tail_slices(t) * ((size_t)2 * d_model + (size_t)C * d_model + C) * sizeof(float);
 }
 
-int immtsf_informer_tail_forward(int32_t B, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model, const float* x, const float* gamma,
-                                 const float* beta, float eps, const float* W, const float* bias, const float* means, const float* stdev,
-                                 float* y, float* row_mean, float* row_rstd, immtsf_stream_t stream) {
-    const TailDims t{B, Lp, pred_len, C, d_model};
+static int tail_forward(const TailDims& t, const float* x, const float* gamma, const float* beta, float eps, const float* W, const float* bias,
+                        const float* means, const float* stdev, float* y, float* row_mean, float* row_rstd, immtsf_stream_t stream) {
+    const int B = t.B, Lp = t.Lp;
     if (!x || !gamma || !beta || !W || !bias || !means || !stdev || !y || !row_mean || !row_rstd) return IMMTSF_EINVAL;
     if (!al16(x) || !al16(gamma) || !al16(beta) || !al16(W)) return IMMTSF_EINVAL;
     if (tail_bad(t)) return IMMTSF_EUNSUPPORTED;
@@ -623,11 +622,10 @@ int immtsf_informer_tail_forward(int32_t B, int32_t Lp, int32_t pred_len, int32_
     return IMMTSF_OK;
 }
 
-int immtsf_informer_tail_backward(int32_t B, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model, const float* x, const float* gamma,
-                                  const float* beta, const float* W, const float* stdev, const float* row_mean, const float* row_rstd,
-                                  const float* dy, float* dx, float* dparams, void* workspace, size_t workspace_bytes,
-                                  immtsf_stream_t stream) {
-    const TailDims t{B, Lp, pred_len, C, d_model};
+static int tail_backward(const TailDims& t, const float* x, const float* gamma, const float* beta, const float* W, const float* stdev,
+                         const float* row_mean, const float* row_rstd, const float* dy, float* dx, float* dparams, void* workspace,
+                         size_t workspace_bytes, immtsf_stream_t stream) {
+    const int B = t.B, Lp = t.Lp, pred_len = t.P, C = t.C, d_model = t.D;
     if (!x || !gamma || !beta || !W || !stdev || !row_mean || !row_rstd || !dy || !dx || !dparams || !workspace) return IMMTSF_EINVAL;
     if (!al16(x) || !al16(gamma) || !al16(W) || !al16(dx)) return IMMTSF_EINVAL;
     if (tail_bad(t)) return IMMTSF_EUNSUPPORTED;
@@ -644,6 +642,35 @@ int immtsf_informer_tail_backward(int32_t B, int32_t Lp, int32_t pred_len, int32
     hipLaunchKernelGGL(informer_slice_sum_kernel, dim3(grid_for(N, 256)), dim3(256), 0, s, N, ns, part, dparams);
     IMMTSF_LAUNCH_CHECK();
     return IMMTSF_OK;
+}
+
+int immtsf_informer_tail_forward(int32_t B, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model, const float* x, const float* gamma,
+                                 const float* beta, float eps, const float* W, const float* bias, const float* means, const float* stdev,
+                                 float* y, float* row_mean, float* row_rstd, immtsf_stream_t stream) {
+    return tail_forward(TailDims{B, Lp, pred_len, C, d_model, 0}, x, gamma, beta, eps, W, bias, means, stdev, y, row_mean, row_rstd, stream);
+}
+
+int immtsf_informer_tail_backward(int32_t B, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model, const float* x, const float* gamma,
+                                  const float* beta, const float* W, const float* stdev, const float* row_mean, const float* row_rstd,
+                                  const float* dy, float* dx, float* dparams, void* workspace, size_t workspace_bytes,
+                                  immtsf_stream_t stream) {
+    return tail_backward(TailDims{B, Lp, pred_len, C, d_model, 0}, x, gamma, beta, W, stdev, row_mean, row_rstd, dy, dx, dparams, workspace,
+                         workspace_bytes, stream);
+}
+
+// TimesNet's tail (models/TimesNet.py): the same kernels on x (B, T, D) with the horizon at rows row_off .. row_off + Lp - 1 of a window
+int immtsf_timesnet_tail_forward(int32_t B, int32_t Lp, int32_t T, int32_t row_off, int32_t C, int32_t d_model, const float* x,
+                                 const float* gamma, const float* beta, float eps, const float* W, const float* bias, const float* means,
+                                 const float* stdev, float* y, float* row_mean, float* row_rstd, immtsf_stream_t stream) {
+    return tail_forward(TailDims{B, Lp, T, C, d_model, row_off}, x, gamma, beta, eps, W, bias, means, stdev, y, row_mean, row_rstd, stream);
+}
+
+int immtsf_timesnet_tail_backward(int32_t B, int32_t Lp, int32_t T, int32_t row_off, int32_t C, int32_t d_model, const float* x,
+                                  const float* gamma, const float* beta, const float* W, const float* stdev, const float* row_mean,
+                                  const float* row_rstd, const float* dy, float* dx, float* dparams, void* workspace, size_t workspace_bytes,
+                                  immtsf_stream_t stream) {
+    return tail_backward(TailDims{B, Lp, T, C, d_model, row_off}, x, gamma, beta, W, stdev, row_mean, row_rstd, dy, dx, dparams, workspace,
+                         workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -318,6 +318,13 @@ _PROTOS = {
     "immtsf_informer_tail_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
     "immtsf_informer_tail_forward": (C.c_int, [C.c_int32] * 5 + [c_f32p, c_f32p, c_f32p, C.c_float] + [c_f32p] * 7 + [c_stream]),
     "immtsf_informer_tail_backward": (C.c_int, [C.c_int32] * 5 + [c_f32p] * 10 + [C.c_void_p, C.c_size_t, c_stream]),
+    "immtsf_timesnet_model_supported": (C.c_int, [C.c_int32] * 4),
+    "immtsf_timesnet_front_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "immtsf_timesnet_front_forward": (C.c_int, [C.c_int32] * 7 + [c_f32p] * 12 + [C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, c_stream]),
+    "immtsf_timesnet_front_backward": (C.c_int, [C.c_int32] * 7 + [c_f32p] * 12 + [C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                 C.c_size_t, c_stream]),
+    "immtsf_timesnet_tail_forward": (C.c_int, [C.c_int32] * 6 + [c_f32p, c_f32p, c_f32p, C.c_float] + [c_f32p] * 7 + [c_stream]),
+    "immtsf_timesnet_tail_backward": (C.c_int, [C.c_int32] * 6 + [c_f32p] * 10 + [C.c_void_p, C.c_size_t, c_stream]),
     "immtsf_eval_metrics_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "immtsf_eval_metrics_accum": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                             c_stream]),

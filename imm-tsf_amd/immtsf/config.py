@@ -141,6 +141,20 @@ informer_fused = os.environ.get("IMMTSF_INFORMER_FUSED", "1") != "0"
 # immtsf.ops.token_embed, layer_norm and linear) -- the cross-check.  Independent of informer_fused, which steers the layers.  fp32 in
 # either precision mode
 informer_model_fused = os.environ.get("IMMTSF_INFORMER_MODEL_FUSED", "1") != "0"
+# TimesNet's model (models.TimesNet): everything around the TimesBlock loop -- padding, plain instance norm, the input concatenation,
+# DataEmbedding, the horizon rows and predict_linear as one HIP launch forward and two backward (csrc/timesnet_model.hip), the last
+# layer_norm + projection + de-normalisation + the slice to the horizon as one forward and two backward (csrc/informer.hip's tail kernels
+# with a row offset) -- wherever immtsf_timesnet_model_supported allows, c_out == enc_in, the batch fits the model lengths and wants no
+# gradient; IMMTSF_TIMESNET_MODEL_FUSED=0: the composed path (torch cats and permutes around immtsf.ops.token_embed, linear and layer_norm),
+# bit for bit what it was -- the cross-check.  fp32 in either precision mode
+timesnet_model_fused = os.environ.get("IMMTSF_TIMESNET_MODEL_FUSED", "1") != "0"
+# ... and only up to the largest size at which the route measured not slower than the composed one: (input_len + pred_len)^2 * d_model <=
+# this (cfg4's 64^2 * 16; at 192^2 * 64 the fused step measured 1.7 % slower).  None: no bound (tools/timesnet_bench.py --model
+# measures the kernels on both sides of it)
+timesnet_model_max_work = 64 * 64 * 16
+# whether that front end keeps its embedded rows E (B, input_len, d_model) for the backward (1) or forms them again there (0, the
+# default: DESIGN 4e has the measurement)
+timesnet_model_save_e = os.environ.get("IMMTSF_TIMESNET_MODEL_SAVE_E", "0") == "1"
 # CRU's Kalman recurrence as one HIP launch forward and two backward (csrc/cru.hip) wherever the cell is the continuous CRUCell with the
 # single Linear + softmax coefficient net and immtsf_cru_supported allows; IMMTSF_CRU_FUSED=0: the composed path (a Python loop over the
 # time points around torch.matrix_exp) -- the cross-check.  The kernels are fp32 in either precision mode

@@ -3199,6 +3199,128 @@ def informer_tail(x, norm, projection, means, stdev, Lp):
     return InformerTailFn.apply(x.float(), norm.weight, norm.bias, projection.weight, projection.bias, means, stdev, int(Lp), float(norm.eps))
 
 
+# ---- TimesNet's model stages (csrc/timesnet_model.hip, csrc/informer.hip's tail): everything of models/TimesNet.py around the TimesBlocks
+SITE_TIMESNET_EMBED = SITE_LAYER_BASE + 41      # token_embed's site and element (b input_len + s) d_model + f: either route, one mask
+
+
+def timesnet_model_supported(input_len, pred_len, Cc, d_model):
+    """the limits of the fused TimesNet stages (immtsf_timesnet_model_supported): input_len + pred_len <= 256, 1 <= C <= 10,
+    d_model % 4 == 0, 4 <= d_model <= 512"""
+    return bool(_lib.load().immtsf_timesnet_model_supported(int(input_len), int(pred_len), int(Cc), int(d_model)))
+
+
+class TimesNetFrontFn(torch.autograd.Function):
+    """padding, plain instance norm, the input concatenation, DataEmbedding, the horizon rows and predict_linear as ONE launch; backward =
+    d predict_linear.weight / .bias and d tokenConv.weight in TWO (immtsf_timesnet_front_forward / _backward).  data / mask (B, L, C),
+    tp (B, L), tpp (B, Lp) are data: no gradient.  dims = (input_len, pred_len); drop = (p, seed, counter pointer, site); save_e: keep
+    the embedded rows for the backward instead of forming them again.  -> enc (B, input_len + pred_len, D), stats (2, B, 1, C)."""
+
+    @staticmethod
+    def forward(ctx, data, mask, tp, tpp, W_tok, pe, W_pred, b_pred, dims, drop, save_e):
+        lib = _lib.load()
+        data, mask, tp, tpp, W_tok, pe, W_pred, b_pred = (_c(t) for t in (data, mask, tp, tpp, W_tok, pe, W_pred, b_pred))
+        _need_gpu(data, mask, tp, tpp, W_tok, pe, W_pred, b_pred)
+        (B, L, Cc), Lp, (S, P), D = data.shape, tpp.shape[1], dims, W_tok.shape[0]
+        p, seed, cnt, site = drop
+        dev = data.device
+        stats = torch.empty(2, B, 1, Cc, dtype=torch.float32, device=dev)
+        enc = torch.empty(B, S + P, D, dtype=torch.float32, device=dev)
+        E = torch.empty(B, S, D, dtype=torch.float32, device=dev) if save_e else None
+        check(lib.immtsf_timesnet_front_forward(B, L, S, Lp, P, Cc, D, ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(W_tok), ptr(pe), ptr(W_pred),
+                                                ptr(b_pred), ptr(stats[0]), ptr(stats[1]), ptr(enc), ptr(E), p, seed, site, cnt, stream_ptr()),
+              "timesnet_front_forward")
+        ctx.cfg = (B, L, S, Lp, P, Cc, D, p, seed, cnt, site)
+        ctx.save_for_backward(data, mask, tp, tpp, W_tok, pe, W_pred, stats, E)
+        ctx.mark_non_differentiable(stats)
+        return enc, stats
+
+    @staticmethod
+    def backward(ctx, d_enc, _d_stats):
+        lib = _lib.load()
+        data, mask, tp, tpp, W_tok, pe, W_pred, stats, E = ctx.saved_tensors
+        B, L, S, Lp, P, Cc, D, p, seed, cnt, site = ctx.cfg
+        dev, T, Kc = data.device, S + P, 2 * Cc + 1
+        flat = torch.empty(T * T + T + D * Kc * 3, dtype=torch.float32, device=dev)      # every entry is written: no zero fill
+        ws = _bytes(lib.immtsf_timesnet_front_workspace_bytes(B, S, P, Cc, D), dev)
+        check(lib.immtsf_timesnet_front_backward(B, L, S, Lp, P, Cc, D, ptr(data), ptr(mask), ptr(tp), ptr(tpp), ptr(W_tok), ptr(pe), ptr(W_pred),
+                                                 ptr(stats[0]), ptr(stats[1]), ptr(E), ptr(d_enc.contiguous()), ptr(flat), p, seed, site, cnt,
+                                                 ptr(ws), ws.numel(), stream_ptr()), "timesnet_front_backward")
+        need = ctx.needs_input_grad
+        return (None,) * 4 + (flat[T * T + T:].view(D, Kc, 3) if need[4] else None, None, flat[:T * T].view(T, T) if need[6] else None,
+                              flat[T * T:T * T + T] if need[7] else None) + (None,) * 3
+
+
+def timesnet_front(data, mask, tp, tpp, input_len, pred_len, W_token, pe, W_predict, b_predict, p_drop=0.0, training=False, seed=None,
+                   save_e=None):
+    """data, mask (B, L <= input_len, C), tp (B, L), tpp (B, Lp <= pred_len) -> (enc (B, input_len + pred_len, D), means, stdev (B, 1, C)) of
+    TimesNet's front end.  W_token: enc_embedding's tokenConv weight (D, 2C + 1, 3); pe: its positional table (1, n, D) or (n, D);
+    W_predict (T, T), b_predict (T): predict_linear.  The dropout mask is token_embed's: one config.next_seed() when p > 0 in training
+    (`seed` overrides it), SITE_TIMESNET_EMBED.  save_e None: config.timesnet_model_save_e."""
+    B, L, Cc = data.shape
+    D, Lp, T = W_token.shape[0], tpp.shape[1], input_len + pred_len
+    pe = pe.reshape(-1, pe.shape[-1])
+    if not (timesnet_model_supported(input_len, pred_len, Cc, D) and B >= 1 and 1 <= L <= input_len and 1 <= Lp <= pred_len) or \
+            tuple(mask.shape) != (B, L, Cc) or tuple(tp.shape) != (B, L) or tpp.shape[0] != B or tuple(W_token.shape) != (D, 2 * Cc + 1, 3) or \
+            pe.shape[0] < input_len or pe.shape[1] != D or tuple(W_predict.shape) != (T, T) or b_predict is None or \
+            tuple(b_predict.shape) != (T,):
+        raise _lib.ImmtsfError(f"timesnet_front: shapes outside the fused kernel (B {B}, L {L}, input_len {input_len}, Lp {Lp}, pred_len "
+                               f"{pred_len}, C {Cc}, d_model {D})")
+    p = float(p_drop) if training else 0.0
+    drop = (p, (config.next_seed() if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF) if p > 0 else 0,
+            config.dropout_counter_ptr(data.device) if p > 0 else None, SITE_TIMESNET_EMBED)
+    enc, stats = TimesNetFrontFn.apply(data, mask, tp, tpp, W_token, pe, W_predict, b_predict, (int(input_len), int(pred_len)), drop,
+                                       bool(config.timesnet_model_save_e if save_e is None else save_e))
+    return enc, stats[0], stats[1]
+
+
+class TimesNetTailFn(torch.autograd.Function):
+    """layer_norm -> projection -> * stdev + means on the rows off .. off + Lp - 1 of x (B, T, D) as ONE launch -> (B, Lp, C); backward = dx
+    (exact zeros on every other row), d gamma, d beta, dW, d bias in TWO (immtsf_timesnet_tail_forward / _backward: InformerTailFn's
+    kernels with a row offset).  means / stdev (B, 1, C) are data: no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, W, bias, means, stdev, off, Lp, eps):
+        lib = _lib.load()
+        x, gamma, beta, W, bias, means, stdev = (_c(t) for t in (x, gamma, beta, W, bias, means, stdev))
+        _need_gpu(x, gamma, beta, W, bias, means, stdev)
+        B, T, D = x.shape
+        Cc = W.shape[0]
+        y = torch.empty(B, Lp, Cc, dtype=torch.float32, device=x.device)
+        rows = torch.empty(2, B * Lp, dtype=torch.float32, device=x.device)      # mean, rstd of every normalised row
+        check(lib.immtsf_timesnet_tail_forward(B, Lp, T, off, Cc, D, ptr(x), ptr(gamma), ptr(beta), eps, ptr(W), ptr(bias), ptr(means),
+                                               ptr(stdev), ptr(y), ptr(rows[0]), ptr(rows[1]), stream_ptr()), "timesnet_tail_forward")
+        ctx.cfg = (B, Lp, T, off, Cc, D)
+        ctx.save_for_backward(x, gamma, beta, W, stdev, rows)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, gamma, beta, W, stdev, rows = ctx.saved_tensors
+        B, Lp, T, off, Cc, D = ctx.cfg
+        dx = torch.empty_like(x)
+        flat = torch.empty(2 * D + Cc * D + Cc, dtype=torch.float32, device=x.device)      # every entry is written: no zero fill
+        ws = _bytes(lib.immtsf_informer_tail_workspace_bytes(B, Lp, Cc, D), x.device)
+        check(lib.immtsf_timesnet_tail_backward(B, Lp, T, off, Cc, D, ptr(x), ptr(gamma), ptr(beta), ptr(W), ptr(stdev), ptr(rows[0]),
+                                                ptr(rows[1]), ptr(dy.contiguous()), ptr(dx), ptr(flat), ptr(ws), ws.numel(), stream_ptr()),
+              "timesnet_tail_backward")
+        rets = (dx, flat[:D], flat[D:2 * D], flat[2 * D:2 * D + Cc * D].view(Cc, D), flat[2 * D + Cc * D:])
+        return tuple(r if need else None for r, need in zip(rets, ctx.needs_input_grad[:5])) + (None,) * 5
+
+
+def timesnet_tail(x, norm, projection, means, stdev, input_len, Lp):
+    """x (B, T, D) the last TimesBlock's output (before the last layer_norm), norm = nn.LayerNorm(D), projection = nn.Linear(D, C) with
+    bias, means / stdev (B, 1, C) of the front end -> the de-normalised forecast of rows input_len .. input_len + Lp - 1: (B, Lp, C)"""
+    B, T, D = x.shape
+    Cc = projection.weight.shape[0]
+    if not (informer_model_supported(1, T, Cc, D) and Lp >= 1 and input_len >= 0 and input_len + Lp <= T) or projection.bias is None or \
+            tuple(projection.weight.shape) != (Cc, D) or tuple(norm.weight.shape) != (D,) or norm.bias is None or \
+            means.numel() != B * Cc or stdev.numel() != B * Cc:
+        raise _lib.ImmtsfError(f"timesnet_tail: shapes outside the fused kernel (B {B}, rows {input_len} + {Lp} of {T}, C {Cc}, d_model {D})")
+    return TimesNetTailFn.apply(x.float(), norm.weight, norm.bias, projection.weight, projection.bias, means, stdev, int(input_len), int(Lp),
+                                float(norm.eps))
+
+
 # ------------------------------------------------------------------------------------------------ CRU backbone
 def cru_supported(lsd, num_basis, bandwidth, T):
     """the limits of the fused CRU recurrence (immtsf_cru_supported): lsd even, 2 <= lsd <= 32, num_basis <= 256, bandwidth <= lsd / 2,

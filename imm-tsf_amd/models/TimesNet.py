@@ -13,7 +13,8 @@ import torch.nn.functional as F
 
 from immtsf import config
 from immtsf.ops import (INCEPTION_MAX, conv2d_periods, conv2d_same_cl, inception_merge, inception_periods, inception_periods_ok, layer_norm, linear,
-                        period_aggregate, period_rows, timesnet_spectrum, timesnet_spectrum_ok)
+                        period_aggregate, period_rows, timesnet_front, timesnet_model_supported, timesnet_spectrum, timesnet_spectrum_ok,
+                        timesnet_tail)
 from immtsf.dropin import fp32_entry as _fp32_entry
 from layers.Conv_Blocks import Inception_Block_V1
 from layers.Embed import DataEmbedding
@@ -127,9 +128,49 @@ class TimesNet(nn.Module):
         self.predict_linear = nn.Linear(self.seq_len + self.pred_len, self.pred_len + self.seq_len)
         self.projection = nn.Linear(configs.d_model, configs.c_out, bias=True)
         self.zeros_pad = torch.zeros(configs.batch_size, max(configs.input_len, configs.pred_len), configs.enc_in).to(configs.device)
+        self.fused_calls = 0         # forecasting() calls that took the fused front end and tail (tests assert which path ran)
+
+    def _fused_ok(self, tp_to_predict, data, tp, mask):
+        """whether the stages around the TimesBlock loop run as immtsf.ops.timesnet_front / timesnet_tail (csrc/timesnet_model.hip): knob
+        on, fp32 data on the GPU that wants no gradient and fits the model lengths, fp32 contiguous parameters beside it, c_out == C, the
+        layers TimesNet was built with, immtsf_timesnet_model_supported, and a size at which the route measured not slower
+        (config.timesnet_model_max_work)"""
+        emb, pl, proj, ln = self.enc_embedding, self.predict_linear, self.projection, self.layer_norm
+        if not (config.timesnet_model_fused and data.dim() == 3 and tp_to_predict.dim() == 2 and self.layer >= 1 and
+                isinstance(emb, DataEmbedding) and isinstance(ln, nn.LayerNorm) and pl.bias is not None and proj.bias is not None and
+                ln.bias is not None):
+            return False
+        B, L, C = data.shape
+        batch = (tp_to_predict, data, tp, mask)
+        params = (emb.value_embedding.tokenConv.weight, emb.position_embedding.pe, pl.weight, pl.bias, proj.weight, proj.bias, ln.weight, ln.bias)
+        return (B > 0 and 1 <= L <= self.input_len and 1 <= tp_to_predict.shape[1] <= self.pred_len and
+                all(t.is_cuda and t.dtype == torch.float32 and not t.requires_grad for t in batch) and
+                all(t.dtype == torch.float32 and t.is_contiguous() and t.device == data.device for t in params) and
+                tuple(mask.shape) == (B, L, C) and tuple(tp.shape) == (B, L) and tp_to_predict.shape[0] == B and
+                proj.out_features == C and emb.value_embedding.tokenConv.in_channels == 2 * C + 1 and
+                pl.in_features == pl.out_features == self.input_len + self.pred_len and
+                timesnet_model_supported(self.input_len, self.pred_len, C, proj.in_features) and
+                (config.timesnet_model_max_work is None or
+                 (self.input_len + self.pred_len) ** 2 * proj.in_features <= config.timesnet_model_max_work))
 
     @_fp32_entry
     def forecasting(self, tp_to_predict, observed_data, observed_tp, observed_mask):
+        if self._fused_ok(tp_to_predict, observed_data, observed_tp, observed_mask):
+            B, L, _ = observed_data.shape
+            Lp = tp_to_predict.shape[1]
+            if (L < self.input_len or Lp < self.pred_len) and B > self.zeros_pad.shape[0]:      # the reference pads from batch_size rows of
+                raise RuntimeError(f"TimesNet: {B} windows to pad, but the padding buffer has batch_size = "      # zeros: it fails here
+                                   f"{self.zeros_pad.shape[0]} rows")
+            self.fused_calls += 1
+            emb, pl = self.enc_embedding, self.predict_linear
+            enc, means, stdev = timesnet_front(observed_data, observed_mask, observed_tp, tp_to_predict, self.input_len, self.pred_len,
+                                               emb.value_embedding.tokenConv.weight, emb.position_embedding.pe, pl.weight, pl.bias,
+                                               emb.dropout.p, self.training)
+            for i in range(self.layer):
+                enc = self.model[i](enc)
+                if i < self.layer - 1:
+                    enc = layer_norm(enc, self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps)
+            return timesnet_tail(enc, self.layer_norm, self.projection, means, stdev, self.input_len, Lp)
         tp_to_predict, data, tp, mask, Lp = pad_history(self.zeros_pad, self.input_len, self.pred_len, tp_to_predict,
                                                         observed_data, observed_tp, observed_mask)
         x, means, stdev = plain_instance_norm(data)

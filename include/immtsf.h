@@ -1202,6 +1202,45 @@ int immtsf_informer_tail_backward(int32_t B, int32_t Lp, int32_t pred_len, int32
                                   const float* dy, float* dx, float* dparams, void* workspace, size_t workspace_bytes,
                                   immtsf_stream_t stream);
 
+/* ---- TimesNet's model stages (added within ABI 7: new functions only; csrc/timesnet_model.hip, csrc/informer.hip; reference
+ * models/TimesNet.py:108-131).  All fp32.  With S = input_len, P = pred_len, T = S + P:
+ * front: data, mask (B, L, C), tp (B, L), tpp (B, Lp) at the caller's L <= S, Lp <= P (rows beyond count as zeros; no padded copy), W_token
+ * (d_model, 2C+1, 3) enc_embedding's tokenConv weight, pe (>= S, d_model) its positional table, W_predict (T, T) / b_predict (T)
+ * predict_linear.  forward, ONE launch: per (window, channel) mean = sum_l data / S, x = data - mean, stdev = sqrt(sum_l x^2 / S + 1e-5)
+ * over all S rows (immtsf_instance_norm's sums: the same bits) -> means, stdev (B, C); with in = [x / stdev | mask | tp] formed in LDS,
+ *     E[b, s, :] = drop(sum_k sum_c W_token[:, c, k] in[b, (s + k - 1) mod S, c] + pe[s, :])   s < S;   E[b, S + j, :] = tpp[b, j] (0: j >= Lp)
+ *     enc[b, t, d] = sum_s W_predict[t, s] E[b, s, d] + b_predict[t]                                    (B, T, d_model)
+ * dropout: the Philox keep-mask of `site` at element (b S + s) d_model + d, which is immtsf_embed_forward's on the padded input;
+ * seed_step_dev as everywhere (may be NULL).  E_save (B, S, d_model) or NULL: where to keep the embedded rows for the backward.
+ * backward, TWO launches: OVERWRITES dparams = [dW_predict (T, T) | db_predict (T) | dW_token (d_model, 2C+1, 3)] from d_enc (B, T, d_model,
+ * 16-byte aligned), the raw batch and means / stdev of the forward; E_saved as the forward wrote it, or NULL to form E again (the masks
+ * are re-derived either way).  The batch gets no gradient.  No atomics, per-workgroup partial sums added in a fixed order: same inputs,
+ * same bits.  ..._model_supported (host arithmetic only): input_len, pred_len >= 1, input_len + pred_len <= 256, 1 <= C <= 10 (the
+ * widths at which DataEmbedding takes immtsf_embed_forward), d_model % 4 == 0, 4 <= d_model <= 512; otherwise the calls return
+ * IMMTSF_EUNSUPPORTED.  ..._front_workspace_bytes: the partial sums of the backward (host arithmetic only; 0 for unsupported dimensions).
+ * tail: immtsf_informer_tail_forward / _backward on x (B, T, d_model) with the Lp normalised and projected rows at row_off .. row_off +
+ * Lp - 1 of every window (row_off + Lp <= T <= 512; dx exact zeros on every other row); y, row_mean, row_rstd, dparams and the workspace
+ * (immtsf_informer_tail_workspace_bytes(B, Lp, C, d_model)) as there. */
+int immtsf_timesnet_model_supported(int32_t input_len, int32_t pred_len, int32_t C, int32_t d_model);
+size_t immtsf_timesnet_front_workspace_bytes(int32_t B, int32_t input_len, int32_t pred_len, int32_t C, int32_t d_model);
+int immtsf_timesnet_front_forward(int32_t B, int32_t L, int32_t input_len, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model,
+                                  const float* data, const float* mask, const float* tp, const float* tpp, const float* W_token,
+                                  const float* pe, const float* W_predict, const float* b_predict, float* means, float* stdev, float* enc,
+                                  float* E_save, float p_drop, uint64_t seed, uint64_t site, const uint64_t* seed_step_dev,
+                                  immtsf_stream_t stream);
+int immtsf_timesnet_front_backward(int32_t B, int32_t L, int32_t input_len, int32_t Lp, int32_t pred_len, int32_t C, int32_t d_model,
+                                   const float* data, const float* mask, const float* tp, const float* tpp, const float* W_token,
+                                   const float* pe, const float* W_predict, const float* means, const float* stdev, const float* E_saved,
+                                   const float* d_enc, float* dparams, float p_drop, uint64_t seed, uint64_t site,
+                                   const uint64_t* seed_step_dev, void* workspace, size_t workspace_bytes, immtsf_stream_t stream);
+int immtsf_timesnet_tail_forward(int32_t B, int32_t Lp, int32_t T, int32_t row_off, int32_t C, int32_t d_model, const float* x,
+                                 const float* gamma, const float* beta, float eps, const float* W, const float* bias, const float* means,
+                                 const float* stdev, float* y, float* row_mean, float* row_rstd, immtsf_stream_t stream);
+int immtsf_timesnet_tail_backward(int32_t B, int32_t Lp, int32_t T, int32_t row_off, int32_t C, int32_t d_model, const float* x,
+                                  const float* gamma, const float* beta, const float* W, const float* stdev, const float* row_mean,
+                                  const float* row_rstd, const float* dy, float* dx, float* dparams, void* workspace, size_t workspace_bytes,
+                                  immtsf_stream_t stream);
+
 /* ---- device-side batch builder: the reference's collate functions over a dataset that is
  * resident in HBM.  Replaces lib/parse_datasets.py:252-295 (variable_time_collate_fn), :298-366 +
  * lib/utils.py:359-413 (patch_variable_time_collate_fn / split_and_patch_batch) and :764-824 (multimodal wrapper).

@@ -9,9 +9,15 @@ warming both paths: alternating passes of `--iters` eager steps each, then alter
 microseconds per step for both paths in both modes (best pass, and all passes) and the number of kernel nodes of each graph (read from
 the graph itself; the library's timing tap does not see torch's kernels).
 
+With --model the two paths differ in what is AROUND the TimesBlock loop instead (the period selection stays on its default):
+  fused   config.timesnet_model_fused on: the front end one HIP launch (csrc/timesnet_model.hip) and the output tail one, two each backward;
+  torch   IMMTSF_TIMESNET_MODEL_FUSED=0: pad / instance norm / cat / DataEmbedding / cat / permuted predict_linear, and layer_norm + projection
+          over all rows + de-normalisation + slice.
+IMMTSF_TIMESNET_MODEL_SAVE_E=1 makes the fused front end keep its embedded rows for the backward instead of forming them again.
+
 The driver (no --one) runs every shape as a child process under its own time limit and stops at the first that fails.
 
-usage: python tools/timesnet_bench.py [--iters 200] [--passes 3] [--limit 240] [--out FILE]
+usage: python tools/timesnet_bench.py [--model] [--iters 200] [--passes 3] [--limit 240] [--out FILE]
 """
 import argparse
 import json
@@ -67,9 +73,12 @@ def count_kernels(graph):
     return count(ctypes.c_void_p(graph.raw_cuda_graph()))
 
 
-def make(shape, B=None, seed=0):
+KNOBS = {False: "timesnet_spectrum_fused", True: "timesnet_model_fused"}      # --model -> the config attribute the two paths differ in
+
+
+def make(shape, B=None, seed=0, model=False):
     """-> (models {path: TimesNet}, step(path) -> forecast: one forward + backward of that path's model on one fixed batch).  Both models
-    start from the same parameters."""
+    start from the same parameters.  model: the paths differ in config.timesnet_model_fused instead of config.timesnet_spectrum_fused."""
     import torch
     from immtsf import config
     from models.TimesNet import TimesNet
@@ -92,13 +101,17 @@ def make(shape, B=None, seed=0):
         models[name] = TimesNet(cfg).to(dev).train()
 
     def step(name):
-        was = config.timesnet_spectrum_fused
-        config.timesnet_spectrum_fused = name == "fused"
+        knob = KNOBS[bool(model)]
+        was, bound = getattr(config, knob), config.timesnet_model_max_work
+        setattr(config, knob, name == "fused")
+        if model:
+            config.timesnet_model_max_work = None      # the kernels at every shape: this tool is what the routing bound is read from
         try:
             out = models[name].forecasting(tpp, data, tp, mask)
             (out * up).sum().backward()
         finally:
-            config.timesnet_spectrum_fused = was
+            setattr(config, knob, was)
+            config.timesnet_model_max_work = bound
         return out
 
     return models, step
@@ -129,9 +142,9 @@ def spectrum_calls(model):
     return sum(blk.spectrum_calls for blk in model.model)
 
 
-def one(shape, iters, passes):
+def one(shape, iters, passes, model=False):
     import torch
-    models, step = make(shape)
+    models, step = make(shape, model=model)
 
     def timed(fn, n):
         torch.cuda.synchronize()
@@ -142,7 +155,10 @@ def one(shape, iters, passes):
         return (time.perf_counter() - t0) * 1e6 / n
 
     graphs = {name: capture(models, step, name)[0] for name in PATHS}
-    assert spectrum_calls(models["fused"]) > 0 and spectrum_calls(models["torch"]) == 0
+    if model:
+        assert models["fused"].fused_calls > 0 and models["torch"].fused_calls == 0
+    else:
+        assert spectrum_calls(models["fused"]) > 0 and spectrum_calls(models["torch"]) == 0
     eager = {n: [] for n in PATHS}
     replay = {n: [] for n in PATHS}
     for _ in range(passes):
@@ -152,7 +168,7 @@ def one(shape, iters, passes):
         for name in PATHS:
             replay[name].append(timed(graphs[name].replay, iters))
     s = SHAPES[shape]
-    line = {"tool": "timesnet_bench", "shape": shape, **s, "T": s["input_len"] + s["pred_len"], "precision": "fp32", "iters": iters,
+    line = {"tool": "timesnet_bench", "what": "model stages" if model else "period selection", "shape": shape, **s, "T": s["input_len"] + s["pred_len"], "precision": "fp32", "iters": iters,
             "passes": passes}
     for name in PATHS:
         line[f"{name}_eager_us"] = round(min(eager[name]), 2)
@@ -173,13 +189,14 @@ def main():
     ap.add_argument("--limit", type=int, default=240, help="seconds a child process may take")
     ap.add_argument("--one", default=None, choices=sorted(SHAPES), help="run this shape in this process")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--model", action="store_true", help="the fused front end and tail against IMMTSF_TIMESNET_MODEL_FUSED=0")
     args = ap.parse_args()
     if args.one is not None:
-        return one(args.one, args.iters, args.passes)
+        return one(args.one, args.iters, args.passes, args.model)
     lines = []
     for shape in SHAPES:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--one", shape, "--iters", str(args.iters),
-               "--passes", str(args.passes)]
+               "--passes", str(args.passes)] + (["--model"] if args.model else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(r.stdout)
         sys.stdout.flush()
